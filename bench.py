@@ -20,10 +20,16 @@ substrata_amd/scenes.py) dropped on the ground quad.  The measured state is PINN
     each leg starts from a fresh world built from the snapshot + PRIME_STEPS (24) untimed steps that rebuild the contact cache and
              let the launch plan settle, then the same W warm-up steps:
       timed      K steps, barrier + synchronize on both sides                           -> value, ms_per_step
+    with --full, after the timed leg:
       read-back  the application's real loop, every step followed by the active-pose read-back (reported next to the headline)
       profiled   P steps with HIP events around every launch on the world's stream      -> roofline, kernel_ms_per_step
       cpu        the CPU oracle (a port, NOT Jolt) built from the same snapshot, 1 untimed + C timed steps -> cpu_baseline
     The simulation is deterministic, so every GPU leg walks through the very same states; `checks` in the JSON asserts it.
+
+A plain run (no --full) sets up, warms up, times the K steps and prints the headline line; the other legs (and, at N > 1 or config 4, the
+profiled steps and the CPU baseline) run only with --full.  --dump-outputs DIR writes the body states the timed world holds after its last
+timed step (pos, rot, lin_vel, ang_vel, active; float32, one DIR/<field>.npy each; at most 64 MB, beyond that a fixed seeded sample of the
+bodies whose indices are in DIR/sample_index.npy).  Tiles of N > 1 ranks write DIR/<field>_rank<r>.npy.
 
 N > 1: BASELINE config 4, the 1M-box lattice (100^3, spacing 1.25 m, seed 4) STRONG-scaled over N spatial tiles of the 3-D grid
 2x1x1 / 2x2x1 / 2x2x2 (substrata_amd/tiles.py), one process per GPU, ghost bodies exchanged once per step by sgp_tiles_exchange (RCCL
@@ -80,7 +86,28 @@ def parse():
     ap.add_argument("--retile-every", type=int, default=16, help="config4 on N > 1 GPUs: move the tiles' split planes to the quantiles of bodies + contacts every this many steps (0: static split)")
     ap.add_argument("--force-comm", action="store_true", help="N = 1 with --workload config4: build the process group and the RCCL communicator anyway "
                     "(one rank), so that a one-GPU box runs the very code path of N > 1")
+    ap.add_argument("--full", action="store_true", help="also run the legs beyond the headline: active-pose read-back, profiled steps (roofline, "
+                    "kernel_ms_per_step), the CPU baseline and the bit-exact check against the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the body states after the last timed step as DIR/<field>.npy (float32)")
     return ap.parse_args()
+
+
+DUMP_BYTES = 64 << 20
+DUMP_FIELDS = ("pos", "rot", "lin_vel", "ang_vel", "active")
+
+
+def dump_outputs(dirname, states, suffix="", budget=DUMP_BYTES):
+    """--dump-outputs: what a caller reads back after the timed path's last step, the body states, one float32 .npy per field.  Beyond
+    `budget` bytes a fixed seeded sample of the bodies is written, its indices (float64) in sample_index<suffix>.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    per_body = 4 * sum(int(np.prod(states.dtype[f].shape)) for f in DUMP_FIELDS)
+    if len(states) * per_body > budget:
+        k = (budget - 1024) // (per_body + 8)        # (1024: the .npy headers)
+        idx = np.sort(np.random.default_rng(20260101).choice(len(states), size=k, replace=False))
+        np.save(os.path.join(dirname, f"sample_index{suffix}.npy"), idx.astype(np.float64))
+        states = states[idx]
+    for f in DUMP_FIELDS:
+        np.save(os.path.join(dirname, f"{f}{suffix}.npy"), np.ascontiguousarray(states[f], dtype=np.float32))
 
 
 def single_gpu_reference(workload, lattice):
@@ -376,9 +403,13 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
         st = w.stats()
-        n_prof = max(1, args.profile_steps)
-        prof = profile_leg(w, n_prof, exchange=(ex.exchange if ex is not None else None))
-        roof, roof_solver, kernel_ms = rooflines(prof, n_prof, w.desc.settings.num_velocity_steps, pmc, same_workload_as_profiles=False)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, w.read_states(0, w.num_bodies()), suffix=(f"_rank{rank}" if world_size > 1 else ""),
+                         budget=DUMP_BYTES // max(1, world_size))
+        if args.full:
+            n_prof = max(1, args.profile_steps)
+            prof = profile_leg(w, n_prof, exchange=(ex.exchange if ex is not None else None))
+            roof, roof_solver, kernel_ms = rooflines(prof, n_prof, w.desc.settings.num_velocity_steps, pmc, same_workload_as_profiles=False)
         ex_ms = ((ex_after.total_exchange_ms - ex_before.total_exchange_ms) / max(1, ex_after.exchanges - ex_before.exchanges)) if ex is not None else 0.0
         local = np.array([w.num_bodies() - 1 - (ex.last_imported if ex else 0), st.num_manifolds, st.num_active,
                           ex.last_exported if ex else 0, ex.last_imported if ex else 0, st.pairs_dropped + st.manifolds_dropped,
@@ -391,7 +422,7 @@ def main():
         else:
             allv = local[None, :]
         cpu_base = None
-        if n_gpus == 1 and ex is None and not args.no_cpu_baseline and args.cpu_steps > 0:
+        if args.full and n_gpus == 1 and ex is None and not args.no_cpu_baseline and args.cpu_steps > 0:
             # B2 beside config 4 on one GPU: the CPU port (oracle, NOT Jolt) on the state after the timed and profiled steps -- one untimed step
             # (contact cache) + two timed ones with 64 threads (a step of the collapsing 1M tower is several seconds of CPU work)
             from oracle import oracle
@@ -444,8 +475,9 @@ def main():
                     "route_retries_per_tile": [int(v) for v in allv[:, 9]], "host_side_imports_in_timed_steps_per_tile": [int(v) for v in allv[:, 10]],
                     "body_steps_per_s": steps_per_s * total_bodies,
                 },
-                "roofline": roof, "roofline_solver": roof_solver, "kernel_ms_per_step": kernel_ms, "cpu_baseline": cpu_base,
             }
+            if args.full:
+                out.update({"roofline": roof, "roofline_solver": roof_solver, "kernel_ms_per_step": kernel_ms, "cpu_baseline": cpu_base})
             if share_gpu and world_size > 1:
                 out["transport"] = "test stand-in"
                 out["note"] = "SGP_BENCH_SHARE_GPU=1: every rank ran on cuda:0 behind a test-only collective library -- a launch-path check, NOT a scaling number"
@@ -518,7 +550,36 @@ def main():
     elapsed = time.perf_counter() - t0
     st = w.stats()
     graph_replays, eager_steps, idle_steps = w.launch_counts()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, w.read_states(0, len(snap)))
     w.close()
+
+    steps_per_s = args.steps / elapsed
+    ms_per_step = 1000.0 * elapsed / args.steps
+    out = {
+        "metric": "physics steps/sec at fixed dt, 100k bodies" if workload == "config3" else "physics steps/sec at fixed dt, 1k cars + 50k debris",
+        "value": steps_per_s, "unit": "steps/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True,
+        # one GPU: nothing is scaled on this line.  `--gpus N` > 1 runs BASELINE config 4 (1M boxes) STRONG-scaled over N tiles and says "strong" on its own line.
+        "scaling": None, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {
+            "workload": (f"BASELINE config 3: {n_bodies} mixed box/sphere/capsule bodies, 100x100x{max(1, args.bodies // 10000)} lattice spacing 1.5 m, seed 3, "
+                         "ground quad 2000 m, dt 1/60, Jolt default settings (10 velocity / 2 position iterations), sleeping enabled")
+                        if workload == "config3" else
+                        ("BASELINE config 5: 1024 cars (32x32 grid, spacing 8 m; chassis = the 12-point convex hull of the car script, centre of mass lowered 0.2 m, 1200 kg, 4 wheels, "
+                         "FWD, Scripting.cpp defaults; input forward=1, steer=sin(0.5t+id) refreshed every step) + 50k unit-box debris, seed 5, dt 1/60"),
+            "state": f"pinned: {SETTLE_STEPS} untimed settle steps -> snapshot; every leg = fresh world from the snapshot + {PRIME_STEPS} priming steps + warm-up",
+            "bodies_per_gpu": n_bodies, "tiles": 1, "value_definition": "world steps/s",
+            "active_bodies_end": st.num_active, "contact_constraints_start": st_start.num_manifolds, "contact_constraints_end": st.num_manifolds,
+            "contact_points_end": st.num_contact_points, "colours_end": st.num_colours,
+            "contact_constraints_after_settle": settle_stats.num_manifolds,
+            "dropped_pairs_or_manifolds": st.pairs_dropped + st.manifolds_dropped,
+            "graph_replays_timed_world": graph_replays, "eager_steps_timed_world": eager_steps,
+        },
+    }
+    if not args.full:
+        emit_line(out)
+        return
 
     # ---- the application's real loop: every step followed by the read-back of the active bodies' poses ------
     # (GUIClient walks activated_obs after think(), GUIClient.cpp:6581-6723).  Reported next to the headline, never as `value`.
@@ -538,6 +599,8 @@ def main():
         n_read_back = len(active_states)
         st_rb = w.stats()
         w.close()
+    out["config"]["steps_per_s_with_active_pose_readback"] = readback_steps_per_s
+    out["config"]["bodies_read_back_per_step"] = n_read_back
 
     # ---- roofline: HIP events around every launch ------------------------------------------------------------------------
     n_prof = max(1, args.profile_steps)
@@ -549,33 +612,9 @@ def main():
     w.close()
     roof, roof_solver, kernel_ms = rooflines(prof, n_prof, vel_iters, pmc, same_workload_as_profiles=(workload == "config3" and args.bodies == 100000))
 
-    steps_per_s = args.steps / elapsed
-    ms_per_step = 1000.0 * elapsed / args.steps
     sum_kernel_ms = float(sum(kernel_ms.values()))
     profiled_step_ms = float(prof["total_ms"])      # first to last launch of a PROFILED step (eager launches, an event pair around each)
-    out = {
-        "metric": "physics steps/sec at fixed dt, 100k bodies" if workload == "config3" else "physics steps/sec at fixed dt, 1k cars + 50k debris",
-        "value": steps_per_s, "unit": "steps/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True,
-        # one GPU: nothing is scaled on this line.  `--gpus N` > 1 runs BASELINE config 4 (1M boxes) STRONG-scaled over N tiles and says "strong" on its own line.
-        "scaling": None, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {
-            "workload": (f"BASELINE config 3: {n_bodies} mixed box/sphere/capsule bodies, 100x100x{max(1, args.bodies // 10000)} lattice spacing 1.5 m, seed 3, "
-                         "ground quad 2000 m, dt 1/60, Jolt default settings (10 velocity / 2 position iterations), sleeping enabled")
-                        if workload == "config3" else
-                        ("BASELINE config 5: 1024 cars (32x32 grid, spacing 8 m; chassis = the 12-point convex hull of the car script, centre of mass lowered 0.2 m, 1200 kg, 4 wheels, "
-                         "FWD, Scripting.cpp defaults; input forward=1, steer=sin(0.5t+id) refreshed every step) + 50k unit-box debris, seed 5, dt 1/60"),
-            "state": f"pinned: {SETTLE_STEPS} untimed settle steps -> snapshot; every leg = fresh world from the snapshot + {PRIME_STEPS} priming steps + warm-up",
-            "bodies_per_gpu": n_bodies, "tiles": 1, "value_definition": "world steps/s",
-            "active_bodies_end": st.num_active, "contact_constraints_start": st_start.num_manifolds, "contact_constraints_end": st.num_manifolds,
-            "contact_points_end": st.num_contact_points, "colours_end": st.num_colours,
-            "contact_constraints_after_settle": settle_stats.num_manifolds,
-            "dropped_pairs_or_manifolds": st.pairs_dropped + st.manifolds_dropped,
-            "steps_per_s_with_active_pose_readback": readback_steps_per_s, "bodies_read_back_per_step": n_read_back,
-            "graph_replays_timed_world": graph_replays, "eager_steps_timed_world": eager_steps,
-        },
-        "roofline": roof, "roofline_solver": roof_solver, "kernel_ms_per_step": kernel_ms,
-    }
+    out.update({"roofline": roof, "roofline_solver": roof_solver, "kernel_ms_per_step": kernel_ms})
 
     # ---- the whole step against the roofline (SURVEY 8d's B_step with this step's own counts) ------------------------
     # B_step = 188 N (sweep) + 40 N (cell key + index, sorted read) + 96 P (pair gather 2 x 44 + pair id) + 132 M (manifold) + I_v C 192 + I_p C 104

@@ -6,12 +6,13 @@ variable -> class table, and for `name.Member` / `name->Member` with a Jolt-styl
 through a call chain (`GetWheel(i)->GetSettings()->mRadius`) are attributed by CHAINED_OWNER below.  Each (class, member) pair is then
 compiled as a probe against substrata_amd/shim/Jolt: a class has a member named M iff deriving from it AND from a struct that declares M
 makes `&Derived::M` ambiguous (works for overloaded and for data members alike).  Nothing of the reference is copied: the committed list
-holds (class, member) names only, and the first test keeps it in step with the tree where the tree exists."""
+holds (class, member) names only, and the first test derives it from what the scan finds in each caller file (declarations, uses, chained
+members: names only, stored in tests/golden/reference_callers.json); where the reference tree is present it scans the tree again and compares."""
+import json
 import os
 import re
 import subprocess
 
-import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHIM = os.path.join(ROOT, "substrata_amd", "shim")
@@ -96,21 +97,33 @@ WheeledVehicleController|WheeledVehicleControllerSettings:mEngine
 """.split()
 
 
-def extract():
-    texts, var_types = {}, {}
+GOLDEN = os.path.join(ROOT, "tests", "golden", "reference_callers.json")
+
+
+def scan_reference():
+    """What the patterns find in each caller file of the reference tree (comments stripped), as tests/golden/reference_callers.json stores it."""
+    out = {}
     for f in FILES:
         with open(os.path.join(REF, f), errors="replace") as fh:
             t = fh.read()
         t = re.sub(r"//[^\n]*", "", t)
         t = re.sub(r"/\*.*?\*/", "", t, flags=re.S)
-        texts[f] = t
-        for m in DECL.finditer(t):
-            cls = m.group(1) if not m.group(2) else m.group(1) + "::" + m.group(2)
-            var_types.setdefault(m.group(3), set()).add(ALIASES.get(cls, cls))
+        decls = {(m.group(3), m.group(1) if not m.group(2) else m.group(1) + "::" + m.group(2)) for m in DECL.finditer(t)}
+        uses = {(m.group(1), m.group(2)) for m in USE.finditer(t)}
+        out[f] = {"declarations": [list(x) for x in sorted(decls)], "uses": [list(x) for x in sorted(uses)],
+                  "chained": sorted({m.group(1) for m in CHAIN.finditer(t)})}
+    return out
+
+
+def extract(scan):
+    """(classes a variable may have | member) for every use the scan found: a variable -> class table from the declarations of all files first."""
+    var_types = {}
+    for d in scan.values():
+        for v, cls in d["declarations"]:
+            var_types.setdefault(v, set()).add(ALIASES.get(cls, cls))
     out = set()
-    for t in texts.values():
-        for m in USE.finditer(t):
-            v, mem = m.group(1), m.group(2)
+    for d in scan.values():
+        for v, mem in d["uses"]:
             if NOT_JOLT.match(mem):
                 continue
             if v in var_types:
@@ -119,15 +132,18 @@ def extract():
                 out.add(CHAINED_OWNER[mem] + ":" + mem)
             else:
                 out.add("?:" + mem)
-        for m in CHAIN.finditer(t):
-            mem = m.group(1)
+        for mem in d["chained"]:
             out.add(CHAINED_OWNER.get(mem, "?") + ":" + mem)
     return sorted(out)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree is not on this machine")
 def test_committed_member_list_is_what_the_reference_uses():
-    got = extract()
+    with open(GOLDEN) as fh:
+        stored = json.load(fh)["members"]
+    if os.path.isdir(REF):
+        assert scan_reference() == stored
+    assert sorted(stored) == sorted(FILES)
+    got = extract(stored)
     assert not [x for x in got if x.startswith("?:")], [x for x in got if x.startswith("?:")]      # every chained member has an owner
     assert got == sorted(COMMITTED)
 

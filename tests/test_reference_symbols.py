@@ -1,12 +1,12 @@
 """Tier 2 of the boundary, checked against the reference's own text: every `JPH::` name the six gui_client callers (and JoltUtils.h) use must
-exist in the look-alike set under substrata_amd/shim/Jolt.  The names are extracted from /root/reference at test time, so this test only
-runs where the reference tree is present (the authoring container); elsewhere it checks the committed list, which the first test keeps in
-step with the tree."""
+exist in the look-alike set under substrata_amd/shim/Jolt.  The names each caller file holds are stored, names only, in
+tests/golden/reference_callers.json; the first test derives the committed list from them, and where the reference tree is present it also
+extracts them again from the tree and compares."""
+import json
 import os
 import re
 import subprocess
 
-import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHIM = os.path.join(ROOT, "substrata_amd", "shim")
@@ -44,17 +44,25 @@ ALL_HEADERS = """#include <Jolt/Jolt.h>
 """
 
 
-def extract():
-    names = set()
+GOLDEN = os.path.join(ROOT, "tests", "golden", "reference_callers.json")
+
+
+def scan_reference():
+    """The JPH:: names of each caller file of the reference tree, as tests/golden/reference_callers.json stores them."""
+    names = {}
     for f in CALLER_FILES:
         with open(os.path.join(REF, f), errors="replace") as fh:
-            names.update(TOKEN.findall(fh.read()))
-    return sorted(names)
+            names[f] = sorted(set(TOKEN.findall(fh.read())))
+    return names
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree is not on this machine")
 def test_committed_list_is_what_the_reference_uses():
-    assert extract() == sorted(COMMITTED)
+    with open(GOLDEN) as fh:
+        stored = json.load(fh)["jph_names"]
+    if os.path.isdir(REF):
+        assert scan_reference() == stored
+    assert sorted(stored) == sorted(CALLER_FILES)
+    assert sorted(set().union(*map(set, stored.values()))) == sorted(COMMITTED)
 
 
 def test_every_jph_name_of_the_callers_exists_in_the_lookalikes():

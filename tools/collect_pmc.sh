@@ -9,7 +9,7 @@ rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
 	SGP_NO_GRAPH=1 timeout 900 rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$OUT/$c" -o pmc -- \
-		python "$REPO/bench.py" --steps 30 --warmup 20 --cpu-steps 0 --no-readback-leg "$@" > "$OUT/$c.log" 2>&1
+		python "$REPO/bench.py" --steps 30 --warmup 20 --cpu-steps 0 --no-readback-leg --full "$@" > "$OUT/$c.log" 2>&1
 	echo "$c pass: rc=$?"
 done
 f=$(find "$OUT/FETCH_SIZE" -name "*counter_collection.csv" | head -1)

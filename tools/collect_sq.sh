@@ -12,7 +12,7 @@ for set in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY" "SQ_ACTIVE_
            "TA_BUSY_avr TA_ADDR_STALLED_BY_TC_CYCLES_sum TA_DATA_STALLED_BY_TC_CYCLES_sum TCP_TCR_TCP_STALL_CYCLES_sum"; do
 	i=$((i + 1))
 	SGP_NO_GRAPH=1 timeout 600 rocprofv3 --pmc $set --kernel-trace --output-format csv -d "$OUT/pass$i" -o sq -- \
-		python "$REPO/bench.py" --steps 12 --warmup 8 --cpu-steps 0 --no-readback-leg --profile-steps 1 "$@" > "$OUT/pass$i.log" 2>&1
+		python "$REPO/bench.py" --steps 12 --warmup 8 --cpu-steps 0 --no-readback-leg --profile-steps 1 --full "$@" > "$OUT/pass$i.log" 2>&1
 	echo "pass $i ($set): rc=$?"
 done
 python "$REPO/tools/sq_summary.py" "$OUT" "$OUT/sq_summary.md"

@@ -1,9 +1,10 @@
-# SQ counters for the kernels of one step (k_bp_pairs, k_narrowphase, k_setup ...): where the wave cycles go
+# SQ counters for the kernels of one step (k_bp_pairs, k_narrowphase, k_setup ...): where the wave cycles go.  Usage: bash tools/experiments/pmc_bp_pairs.sh <output directory>
+OUT=$(realpath -m "${1:?usage: pmc_bp_pairs.sh <output directory>}"); mkdir -p "$OUT"
 R=$PWD; cd /tmp && export TMPDIR=/tmp
 for c in "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_WAVES"; do
-  rm -rf $R/gpurun_out/pmc_sq
-  SGP_NO_GRAPH=1 timeout 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $R/gpurun_out/pmc_sq -o pmc -- python $R/bench.py --steps 6 --warmup 6 --cpu-steps 0 --no-readback-leg --profile-steps 1 > $R/gpurun_out/pmc_sq.log 2>&1
-  f=$(find $R/gpurun_out/pmc_sq -name "*counter_collection.csv" | head -1)
+  rm -rf $OUT/pmc_sq
+  SGP_NO_GRAPH=1 timeout 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/pmc_sq -o pmc -- python $R/bench.py --steps 6 --warmup 6 --cpu-steps 0 --no-readback-leg --profile-steps 1 --full > $OUT/pmc_sq.log 2>&1
+  f=$(find $OUT/pmc_sq -name "*counter_collection.csv" | head -1)
   python - "$f" <<'PY'
 import csv, sys, collections
 acc = collections.defaultdict(lambda: collections.defaultdict(list))
@@ -15,4 +16,4 @@ for k, d in acc.items():
     print(k, {c: round(sum(v[len(v)//2:]) / max(1, len(v[len(v)//2:]))) for c, v in d.items()})
 PY
 done
-rm -rf $R/gpurun_out/pmc_sq
+rm -rf $OUT/pmc_sq
