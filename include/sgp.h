@@ -364,7 +364,7 @@ int  sgp_world_launch_counts(sgp_world* w, uint32_t* graph_replays_out, uint32_t
 const char* sgp_kernel_class_name(int k);
 /* sizeof() of ABI struct number `which` (order: settings, world_desc, body_desc, body_state, body_event, contact_event,
  * ray, hit, step_stats, step_profile, ghost_record, vehicle_desc, vehicle_input, vehicle_state, hull_info, capsule_query,
- * query_contact, mesh_info) so bindings can verify their layout. */
+ * query_contact, mesh_info, heightfield_desc) so bindings can verify their layout. */
 int  sgp_abi_sizeof(int which);
 /* activated_obs / newly_activated_obs maintenance + listener callbacks (PhysicsWorld.h:194-200). */
 int  sgp_world_drain_events(sgp_world* w, int kind, void* out, uint32_t cap, uint32_t* n_out);
@@ -458,6 +458,35 @@ int  sgp_mesh_destroy(sgp_world* w, uint32_t mesh_id);
  * stores the batch's material index there, PhysicsWorld.cpp:1032-1060), reported by ray hits.  NULL = all 0. */
 int  sgp_mesh_create_with_materials(sgp_world* w, const float* vertices_xyz, uint32_t num_vertices, const uint32_t* indices, uint32_t num_triangles,
                                     const uint32_t* triangle_materials, sgp_mesh_info* info_out);
+
+/* ---- height fields (JPH::HeightFieldShape, TerrainSystem.cpp:1300, PhysicsWorld.cpp:1086-1119) -----------------------------
+ * A W x W grid of heights that collides exactly like the triangle mesh of the same samples (docs/CONTRACT.md 4d), without the mesh's
+ * vertex, triangle and tree storage: triangles are found from the grid.  A field is an entry of the mesh table: bodies use it with
+ * SGP_SHAPE_MESH and shape[0] = mesh_id, and sgp_mesh_destroy / sgp_mesh_edge_flags take its id.  sgp_mesh_info reports W * W
+ * vertices, 2 (W - 1)^2 triangles, the number of 8 x 8-quad blocks as num_nodes, and the bounds of all vertices.
+ *   frame      heights run along local +y; the grid lies in local x-z.
+ *   samples    row-major: sample (x, z) is heights[z * W + x].
+ *   vertex     of sample (x, z), fp32, in exactly this order, no contraction:
+ *                ((spacing[0] * x + offset[0]) * scale[0], (h + offset[1]) * scale[1], (spacing[1] * z + offset[2]) * scale[2])
+ *              (offset, spacing: HeightFieldShapeSettings inOffset / inScale; scale: the object's scale, baked in as for meshes)
+ *              (with offset (0, 0, -quad_w (W - 1)) and spacing quad_w: the facade's triangulated chunk times the object's scale, bit for bit,
+ *              except that a sample of -0.0 becomes +0.0: -0.0 + 0.0 = +0.0)
+ *   triangles  the quad (x, z) has corners a = (x, z), b = (x + 1, z), c = (x, z + 1), d = (x + 1, z + 1); triangle 2 (z (W - 1) + x)
+ *              is (a, c, d) and triangle 2 (z (W - 1) + x) + 1 is (a, d, b); both face +y.
+ *   edges      active edges exactly as sgp_mesh_create finds them for that triangle list.
+ *   materials  optional, one word per quad (z (W - 1) + x), reported for both its triangles in sgp_hit::material; NULL = 0.
+ * SGP_ERR_INVALID unless W >= 2, every height is finite, spacing > 0, scale > 0 on every axis (a mirroring scale would turn the
+ * triangles inside out: use a mesh) and 2 (W - 1)^2 < 2^29.  No power-of-two or block-size rule. */
+typedef struct sgp_heightfield_desc {
+	const float*    heights;          /* sample_count * sample_count heights, row-major */
+	uint32_t        sample_count;     /* W */
+	float           offset[3];
+	float           spacing[2];       /* x, z */
+	float           scale[3];
+	uint32_t        reserved_;        /* must be 0 (SGP_ERR_INVALID otherwise) */
+	const uint32_t* quad_materials;   /* (W - 1)^2 words or NULL */
+} sgp_heightfield_desc;
+int  sgp_heightfield_create(sgp_world* w, const sgp_heightfield_desc* desc, sgp_mesh_info* info_out);
 
 /* ---- wheeled vehicles --------------------------------------------------------
  * Replaces JPH::VehicleConstraint + JPH::WheeledVehicleController + JPH::VehicleCollisionTesterCastSphere as CarPhysics

@@ -195,6 +195,11 @@ class MeshInfo(C.Structure):
     _fields_ = [("mesh_id", u32), ("num_vertices", u32), ("num_triangles", u32), ("num_nodes", u32), ("aabb_min", f32 * 3), ("aabb_max", f32 * 3)]
 
 
+class HeightfieldDesc(C.Structure):
+    _fields_ = [("heights", C.c_void_p), ("sample_count", u32), ("offset", f32 * 3), ("spacing", f32 * 2), ("scale", f32 * 3),
+                ("reserved_", u32), ("quad_materials", C.c_void_p)]
+
+
 class CapsuleQuery(C.Structure):
     _fields_ = [("pos", f32 * 3), ("rot", f32 * 4), ("radius", f32), ("half_height", f32), ("max_separation", f32),
                 ("ignore_id", u32), ("collidable_only", u32), ("movement", f32 * 3), ("active_edges", u32)]
@@ -213,14 +218,14 @@ class QueryContact(C.Structure):
 ABI_SIZEOF_ORDER = ["sgp_settings", "sgp_world_desc", "sgp_body_desc", "sgp_body_state", "sgp_body_event",
                     "sgp_contact_event", "sgp_ray", "sgp_hit", "sgp_step_stats", "sgp_step_profile", "sgp_ghost_record",
                     "sgp_vehicle_desc", "sgp_vehicle_input", "sgp_vehicle_state", "sgp_hull_info",
-                    "sgp_capsule_query", "sgp_query_contact", "sgp_mesh_info"]
+                    "sgp_capsule_query", "sgp_query_contact", "sgp_mesh_info", "sgp_heightfield_desc"]
 
 STRUCTS = {"sgp_settings": Settings, "sgp_world_desc": WorldDesc, "sgp_body_desc": BodyDesc,
            "sgp_body_state": BodyState, "sgp_body_event": BodyEvent, "sgp_contact_event": ContactEvent,
            "sgp_ray": Ray, "sgp_hit": Hit, "sgp_step_stats": StepStats, "sgp_step_profile": StepProfile,
            "sgp_ghost_record": GhostRecord, "sgp_vehicle_desc": VehicleDesc, "sgp_vehicle_input": VehicleInput,
            "sgp_vehicle_state": VehicleState, "sgp_hull_info": HullInfo, "sgp_capsule_query": CapsuleQuery,
-           "sgp_query_contact": QueryContact, "sgp_mesh_info": MeshInfo}
+           "sgp_query_contact": QueryContact, "sgp_mesh_info": MeshInfo, "sgp_heightfield_desc": HeightfieldDesc}
 
 body_desc_dtype = np.dtype(BodyDesc)
 body_state_dtype = np.dtype(BodyState)
@@ -320,6 +325,7 @@ PROTOTYPES = {
     "mesh_create": (C.c_int, [vp, vp, u32, vp, u32, P(MeshInfo)]),
     "mesh_create_with_materials": (C.c_int, [vp, vp, u32, vp, u32, vp, P(MeshInfo)]),
     "mesh_destroy": (C.c_int, [vp, u32]),
+    "heightfield_create": (C.c_int, [vp, P(HeightfieldDesc), P(MeshInfo)]),
     "mesh_edge_flags": (C.c_int, [vp, u32, vp, u32]),
     "hull_destroy": (C.c_int, [vp, u32]),
     "hull_create": (C.c_int, [vp, vp, u32, P(HullInfo)]),

@@ -5,10 +5,148 @@
 // ---- static triangle meshes ----------------------------------------------------------------------------------------
 #define MESH_CAND_CAP 192
 
+// One triangle of a mesh-table entry, whatever its kind: its corners (mesh frame), active-edge bits, index in the caller's order and user data.  `pos`: the
+// position in the tree-ordered triangle array of a triangle mesh, the triangle index itself for a height field (the vertex order and the expression of
+// include/sgp.h: the vertices of the field's triangulation bit for bit).  Every reader of triangles goes through here.
+struct MeshTri { v3 a, b, c; uint32_t edges, index, mat; };
+SGP_DEV float field_coord(const MeshHeader& mh, int axis, uint32_t i)       // axis 0: x of column i, 2: z of row i
+{
+	return axis == 0 ? (mh.spc[0] * (float)i + mh.off[0]) * mh.scl[0] : (mh.spc[1] * (float)i + mh.off[2]) * mh.scl[2];
+}
+SGP_DEV v3 field_vertex(const uint32_t* f, const MeshHeader& mh, uint32_t x, uint32_t z)      // (f: the field pool, DV::mesh_field)
+{
+	const float h = __uint_as_float(f[mh.field_off + z * mh.fw + x]);
+	return V3(field_coord(mh, 0, x), (h + mh.off[1]) * mh.scl[1], field_coord(mh, 2, z));
+}
+SGP_DEV MeshTri field_tri(const uint32_t* f, const MeshHeader& mh, uint32_t pos)
+{
+	MeshTri r;
+	const uint32_t q = pos >> 1, x = q % (mh.fw - 1u), z = q / (mh.fw - 1u);
+	const v3 pa = field_vertex(f, mh, x, z), pd = field_vertex(f, mh, x + 1u, z + 1u);
+	if (pos & 1u) { r.a = pa; r.b = pd; r.c = field_vertex(f, mh, x + 1u, z); }      // (a, d, b)
+	else { r.a = pa; r.b = field_vertex(f, mh, x, z + 1u); r.c = pd; }              // (a, c, d)
+	r.edges = (f[mh.field_off + mh.edge_off + (q >> 2)] >> (8u * (q & 3u) + 3u * (pos & 1u))) & 7u;
+	r.index = pos;
+	r.mat = mh.mat_off ? f[mh.field_off + mh.mat_off + q] : 0u;
+	return r;
+}
+SGP_DEV MeshTri mesh_tri(const DV& d, const MeshHeader& mh, uint32_t pos)
+{
+	if (mh.kind == MESH_KIND_FIELD) return field_tri(d.mesh_field, mh, pos);
+	MeshTri r;
+	const uint4 tri = d.mesh_tris[mh.tri_off + pos];
+	r.a = V3(d.mesh_verts[mh.vert_off + tri.x]); r.b = V3(d.mesh_verts[mh.vert_off + tri.y]); r.c = V3(d.mesh_verts[mh.vert_off + tri.z]);
+	r.edges = MESH_TRI_EDGES(tri.w); r.index = MESH_TRI_INDEX(tri.w); r.mat = d.mesh_tri_mat[mh.tri_off + pos];
+	return r;
+}
+SGP_DEV bool mesh_tri_overlaps(const MeshTri& t, v3 lo, v3 hi)      // the triangle's own bounds against [lo, hi]
+{
+	const v3 tlo = v3_min(v3_min(t.a, t.b), t.c), thi = v3_max(v3_max(t.a, t.b), t.c);
+	return !(thi.x < lo.x || tlo.x > hi.x || thi.y < lo.y || tlo.y > hi.y || thi.z < lo.z || tlo.z > hi.z);
+}
+// The quads [i0, i1] along axis 0 (x) or 2 (z) of a height field whose extent may overlap [lo, hi] on that axis: a superset (one quad of margin on each side
+// of the inverted vertex expression); false when none.
+SGP_DEV bool field_quad_span(const MeshHeader& mh, int axis, float lo, float hi, int& i0, int& i1)
+{
+	const int n = (int)mh.fw - 1;
+	const float sc = axis == 0 ? mh.scl[0] : mh.scl[2], of = axis == 0 ? mh.off[0] : mh.off[2], sp = axis == 0 ? mh.spc[0] : mh.spc[1];
+	const float f0 = (lo / sc - of) / sp, f1 = (hi / sc - of) / sp;
+	i0 = max((int)floorf(fmaxf(fminf(f0, (float)n + 2.0f), -2.0f)) - 1, 0);
+	i1 = min((int)floorf(fmaxf(fminf(f1, (float)n + 2.0f), -2.0f)) + 1, n - 1);
+	return i0 <= i1;
+}
+// The slab test of the path o + t dir, t in [t_lo, t_hi], against [lo, hi] grown by g (t by gt): the t range inside, false on a miss.  (Never rejects what the
+// tree walks' node tests accept: the same growth, by the bounds of a block or a cell instead of a node's.)
+SGP_DEV bool field_slab(v3 o, v3 dir, v3 lo, v3 hi, float g, float gt, float t_lo, float t_hi, float* ta, float* tb)
+{
+	float t0 = t_lo, t1 = t_hi;
+	const float lo3[3] = { lo.x - g, lo.y - g, lo.z - g }, hi3[3] = { hi.x + g, hi.y + g, hi.z + g }, o3[3] = { o.x, o.y, o.z }, d3[3] = { dir.x, dir.y, dir.z };
+	for (int a = 0; a < 3; ++a) {
+		if (fabsf(d3[a]) <= 1.0e-12f) { if (o3[a] < lo3[a] || o3[a] > hi3[a]) return false; }
+		else { float s0 = (lo3[a] - o3[a]) / d3[a], s1 = (hi3[a] - o3[a]) / d3[a]; if (s0 > s1) { const float tmp = s0; s0 = s1; s1 = tmp; } t0 = fmaxf(t0, s0 - gt); t1 = fminf(t1, s1 + gt); if (t0 > t1) return false; }
+	}
+	*ta = t0; *tb = t1;
+	return true;
+}
+SGP_DEV float field_growth(v3 lo, v3 hi) { return 1.0e-4f * (1.0f + fabsf(hi.x) + fabsf(hi.y) + fabsf(hi.z) + fabsf(lo.x) + fabsf(lo.y) + fabsf(lo.z)); }
+// The quads of height field mh that the path o + t dir, t in [0, *best], of a sphere of radius r can reach: the 8 x 8-quad blocks under the path's
+// footprint, nearest first along each axis, each tested with its y range, then its cells; visit(q) tests quad q's two triangles and may lower *best (read
+// again before every test).  The visiting order is not part of any answer: the callers keep the closest hit and, among equal ones, the lowest index.
+template <typename F> SGP_DEV void field_cast_walk(const uint32_t* f, const MeshHeader& mh, v3 o, v3 dir, float r, const float* best, F&& visit)
+{
+	const v3 flo = V3(mh.mnx, mh.mny, mh.mnz), fhi = V3(mh.mxx, mh.mxy, mh.mxz);
+	const float gf = field_growth(flo, fhi);
+	float ta, tb;
+	if (!field_slab(o, dir, flo, fhi, r + gf, gf, 0.0f, *best, &ta, &tb)) return;
+	const v3 pa = v3_add(o, v3_scale(dir, ta)), pb = v3_add(o, v3_scale(dir, tb));
+	const float m = r + gf;
+	int x0, x1, z0, z1;
+	if (!field_quad_span(mh, 0, fminf(pa.x, pb.x) - m, fmaxf(pa.x, pb.x) + m, x0, x1) || !field_quad_span(mh, 2, fminf(pa.z, pb.z) - m, fmaxf(pa.z, pb.z) + m, z0, z1)) return;
+	const int bx0 = x0 / FIELD_BLOCK, bx1 = x1 / FIELD_BLOCK, bz0 = z0 / FIELD_BLOCK, bz1 = z1 / FIELD_BLOCK;
+	const int n = (int)mh.fw - 1;
+	for (int jz = 0; jz <= bz1 - bz0; ++jz) {
+		const int bz = dir.z >= 0.0f ? bz0 + jz : bz1 - jz;
+		for (int jx = 0; jx <= bx1 - bx0; ++jx) {
+			const int bx = dir.x >= 0.0f ? bx0 + jx : bx1 - jx;
+			const float2 yr = make_float2(__uint_as_float(f[mh.field_off + mh.blk_off + 2u * ((uint32_t)bz * mh.nb + (uint32_t)bx)]), __uint_as_float(f[mh.field_off + mh.blk_off + 2u * ((uint32_t)bz * mh.nb + (uint32_t)bx) + 1u]));
+			const int cx0 = max(bx * FIELD_BLOCK, x0), cx1 = min(min(bx * FIELD_BLOCK + FIELD_BLOCK, n) - 1, x1), cz0 = max(bz * FIELD_BLOCK, z0), cz1 = min(min(bz * FIELD_BLOCK + FIELD_BLOCK, n) - 1, z1);
+			{
+				const v3 lo = V3(field_coord(mh, 0, (uint32_t)cx0), yr.x, field_coord(mh, 2, (uint32_t)cz0)), hi = V3(field_coord(mh, 0, (uint32_t)cx1 + 1u), yr.y, field_coord(mh, 2, (uint32_t)cz1 + 1u));
+				const float g = field_growth(lo, hi);
+				float s0, s1;
+				if (!field_slab(o, dir, lo, hi, r + g, g, 0.0f, *best, &s0, &s1)) continue;
+			}
+			for (int cz = cz0; cz <= cz1; ++cz) for (int cx = cx0; cx <= cx1; ++cx) {
+				const v3 a = field_vertex(f, mh, (uint32_t)cx, (uint32_t)cz), b = field_vertex(f, mh, (uint32_t)cx + 1u, (uint32_t)cz), c = field_vertex(f, mh, (uint32_t)cx, (uint32_t)cz + 1u), e = field_vertex(f, mh, (uint32_t)cx + 1u, (uint32_t)cz + 1u);
+				const v3 lo = v3_min(v3_min(a, b), v3_min(c, e)), hi = v3_max(v3_max(a, b), v3_max(c, e));
+				const float g = field_growth(lo, hi);
+				float s0, s1;
+				if (field_slab(o, dir, lo, hi, r + g, g, 0.0f, *best, &s0, &s1)) visit((uint32_t)cz * (uint32_t)n + (uint32_t)cx);
+			}
+		}
+	}
+}
+
+// A ray (ray = true: front faces, sgd_ray_tri_uv) or a swept sphere of radius r (sgd_cast_sphere_tri) against a height field, in the mesh frame: the closest
+// hit within max_t, on equal distance the lower triangle index (tri = 0xFFFFFFFF: none).  (Inline: as a call, the kernels that reach it were given the
+// whole register file and 120 more bytes of scratch per lane.)
+struct FieldCastHit { float t, u, v; uint32_t tri, mat; v3 n; };
+SGP_DEV FieldCastHit field_cast(const uint32_t* f, MeshHeader mh, v3 o, v3 dir, float r, float max_t, bool ray)
+{
+	FieldCastHit h; h.t = max_t; h.u = 0.0f; h.v = 0.0f; h.tri = 0xFFFFFFFFu; h.mat = 0u; h.n = V3(0.0f, 0.0f, 0.0f);
+	float best = max_t;
+	auto test = [&](const MeshTri& tr) {
+		float uv[2] = { 0.0f, 0.0f }; v3 nn = V3(0.0f, 0.0f, 0.0f);
+		const float tt = ray ? sgd_ray_tri_uv(o, dir, tr.a, tr.b, tr.c, best, uv) : sgd_cast_sphere_tri(o, dir, tr.a, tr.b, tr.c, best, r, &nn);
+		if (tt >= 0.0f && (tt < best || h.tri == 0xFFFFFFFFu || (tt == best && tr.index < h.tri))) {
+			best = tt; h.t = tt; h.tri = tr.index; h.mat = tr.mat; h.u = uv[0]; h.v = uv[1];
+			if (ray) { const v3 c = v3_cross(v3_sub(tr.b, tr.a), v3_sub(tr.c, tr.a)); h.n = v3_scale(c, 1.0f / v3_len(c)); } else h.n = nn;
+		}
+	};
+	field_cast_walk(f, mh, o, dir, ray ? 0.0f : r, &best, [&](uint32_t q) { test(field_tri(f, mh, 2u * q)); test(field_tri(f, mh, 2u * q + 1u)); });
+	return h;
+}
+
+// Triangles of a height field whose own bounds overlap the mesh-local box [llo, lhi], ascending (quad order is triangle order); capped (*overflow set).
+SGP_DEV int field_candidates(const DV& d, const MeshHeader& mh, v3 llo, v3 lhi, uint32_t* cand, bool* overflow)
+{
+	int n = 0; *overflow = false;
+	int x0, x1, z0, z1;
+	if (!field_quad_span(mh, 0, llo.x, lhi.x, x0, x1) || !field_quad_span(mh, 2, llo.z, lhi.z, z0, z1)) return 0;
+	for (int z = z0; z <= z1; ++z) for (int x = x0; x <= x1; ++x) for (uint32_t h = 0; h < 2u; ++h) {
+		const uint32_t t = 2u * ((uint32_t)z * (mh.fw - 1u) + (uint32_t)x) + h;
+		if (!mesh_tri_overlaps(mesh_tri(d, mh, t), llo, lhi)) continue;
+		if (n == MESH_CAND_CAP) { *overflow = true; return n; }
+		cand[n++] = t;
+	}
+	return n;
+}
+
 // Triangles of mesh body M (header mh, pose pos / R) whose tree leaves overlap the mesh-local box [llo, lhi]: indices (caller's order)
 // into cand[], ascending.  Returns the count (capped; *overflow set).
 SGP_DEV int mesh_candidates(const DV& d, const MeshHeader& mh, v3 llo, v3 lhi, uint32_t* cand, bool* overflow)
 {
+	if (mh.kind == MESH_KIND_FIELD) return field_candidates(d, mh, llo, lhi, cand, overflow);
 	int n = 0; *overflow = false;
 	uint32_t stack[48]; int sp = 0;
 	stack[sp++] = 0;
@@ -23,9 +161,9 @@ SGP_DEV int mesh_candidates(const DV& d, const MeshHeader& mh, v3 llo, v3 lhi, u
 	}
 	// order by the triangle's index in the caller's order (what the sequential reference walks): insertion sort on (orig, pos)
 	for (int i = 1; i < n; ++i) {
-		const uint32_t pos = cand[i]; const uint32_t key = MESH_TRI_INDEX(d.mesh_tris[mh.tri_off + pos].w);
+		const uint32_t pos = cand[i]; const uint32_t key = mesh_tri(d, mh, pos).index;
 		int j = i - 1;
-		while (j >= 0 && MESH_TRI_INDEX(d.mesh_tris[mh.tri_off + cand[j]].w) > key) { cand[j + 1] = cand[j]; --j; }
+		while (j >= 0 && mesh_tri(d, mh, cand[j]).index > key) { cand[j + 1] = cand[j]; --j; }
 		cand[j + 1] = pos;
 	}
 	return n;
@@ -53,8 +191,8 @@ SGP_DEV int collide_with_mesh(const DV& d, uint32_t mbody, const sgd_shape& X, v
 	const int nc = mesh_candidates(d, mh, llo, lhi, cand, dropped);
 	sgd_mesh_contacts mc; mc.ng = 0;
 	for (int k = 0; k < nc; ++k) {
-		const uint4 tri = d.mesh_tris[mh.tri_off + cand[k]];
-		const v3 a = V3(d.mesh_verts[mh.vert_off + tri.x]), b = V3(d.mesh_verts[mh.vert_off + tri.y]), c = V3(d.mesh_verts[mh.vert_off + tri.z]);
+		const MeshTri tr = mesh_tri(d, mh, cand[k]);
+		const v3 a = tr.a, b = tr.b, c = tr.c;
 		const v3 wa = v3_add(mpos, m33_mul(R, a)), wb = v3_add(mpos, m33_mul(R, b)), wc = v3_add(mpos, m33_mul(R, c));
 		const v3 tmin = V3(fminf(fminf(wa.x, wb.x), wc.x), fminf(fminf(wa.y, wb.y), wc.y), fminf(fminf(wa.z, wb.z), wc.z));
 		const v3 tmax = V3(fmaxf(fmaxf(wa.x, wb.x), wc.x), fmaxf(fmaxf(wa.y, wb.y), wc.y), fmaxf(fmaxf(wa.z, wb.z), wc.z));
@@ -104,7 +242,7 @@ SGP_DEV int mesh_candidates_found(const DV& d, const MeshHeader& mh, v3 llo, v3 
 		if (nd.count == 0) { if (sp + 2 <= 48) { stack[sp++] = nd.left; stack[sp++] = nd.right; } else *overflow = true; continue; }
 		for (uint32_t k = 0; k < nd.count; ++k) {
 			if (n == cap) { *overflow = true; break; }
-			found[n] = nd.left + k; key[n] = MESH_TRI_INDEX(d.mesh_tris[mh.tri_off + nd.left + k].w); ++n;
+			found[n] = nd.left + k; key[n] = mesh_tri(d, mh, nd.left + k).index; ++n;
 		}
 		if (n > stop_after) return n;
 	}
@@ -192,7 +330,8 @@ template <int MESH_GROUP, int KINDS = SGD_KINDS_ALL> SGP_DEV void mesh_pair_grou
 	// fine mesh: hundreds); the two frontiers live in the arrays the sort uses afterwards.  The SET found is that of the depth-first walk unless a table
 	// overflows -- then the answer depends on the order of the walk, and lane 0 repeats it depth-first (eight lanes per pair: it then gives up once it holds
 	// more than MESH_BIG_MIN -- the pair is passed on to the wave-per-pair launch; a table of 64 that overflowed says as much).
-	if (sub == 0) { L.n_front[0] = valid ? 1u : 0u; L.n_front[1] = 0u; L.n_found = 0u; L.redo = 0u; L.key[0] = 0u; L.mc.ng = 0; }
+	const bool field = valid && mh.kind == MESH_KIND_FIELD;      // (a height field has no tree: below)
+	if (sub == 0) { L.n_front[0] = (valid && !field) ? 1u : 0u; L.n_front[1] = 0u; L.n_found = 0u; L.redo = 0u; L.key[0] = 0u; L.mc.ng = 0; }
 	__syncthreads();
 	{
 		for (int level = 0; level < 64; ++level) {
@@ -216,6 +355,36 @@ template <int MESH_GROUP, int KINDS = SGD_KINDS_ALL> SGP_DEV void mesh_pair_grou
 			__syncthreads();
 		}
 	}
+	// A height field: the quads under the box, MESH_GROUP at a time in quad order, and of each quad the triangles whose own bounds overlap the box, packed in
+	// triangle order -- quad order is triangle order, so the list comes out ascending and needs no sort.  A subset of the tree's candidates for the same
+	// triangles (a leaf's box holds its triangles' boxes) that keeps every triangle the bounds filter below would keep: the same groups.
+	{
+		int x0 = 0, x1 = -1, z0 = 0, z1 = -1;
+		if (field && !(field_quad_span(mh, 0, llo.x, lhi.x, x0, x1) && field_quad_span(mh, 2, llo.z, lhi.z, z0, z1))) { x1 = -1; z1 = -1; }
+		const uint32_t nxq = (uint32_t)(x1 - x0 + 1), nq = (field && x1 >= x0 && z1 >= z0) ? nxq * (uint32_t)(z1 - z0 + 1) : 0u;
+		constexpr uint32_t cap = (uint32_t)MESH_LDS_T(MESH_GROUP, KINDS)::CAP, stop = MESH_GROUP == 64 ? cap : (uint32_t)MESH_BIG_MIN;      // (eight lanes: past MESH_BIG_MIN the pair is passed on)
+		int rounds = (int)((nq + MESH_GROUP - 1) / MESH_GROUP);
+#pragma unroll
+		for (int off = 32; off >= 1; off >>= 1) rounds = max(rounds, __shfl_xor(rounds, off, 64));
+		uint32_t n = 0u;
+		const unsigned long long below = (1ull << sub) - 1ull;
+		for (int rd = 0; rd < rounds; ++rd) {
+			const uint32_t k = (uint32_t)(rd * MESH_GROUP + sub);
+			bool k0 = false, k1 = false; uint32_t t = 0u;
+			if (k < nq && n <= stop) {
+				t = 2u * (((uint32_t)z0 + k / nxq) * (mh.fw - 1u) + (uint32_t)x0 + k % nxq);
+				k0 = mesh_tri_overlaps(mesh_tri(d, mh, t), llo, lhi); k1 = mesh_tri_overlaps(mesh_tri(d, mh, t + 1u), llo, lhi);
+			}
+			const unsigned long long b0 = MESH_GROUP == 64 ? __ballot(k0) : ((__ballot(k0) >> (grp * MESH_GROUP)) & ((1ull << (MESH_GROUP & 63)) - 1ull));
+			const unsigned long long b1 = MESH_GROUP == 64 ? __ballot(k1) : ((__ballot(k1) >> (grp * MESH_GROUP)) & ((1ull << (MESH_GROUP & 63)) - 1ull));
+			const uint32_t at = n + (uint32_t)(__popcll(b0 & below) + __popcll(b1 & below));
+			if (k0 && at < cap) L.cand[at] = t;
+			if (k1 && at + (k0 ? 1u : 0u) < cap) L.cand[at + (k0 ? 1u : 0u)] = t + 1u;
+			n += (uint32_t)(__popcll(b0) + __popcll(b1));
+		}
+		if (field && sub == 0) L.n_found = n;
+		if (field && MESH_GROUP == 64 && n > cap) dropped = true;
+	}
 	if (valid && L.redo && !(MESH_GROUP != 64 && L.n_found > (uint32_t)MESH_BIG_MIN)) {
 		if (sub == 0) L.n_found = (uint32_t)mesh_candidates_found(d, mh, llo, lhi, L.found, L.key, &dropped, MESH_GROUP == 64 ? MESH_BIG_CAP : MESH_BIG_MIN, MESH_LDS_T(MESH_GROUP, KINDS)::CAP);
 	}
@@ -228,10 +397,10 @@ template <int MESH_GROUP, int KINDS = SGD_KINDS_ALL> SGP_DEV void mesh_pair_grou
 		if (sub == 0) { const uint32_t kb = atomicAdd(&d.ctr->n_mesh_big, 1u); if (kb < d.cap_mesh_pairs) d.mesh_big[kb] = pair; else atomicAdd(&d.ctr->pairs_dropped, 1u); }      // (four lists feed this one: bounded like them, the excess is counted)
 		valid = false; nc = 0; dropped = false;
 	}
-	for (int i = sub; i < nc; i += MESH_GROUP) L.key[i] = MESH_TRI_INDEX(d.mesh_tris[mh.tri_off + L.found[i]].w);
+	if (!field) for (int i = sub; i < nc; i += MESH_GROUP) L.key[i] = mesh_tri(d, mh, L.found[i]).index;
 	__syncthreads();
-	// candidates in the order of the caller's triangle indices: the rank of a key is the number of smaller keys
-	for (int i = sub; i < nc; i += MESH_GROUP) {
+	// candidates in the order of the caller's triangle indices: the rank of a key is the number of smaller keys (a height field's are in order already)
+	if (!field) for (int i = sub; i < nc; i += MESH_GROUP) {
 		const uint32_t ki = L.key[i];
 		int rank = 0;
 		for (int j = 0; j < nc; ++j) rank += L.key[j] < ki ? 1 : 0;
@@ -252,8 +421,8 @@ template <int MESH_GROUP, int KINDS = SGD_KINDS_ALL> SGP_DEV void mesh_pair_grou
 			bool keep = false; uint32_t cand_k = 0u;
 			if (valid && k < nc) {
 				cand_k = L.cand[k];
-				const uint4 tri = d.mesh_tris[mh.tri_off + cand_k];
-				const v3 a = V3(d.mesh_verts[mh.vert_off + tri.x]), b = V3(d.mesh_verts[mh.vert_off + tri.y]), c = V3(d.mesh_verts[mh.vert_off + tri.z]);
+				const MeshTri tr = mesh_tri(d, mh, cand_k);
+				const v3 a = tr.a, b = tr.b, c = tr.c;
 				const v3 wa = v3_add(mpos, m33_mul(R, a)), wb = v3_add(mpos, m33_mul(R, b)), wc = v3_add(mpos, m33_mul(R, c));
 				const v3 tmin = V3(fminf(fminf(wa.x, wb.x), wc.x), fminf(fminf(wa.y, wb.y), wc.y), fminf(fminf(wa.z, wb.z), wc.z));
 				const v3 tmax = V3(fmaxf(fmaxf(wa.x, wb.x), wc.x), fmaxf(fmaxf(wa.y, wb.y), wc.y), fmaxf(fmaxf(wa.z, wb.z), wc.z));
@@ -277,13 +446,13 @@ template <int MESH_GROUP, int KINDS = SGD_KINDS_ALL> SGP_DEV void mesh_pair_grou
 		const int k = rd * MESH_GROUP + sub;
 		bool hit = false; sgd_manifold m; m.np = 0;
 		if (valid && k < nc) {
-			const uint4 tri = d.mesh_tris[mh.tri_off + L.key[k]];      // (the packed list: every entry passed the bounds test)
-			const v3 a = V3(d.mesh_verts[mh.vert_off + tri.x]), b = V3(d.mesh_verts[mh.vert_off + tri.y]), c = V3(d.mesh_verts[mh.vert_off + tri.z]);
+			const MeshTri tr = mesh_tri(d, mh, L.key[k]);      // (the packed list: every entry passed the bounds test)
+			const v3 a = tr.a, b = tr.b, c = tr.c;
 			{
 				sgd_tri_hull_t th; v3 cen, nrm;
 				sgd_tri_hull(a, b, c, &th, &cen, &nrm);
 				sgd_tri_view T; T.pos = v3_add(mpos, m33_mul(R, cen)); T.R = R; T.scale = V3(1.0f, 1.0f, 1.0f); T.h = &th;
-				hit = sgd_collide_tri<KINDS>(&X, &T, m33_mul(R, nrm), max_sep, &m, active_edges ? MESH_TRI_EDGES(tri.w) : 7u, movement, (KINDS & 2) ? &box_code : nullptr, lpoly) != 0;
+				hit = sgd_collide_tri<KINDS>(&X, &T, m33_mul(R, nrm), max_sep, &m, active_edges ? tr.edges : 7u, movement, (KINDS & 2) ? &box_code : nullptr, lpoly) != 0;
 			}
 		}
 		// the hits of this round into the pair's groups, in candidate order: in turn r every group of the wave merges its r-th hit (as many turns as the group

@@ -17,6 +17,23 @@ SGP_DEV float ray_body(const DV& d, uint32_t type, float4 sh, v3 pos, quat q, v3
 		const MeshHeader mh = d.meshes[(uint32_t)sh.x];
 		float best = max_t; uint32_t best_idx = 0xFFFFFFFFu; v3 bn = V3(0.0f, 0.0f, 0.0f);
 		const v3 inv = V3(fabsf(dl.x) > 1.0e-12f ? 1.0f / dl.x : 3.0e38f, fabsf(dl.y) > 1.0e-12f ? 1.0f / dl.y : 3.0e38f, fabsf(dl.z) > 1.0e-12f ? 1.0f / dl.z : 3.0e38f);
+		auto test = [&](const MeshTri& tr) {
+			float uv[2];
+			const float tt = sgd_ray_tri_uv(ol, dl, tr.a, tr.b, tr.c, best, uv);
+			if (tt >= 0.0f && (tt < best || best_idx == 0xFFFFFFFFu || (tt == best && tr.index < best_idx))) {
+				best = tt; best_idx = tr.index;
+				const v3 nn = v3_cross(v3_sub(tr.b, tr.a), v3_sub(tr.c, tr.a)); bn = v3_scale(nn, 1.0f / v3_len(nn));
+				sub->tri = tr.index; sub->mat = tr.mat; sub->u = uv[0]; sub->v = uv[1];
+			}
+		};
+		// a height field: the blocks and cells under the path (field_cast, out of line), no stack
+		if (mh.kind == MESH_KIND_FIELD) {
+			const FieldCastHit h = field_cast(d.mesh_field, mh, ol, dl, 0.0f, max_t, true);
+			if (h.tri == 0xFFFFFFFFu) return -1.0f;
+			sub->tri = h.tri; sub->mat = h.mat; sub->u = h.u; sub->v = h.v;
+			*n_out = m33_mul(R, h.n);
+			return h.t;
+		}
 		uint32_t stack[48]; int sp = 0;
 		stack[sp++] = 0;
 		while (sp > 0) {
@@ -32,17 +49,7 @@ SGP_DEV float ray_body(const DV& d, uint32_t type, float4 sh, v3 pos, quat q, v3
 			}
 			if (miss) continue;
 			if (nd.count == 0) { if (sp + 2 <= 48) { stack[sp++] = nd.left; stack[sp++] = nd.right; } continue; }
-			for (uint32_t k = 0; k < nd.count; ++k) {
-				const uint4 tri = d.mesh_tris[mh.tri_off + nd.left + k];
-				const v3 pa = V3(d.mesh_verts[mh.vert_off + tri.x]), pb = V3(d.mesh_verts[mh.vert_off + tri.y]), pc = V3(d.mesh_verts[mh.vert_off + tri.z]);
-				float uv[2];
-				const float tt = sgd_ray_tri_uv(ol, dl, pa, pb, pc, best, uv);
-				if (tt >= 0.0f && (tt < best || best_idx == 0xFFFFFFFFu || (tt == best && MESH_TRI_INDEX(tri.w) < best_idx))) {
-					best = tt; best_idx = MESH_TRI_INDEX(tri.w);
-					const v3 nn = v3_cross(v3_sub(pb, pa), v3_sub(pc, pa)); bn = v3_scale(nn, 1.0f / v3_len(nn));
-					sub->tri = MESH_TRI_INDEX(tri.w); sub->mat = d.mesh_tri_mat[mh.tri_off + nd.left + k]; sub->u = uv[0]; sub->v = uv[1];
-				}
-			}
+			for (uint32_t k = 0; k < nd.count; ++k) test(mesh_tri(d, mh, nd.left + k));
 		}
 		if (best_idx == 0xFFFFFFFFu) return -1.0f;
 		*n_out = m33_mul(R, bn);

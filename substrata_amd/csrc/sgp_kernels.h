@@ -85,7 +85,18 @@ struct BpGrid {
 };
 
 // One static triangle mesh in the pools.
-struct MeshHeader { uint32_t vert_off, nv, tri_off, nt, node_off, n_nodes; float mnx, mny, mnz, mxx, mxy, mxz; };
+// kind MESH_KIND_FIELD (sgp_heightfield_create): no vertices, triangles or tree; the field's words in mesh_field[field_off ...]: W * W heights, then
+// the edge bytes (one per quad: bits 0-2 triangle 2q, bits 3-5 triangle 2q + 1; four per word), then the quad materials (mat_off = 0: none), then per
+// 8 x 8-quad block the min and max local y of its vertices (float2).  Offsets are relative to field_off.
+#define MESH_KIND_TRIS 0u
+#define MESH_KIND_FIELD 1u
+#define FIELD_BLOCK 8
+struct MeshHeader {
+	uint32_t vert_off, nv, tri_off, nt, node_off, n_nodes; float mnx, mny, mnz, mxx, mxy, mxz;
+	uint32_t kind, fw, field_off, field_words, edge_off, mat_off, blk_off, nb;      // fw = W; nb = blocks per row
+	float off[3], spc[2], scl[3];
+};
+static_assert(sizeof(MeshHeader) % 16 == 0, "MeshHeader: 16-byte aligned");
 // Node of a mesh's bounding-volume tree (node 0 = root).  Inner node (count == 0): children `left`, `right`.  Leaf: triangles
 // [left, left + count) of the mesh's tree-ordered triangle array (uint4.w of a triangle = its index in the caller's order).
 struct MeshNode { float mnx, mny, mnz; uint32_t left; float mxx, mxy, mxz; uint32_t right; uint32_t count; uint32_t pad[3]; };
@@ -339,7 +350,7 @@ struct DV {
 	struct HullWork* hull_work;      // [cap_hull_pairs] pair + result of the axis search
 	// static triangle meshes: headers + pooled vertices / triangles / tree nodes (mesh frame = body frame)
 	const struct MeshHeader* meshes; uint32_t n_meshes;
-	const float4* mesh_verts; const uint4* mesh_tris; const uint32_t* mesh_tri_mat; const struct MeshNode* mesh_nodes;     // mesh_tri_mat: user data (material index) per tree-ordered triangle
+	const float4* mesh_verts; const uint4* mesh_tris; const uint32_t* mesh_tri_mat; const struct MeshNode* mesh_nodes; const uint32_t* mesh_field;     // mesh_tri_mat: user data (material index) per tree-ordered triangle
 	const LargeGrid* lgrid; const uint32_t* lg_start; const uint32_t* lg_items;      // the static large bodies' grid (cell c: items [lg_start[c], lg_start[c + 1]))
 	uint2* mesh_pairs; uint32_t cap_mesh_pairs; uint32_t* mesh_big;      // mesh_pairs: four lists of cap_mesh_pairs each (by the other body's shape); mesh_big: indices into mesh_pairs
 	// wheeled vehicles (sgp_device_vehicle.h): AoS, one record per vehicle slot

@@ -70,6 +70,7 @@ SGP_API int sgp_abi_sizeof(int which)
 	case 9: return (int)sizeof(sgp_step_profile); case 10: return (int)sizeof(sgp_ghost_record);
 	case 11: return (int)sizeof(sgp_vehicle_desc); case 12: return (int)sizeof(sgp_vehicle_input); case 13: return (int)sizeof(sgp_vehicle_state);
 	case 14: return (int)sizeof(sgp_hull_info); case 15: return (int)sizeof(sgp_capsule_query); case 16: return (int)sizeof(sgp_query_contact); case 17: return (int)sizeof(sgp_mesh_info);
+	case 18: return (int)sizeof(sgp_heightfield_desc);
 	default: return -1;
 	}
 }
@@ -261,6 +262,7 @@ SGP_API int sgp_world_destroy(sgp_world* w)
 	if (w->d_mesh_tris) hipFree(w->d_mesh_tris);
 	if (w->d_mesh_tri_mat) hipFree(w->d_mesh_tri_mat);
 	if (w->d_mesh_nodes) hipFree(w->d_mesh_nodes);
+	if (w->d_mesh_field) hipFree(w->d_mesh_field);
 	if (w->d_vehicles) hipFree(w->d_vehicles);
 	if (w->d_veh_inputs) hipFree(w->d_veh_inputs);
 	hipFree(w->d_veh_rows); hipFree(w->d_veh_head);

@@ -547,7 +547,11 @@ SGP_API int sgp_world_body_counts(sgp_world* w, sgp_body_counts* out)
 		const uint32_t mt = w->hb[id].flags & BF_MOTION_MASK;
 		if (mt == SGP_MOTION_DYNAMIC) out->num_active_dynamic++; else if (mt == SGP_MOTION_KINEMATIC) out->num_active_kinematic++;
 	}
-	for (size_t k = 1; k < w->meshes.size(); ++k) if (w->meshes[k].nt != 0) { out->num_meshes++; out->shape_bytes += sizeof(MeshHeader) + 16ull * w->meshes[k].nv + 16ull * w->meshes[k].nt + sizeof(MeshNode) * (uint64_t)w->meshes[k].n_nodes; }
+	for (size_t k = 1; k < w->meshes.size(); ++k) if (w->meshes[k].nt != 0) {
+		out->num_meshes++;
+		if (w->meshes[k].kind == MESH_KIND_FIELD) out->shape_bytes += sizeof(MeshHeader) + 4ull * w->meshes[k].field_words;      // (samples, edge bytes, materials, block ranges)
+		else out->shape_bytes += sizeof(MeshHeader) + 16ull * w->meshes[k].nv + 16ull * w->meshes[k].nt + sizeof(MeshNode) * (uint64_t)w->meshes[k].n_nodes;
+	}
 	for (size_t k = 1; k < w->hulls.size(); ++k) if (w->hulls[k].nv != 0) { out->num_hulls++; out->shape_bytes += sizeof(sgd_hull); }
 	return SGP_OK;
 }

@@ -134,10 +134,11 @@ struct sgp_world {
 	std::vector<MeshHeader> meshes; std::vector<float4> mesh_verts; std::vector<uint4> mesh_tris; std::vector<uint32_t> mesh_tri_mat; std::vector<MeshNode> mesh_nodes;
 	MeshHeader* d_meshes = nullptr; float4* d_mesh_verts = nullptr; uint4* d_mesh_tris = nullptr; uint32_t* d_mesh_tri_mat = nullptr; MeshNode* d_mesh_nodes = nullptr;
 	size_t cap_mesh_verts = 0, cap_mesh_tris = 0, cap_mesh_tri_mat = 0, cap_mesh_nodes = 0;
+	std::vector<uint32_t> mesh_field; uint32_t* d_mesh_field = nullptr; size_t cap_mesh_field = 0;      // height fields: samples, edge bytes, materials, block ranges (MeshHeader)
 	// shape lifecycle: bodies referencing each mesh / hull, ids and pool ranges of destroyed shapes waiting for reuse, table capacities (grown on demand)
 	std::vector<uint32_t> mesh_refs, hull_refs, free_mesh_ids, free_hull_ids;
 	uint32_t n_big_hulls = 0;      // live hulls of more than SGD_HULL_SMALL_VERTS vertices: their pairs go through k_narrowphase_hull_big (part of the step plan)
-	std::vector<std::pair<uint32_t, uint32_t>> free_vert_ranges, free_tri_ranges, free_node_ranges;      // (offset, length)
+	std::vector<std::pair<uint32_t, uint32_t>> free_vert_ranges, free_tri_ranges, free_node_ranges, free_field_ranges;      // (offset, length)
 	size_t cap_mesh_table = 0, cap_hull_table = 0;
 	std::vector<uint32_t> free_triples;                   // first slot of freed (mesh body + 2 alias) slot triples
 	// convex hull shapes: host copies of the device table (mass properties, radii) -- hull 0 is the +-1 cube template

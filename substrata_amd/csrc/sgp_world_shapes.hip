@@ -80,6 +80,30 @@ template <typename T> static int grow_table(sgp_world* w, T*& dev, size_t& cap, 
 // vertex indices: used by one triangle or by more than two -> active; by two -> inactive when concave or when their normals are within the threshold.
 // Doubles: the flags must come out the same wherever this runs (tests/test_mesh_parity_gpu.py compares them with the sequential CPU statement's).
 #define SGP_ACTIVE_EDGE_COS 0.99619469809f      // cos(5 degrees) as a float (MeshShapeSettings::mActiveEdgeCosThresholdAngle), widened to double for the test below
+static bool tri_normal_d(const float* a, const float* b, const float* c, double n[3])
+{
+	const double e1[3] = { (double)b[0] - a[0], (double)b[1] - a[1], (double)b[2] - a[2] }, e2[3] = { (double)c[0] - a[0], (double)c[1] - a[1], (double)c[2] - a[2] };
+	n[0] = e1[1] * e2[2] - e1[2] * e2[1]; n[1] = e1[2] * e2[0] - e1[0] * e2[2]; n[2] = e1[0] * e2[1] - e1[1] * e2[0];
+	const double l = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+	if (!(l > 1.0e-30)) return false;
+	n[0] /= l; n[1] /= l; n[2] /= l;
+	return true;
+}
+// The decision for one edge used by exactly two triangles: t1 = (a1, b1, c1) is the one of lower index, (va, vb) the edge in t1's winding, t2 the other.
+// false: the edge is inactive in both (concave, or convex within the threshold angle).  A degenerate triangle leaves it active.  (The mesh path's edge sort and
+// the height field's implicit neighbours both come here: the same flags for the same triangles.)
+static bool shared_edge_active(const float* a1, const float* b1, const float* c1, const float* a2, const float* b2, const float* c2, const float* va, const float* vb)
+{
+	double n1[3], n2[3];
+	if (!tri_normal_d(a1, b1, c1, n1) || !tri_normal_d(a2, b2, c2, n2)) return true;
+	const double d[3] = { (double)vb[0] - va[0], (double)vb[1] - va[1], (double)vb[2] - va[2] };
+	const double cos_threshold = (double)SGP_ACTIVE_EDGE_COS;
+	const double cosn = n1[0] * n2[0] + n1[1] * n2[1] + n1[2] * n2[2];
+	const double cx = n1[1] * n2[2] - n1[2] * n2[1], cy = n1[2] * n2[0] - n1[0] * n2[2], cz = n1[0] * n2[1] - n1[1] * n2[0];
+	if (cosn < -0.999848) return true;                                    // back to back
+	if (cx * d[0] + cy * d[1] + cz * d[2] < 0.0) return false;            // concave
+	return cosn < cos_threshold;                                          // convex: active beyond the threshold angle
+}
 static void mesh_active_edges(const float* verts, const uint32_t* idx, uint32_t nt, std::vector<uint8_t>& flags)
 {
 	struct Rec { uint32_t lo, hi, tri, k; };
@@ -87,31 +111,14 @@ static void mesh_active_edges(const float* verts, const uint32_t* idx, uint32_t 
 	flags.assign(nt, 7);
 	for (uint32_t t = 0; t < nt; ++t) for (uint32_t k = 0; k < 3; ++k) { const uint32_t a = idx[3 * t + k], b = idx[3 * t + (k + 1) % 3]; e[3 * (size_t)t + k] = Rec{ std::min(a, b), std::max(a, b), t, k }; }
 	std::sort(e.begin(), e.end(), [](const Rec& x, const Rec& y) { if (x.lo != y.lo) return x.lo < y.lo; if (x.hi != y.hi) return x.hi < y.hi; if (x.tri != y.tri) return x.tri < y.tri; return x.k < y.k; });
-	auto normal = [&](uint32_t t, double n[3]) {
-		const float* a = verts + 3 * idx[3 * t]; const float* b = verts + 3 * idx[3 * t + 1]; const float* c = verts + 3 * idx[3 * t + 2];
-		const double e1[3] = { (double)b[0] - a[0], (double)b[1] - a[1], (double)b[2] - a[2] }, e2[3] = { (double)c[0] - a[0], (double)c[1] - a[1], (double)c[2] - a[2] };
-		n[0] = e1[1] * e2[2] - e1[2] * e2[1]; n[1] = e1[2] * e2[0] - e1[0] * e2[2]; n[2] = e1[0] * e2[1] - e1[1] * e2[0];
-		const double l = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
-		if (!(l > 1.0e-30)) return false;
-		n[0] /= l; n[1] /= l; n[2] /= l;
-		return true;
-	};
-	const double cos_threshold = (double)SGP_ACTIVE_EDGE_COS;
+	auto vtx = [&](uint32_t t, uint32_t k) { return verts + 3 * idx[3 * t + k]; };
 	for (size_t i = 0; i < e.size(); ) {
 		size_t j = i + 1;
 		while (j < e.size() && e[j].lo == e[i].lo && e[j].hi == e[i].hi) ++j;
 		if (j - i == 2 && e[i].lo != e[i].hi) {
-			double n1[3], n2[3];
-			if (normal(e[i].tri, n1) && normal(e[i + 1].tri, n2)) {
-				const uint32_t va = idx[3 * e[i].tri + e[i].k], vb = idx[3 * e[i].tri + (e[i].k + 1) % 3];       // the edge in the first triangle's winding
-				const double d[3] = { (double)verts[3 * vb] - verts[3 * va], (double)verts[3 * vb + 1] - verts[3 * va + 1], (double)verts[3 * vb + 2] - verts[3 * va + 2] };
-				const double cosn = n1[0] * n2[0] + n1[1] * n2[1] + n1[2] * n2[2];
-				const double cx = n1[1] * n2[2] - n1[2] * n2[1], cy = n1[2] * n2[0] - n1[0] * n2[2], cz = n1[0] * n2[1] - n1[1] * n2[0];
-				bool active;
-				if (cosn < -0.999848) active = true;                                    // back to back
-				else if (cx * d[0] + cy * d[1] + cz * d[2] < 0.0) active = false;       // concave
-				else active = cosn < cos_threshold;                                     // convex: active beyond the threshold angle
-				if (!active) { flags[e[i].tri] &= (uint8_t)~(1u << e[i].k); flags[e[i + 1].tri] &= (uint8_t)~(1u << e[i + 1].k); }
+			const uint32_t t1 = e[i].tri, t2 = e[i + 1].tri;
+			if (!shared_edge_active(vtx(t1, 0), vtx(t1, 1), vtx(t1, 2), vtx(t2, 0), vtx(t2, 1), vtx(t2, 2), vtx(t1, e[i].k), vtx(t1, (e[i].k + 1) % 3))) {
+				flags[t1] &= (uint8_t)~(1u << e[i].k); flags[t2] &= (uint8_t)~(1u << e[i + 1].k);
 			}
 		}
 		i = j;
@@ -188,12 +195,103 @@ SGP_API int sgp_mesh_create_with_materials(sgp_world* w, const float* verts, uin
 	return SGP_OK;
 }
 
+// The vertex of sample (x, z) of a height field (include/sgp.h; the device's field_vertex is the same expression, and -ffp-contract=off keeps both as written)
+static inline void field_vertex_h(const MeshHeader& mh, uint32_t x, uint32_t z, float h, float out[3])
+{
+	out[0] = (mh.spc[0] * (float)x + mh.off[0]) * mh.scl[0]; out[1] = (h + mh.off[1]) * mh.scl[1]; out[2] = (mh.spc[1] * (float)z + mh.off[2]) * mh.scl[2];
+}
+
+// JPH::HeightFieldShapeSettings(...).Create() for a static terrain chunk: the samples, one edge byte and (optionally) one material word per quad and the y range
+// of each 8 x 8-quad block go to the field pool; there is no vertex list, no triangle list and no tree.  O(W^2).
+SGP_API int sgp_heightfield_create(sgp_world* w, const sgp_heightfield_desc* hd, sgp_mesh_info* info)
+{
+	if (w) ray_server_stop(w);      // (a resident ray server must not keep this call's stream work waiting: ADVICE r05)
+	if (!w || !hd || !info || !hd->heights || hd->reserved_ != 0u) return fail(SGP_ERR_INVALID, "sgp_heightfield_create: bad arguments");
+	const uint32_t W = hd->sample_count;
+	if (W < 2 || 2ull * (W - 1) * (W - 1) >= (1ull << 29)) return fail(SGP_ERR_INVALID, "sgp_heightfield_create: sample count out of range");
+	for (int a = 0; a < 3; ++a) if (!std::isfinite(hd->offset[a]) || !(hd->scale[a] > 0.0f) || !std::isfinite(hd->scale[a])) return fail(SGP_ERR_INVALID, "sgp_heightfield_create: offset / scale");
+	for (int a = 0; a < 2; ++a) if (!(hd->spacing[a] > 0.0f) || !std::isfinite(hd->spacing[a])) return fail(SGP_ERR_INVALID, "sgp_heightfield_create: spacing");
+	const size_t ns = (size_t)W * W;
+	for (size_t k = 0; k < ns; ++k) if (!std::isfinite(hd->heights[k])) return fail(SGP_ERR_INVALID, "sgp_heightfield_create: non-finite height");
+	hipSetDevice(w->device);
+	MeshHeader mh{};
+	mh.kind = MESH_KIND_FIELD; mh.fw = W;
+	mh.nv = (uint32_t)ns; mh.nt = 2u * (W - 1) * (W - 1);
+	for (int a = 0; a < 3; ++a) { mh.off[a] = hd->offset[a]; mh.scl[a] = hd->scale[a]; }
+	mh.spc[0] = hd->spacing[0]; mh.spc[1] = hd->spacing[1];
+	const uint32_t W1 = W - 1, nq = W1 * W1;
+	mh.nb = (W1 + FIELD_BLOCK - 1) / FIELD_BLOCK; mh.n_nodes = mh.nb * mh.nb;
+	mh.edge_off = (uint32_t)ns;
+	mh.mat_off = hd->quad_materials ? mh.edge_off + (nq + 3) / 4 : 0u;
+	mh.blk_off = mh.edge_off + (nq + 3) / 4 + (hd->quad_materials ? nq : 0u);
+	mh.field_words = mh.blk_off + 2u * mh.n_nodes;
+	// vertices (once: the bounds, the block ranges and the edge decisions read them)
+	std::vector<float> v(3 * ns);
+	float mn[3] = { 3.4e38f, 3.4e38f, 3.4e38f }, mx[3] = { -3.4e38f, -3.4e38f, -3.4e38f };
+	for (uint32_t z = 0; z < W; ++z) for (uint32_t x = 0; x < W; ++x) {
+		float* p = &v[3 * ((size_t)z * W + x)];
+		field_vertex_h(mh, x, z, hd->heights[(size_t)z * W + x], p);
+		for (int a = 0; a < 3; ++a) { mn[a] = std::min(mn[a], p[a]); mx[a] = std::max(mx[a], p[a]); }
+	}
+	mh.mnx = mn[0]; mh.mny = mn[1]; mh.mnz = mn[2]; mh.mxx = mx[0]; mh.mxy = mx[1]; mh.mxz = mx[2];
+	std::vector<uint32_t> words(mh.field_words, 0u);
+	memcpy(words.data(), hd->heights, sizeof(float) * ns);
+	// active edges: the three pairs of each quad's neighbourhood (the diagonal; the left edge with the quad to the left; the bottom edge with the quad below),
+	// each decided by shared_edge_active with the triangle of lower index first -- what mesh_active_edges' sort pairs up for the triangulation
+	std::vector<uint8_t> ef(nq, 0x3F);
+	auto V = [&](uint32_t x, uint32_t z) { return &v[3 * ((size_t)z * W + x)]; };
+	for (uint32_t z = 0; z < W1; ++z) for (uint32_t x = 0; x < W1; ++x) {
+		const uint32_t q = z * W1 + x;
+		const float *a = V(x, z), *b = V(x + 1, z), *c = V(x, z + 1), *dd = V(x + 1, z + 1);
+		// triangle 2q = (a, c, d): edges a-c (0), c-d (1), d-a (2); triangle 2q + 1 = (a, d, b): edges a-d (0), d-b (1), b-a (2)
+		if (!shared_edge_active(a, c, dd, a, dd, b, dd, a)) ef[q] &= (uint8_t)~((1u << 2) | (1u << 3));
+		if (x > 0) {      // a-c of 2q with d'-b' = c-a of 2(q - 1) + 1 = (a', d', b') = (V(x-1, z), c, a)
+			const float* a0 = V(x - 1, z);
+			if (!shared_edge_active(a0, c, a, a, c, dd, c, a)) { ef[q - 1] &= (uint8_t)~(1u << 4); ef[q] &= (uint8_t)~1u; }
+		}
+		if (z > 0) {      // b-a of 2q + 1 with c'-d' = a-b of 2(q - W1) = (a', c', d') = (V(x, z-1), a, b)
+			const float* a0 = V(x, z - 1);
+			if (!shared_edge_active(a0, a, b, a, dd, b, a, b)) { ef[q - W1] &= (uint8_t)~(1u << 1); ef[q] &= (uint8_t)~(1u << 5); }
+		}
+	}
+	for (uint32_t q = 0; q < nq; ++q) words[mh.edge_off + q / 4] |= (uint32_t)ef[q] << (8 * (q % 4));
+	if (hd->quad_materials) memcpy(&words[mh.mat_off], hd->quad_materials, sizeof(uint32_t) * nq);
+	for (uint32_t bz = 0; bz < mh.nb; ++bz) for (uint32_t bx = 0; bx < mh.nb; ++bx) {
+		float lo = 3.4e38f, hi = -3.4e38f;
+		for (uint32_t z = bz * FIELD_BLOCK; z <= std::min((bz + 1) * FIELD_BLOCK, W1); ++z) for (uint32_t x = bx * FIELD_BLOCK; x <= std::min((bx + 1) * FIELD_BLOCK, W1); ++x) { lo = std::min(lo, V(x, z)[1]); hi = std::max(hi, V(x, z)[1]); }
+		const uint32_t b = mh.blk_off + 2u * (bz * mh.nb + bx);
+		memcpy(&words[b], &lo, 4); memcpy(&words[b + 1], &hi, 4);
+	}
+	mh.field_off = take_range(w->free_field_ranges, mh.field_words, w->mesh_field.size());
+	if (w->mesh_field.size() < (size_t)mh.field_off + mh.field_words) w->mesh_field.resize((size_t)mh.field_off + mh.field_words);
+	std::copy(words.begin(), words.end(), w->mesh_field.begin() + mh.field_off);
+	{ int r = grow_pool(w, w->d_mesh_field, w->cap_mesh_field, w->mesh_field.size(), w->cap_mesh_field); if (r != SGP_OK) return r; }
+	HIP_TRY(hipMemcpyAsync(w->d_mesh_field + mh.field_off, words.data(), sizeof(uint32_t) * mh.field_words, hipMemcpyHostToDevice, w->stream));
+	uint32_t id;
+	if (!w->free_mesh_ids.empty()) { id = w->free_mesh_ids.back(); w->free_mesh_ids.pop_back(); w->meshes[id] = mh; w->mesh_refs[id] = 0; }
+	else { id = (uint32_t)w->meshes.size(); w->meshes.push_back(mh); w->mesh_refs.push_back(0); }
+	{ int r = grow_table(w, w->d_meshes, w->cap_mesh_table, w->meshes.size()); if (r != SGP_OK) return r; }
+	w->dv.meshes = w->d_meshes;
+	HIP_TRY(hipMemcpyAsync(&w->d_meshes[id], &w->meshes[id], sizeof(MeshHeader), hipMemcpyHostToDevice, w->stream));
+	HIP_TRY(hipStreamSynchronize(w->stream));
+	w->dv.mesh_field = w->d_mesh_field; w->dv.n_meshes = (uint32_t)w->meshes.size();
+	invalidate_graphs(w);
+	memset(info, 0, sizeof(*info));
+	info->mesh_id = id; info->num_vertices = mh.nv; info->num_triangles = mh.nt; info->num_nodes = mh.n_nodes;
+	memcpy(info->aabb_min, mn, sizeof(mn)); memcpy(info->aabb_max, mx, sizeof(mx));
+	return SGP_OK;
+}
+
 // JPH::Ref<JPH::Shape> going out of scope: the mesh's table slot and pool ranges become reusable.  Refused while a body still uses it.
 // the active-edge bits of a mesh's triangles in the caller's triangle order (tests: compared with the sequential CPU statement's)
 SGP_API int sgp_mesh_edge_flags(sgp_world* w, uint32_t mesh_id, uint8_t* out, uint32_t cap)
 {
 	if (!w || !out || mesh_id < 1 || mesh_id >= w->meshes.size() || w->meshes[mesh_id].nt == 0) return fail(SGP_ERR_BAD_ID, "sgp_mesh_edge_flags: no such mesh");
 	const MeshHeader& mh = w->meshes[mesh_id];
+	if (mh.kind == MESH_KIND_FIELD) {
+		for (uint32_t t = 0; t < mh.nt && t < cap; ++t) out[t] = (uint8_t)((w->mesh_field[mh.field_off + mh.edge_off + (t >> 3)] >> (8 * ((t >> 1) & 3) + 3 * (t & 1))) & 7u);
+		return SGP_OK;
+	}
 	for (uint32_t k = 0; k < mh.nt; ++k) { const uint32_t wv = w->mesh_tris[mh.tri_off + k].w; const uint32_t t = wv & 0x1FFFFFFFu; if (t < cap) out[t] = (uint8_t)(wv >> 29); }
 	return SGP_OK;
 }
@@ -205,7 +303,8 @@ SGP_API int sgp_mesh_destroy(sgp_world* w, uint32_t id)
 	if (w->mesh_refs[id] != 0) return fail(SGP_ERR_REJECTED, "sgp_mesh_destroy: a body still uses the mesh");
 	hipSetDevice(w->device);
 	const MeshHeader mh = w->meshes[id];
-	give_range(w->free_vert_ranges, mh.vert_off, mh.nv); give_range(w->free_tri_ranges, mh.tri_off, mh.nt); give_range(w->free_node_ranges, mh.node_off, mh.n_nodes);
+	if (mh.kind == MESH_KIND_FIELD) give_range(w->free_field_ranges, mh.field_off, mh.field_words);
+	else { give_range(w->free_vert_ranges, mh.vert_off, mh.nv); give_range(w->free_tri_ranges, mh.tri_off, mh.nt); give_range(w->free_node_ranges, mh.node_off, mh.n_nodes); }
 	w->meshes[id] = MeshHeader{};
 	HIP_TRY(hipMemcpyAsync(&w->d_meshes[id], &w->meshes[id], sizeof(MeshHeader), hipMemcpyHostToDevice, w->stream));
 	HIP_TRY(hipStreamSynchronize(w->stream));

@@ -1,3 +1,4 @@
+#include <cmath>
 // See PhysicsObject.h.  Defaults: /root/reference/gui_client/PhysicsObject.cpp:25-60.
 #include "PhysicsObject.h"
 #include "PhysicsWorld.h"
@@ -8,6 +9,12 @@ js::AABBox PhysicsShape::getAABBOS() const
 	if (kind == 0) h = Vec4f(p[0], p[0], p[0], 0.f);
 	else if (kind == 1) h = Vec4f(p[0], p[1], p[2], 0.f);
 	else if (kind == 2) h = Vec4f(p[0], p[0], p[0] + p[1], 0.f);
+	else if (kind == 4 && mesh && mesh->field_w >= 2 && !mesh->heights.empty()) {      // a height field: the bounds of the vertices it stands for
+		const float z_offset = -mesh->quad_w * (float)(mesh->field_w - 1);
+		float hmn = 1e30f, hmx = -1e30f;
+		for (size_t i = 0; i < mesh->heights.size(); ++i) { hmn = std::fmin(hmn, mesh->heights[i]); hmx = std::fmax(hmx, mesh->heights[i]); }
+		return js::AABBox(Vec4f(0.f, hmn, z_offset, 1.f), Vec4f(mesh->quad_w * (float)(mesh->field_w - 1), hmx, mesh->quad_w * (float)(mesh->field_w - 1) + z_offset, 1.f));
+	}
 	else if (kind == 4 && mesh && !mesh->vertices.empty()) {
 		Vec4f mn(1e30f), mx(-1e30f);
 		for (size_t i = 0; i + 2 < mesh->vertices.size(); i += 3) for (int k = 0; k < 3; ++k) { const float c = mesh->vertices[i + k]; if (c < mn[k]) mn[k] = c; if (c > mx[k]) mx[k] = c; }

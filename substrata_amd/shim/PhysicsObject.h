@@ -43,6 +43,9 @@ struct PhysicsMeshData
 	std::vector<uint32_t> indices;      // 3 per triangle, counter-clockwise = front
 	std::vector<uint32_t> materials;    // per triangle: the material index a ray hit reports (JPH::IndexedTriangle::mMaterialIndex, PhysicsWorld.cpp:1032-1060); empty = all 0
 	std::vector<Instance> instances;
+	// a height field (createJoltHeightFieldShape): the field_w x field_w samples instead of vertices / indices (both empty), quad_w their spacing.  An
+	// instance is a native field (sgp_heightfield_create); a scale with a non-positive component gets the triangulation (it would mirror the triangles).
+	std::vector<float> heights; uint32_t field_w = 0; float quad_w = 0.f;
 };
 
 class PhysicsShape

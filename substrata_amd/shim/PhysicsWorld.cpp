@@ -134,19 +134,32 @@ PhysicsShape PhysicsWorld::createMeshShape(const std::vector<Vec3f>& vertices, c
 	return s;
 }
 
-PhysicsShape PhysicsWorld::createJoltHeightFieldShape(int vert_res, const std::vector<float>& heightfield, int width, float quad_w)
+// The triangulation a height field stands for (include/sgp.h): the vertices in the reference's shape space and the two triangles of each quad.
+static void triangulateField(const PhysicsMeshData& m, std::vector<float>& verts, std::vector<uint32_t>& tris)
 {
-	if (width < 2 || vert_res > width || (size_t)width * (size_t)width > heightfield.size()) throw glare::Exception("Error building Jolt heightfield shape: bad sample count");
+	const int width = (int)m.field_w; const float quad_w = m.quad_w;
 	const float z_offset = -quad_w * (float)(width - 1);
-	std::vector<Vec3f> verts; std::vector<uint32> tris;
-	verts.reserve((size_t)width * width);
-	for (int z = 0; z < width; ++z) for (int x = 0; x < width; ++x) verts.push_back(Vec3f(quad_w * (float)x, heightfield[(size_t)z * width + x], quad_w * (float)z + z_offset));
+	verts.clear(); tris.clear();
+	verts.reserve((size_t)width * width * 3);
+	for (int z = 0; z < width; ++z) for (int x = 0; x < width; ++x) { verts.push_back(quad_w * (float)x); verts.push_back(m.heights[(size_t)z * width + x]); verts.push_back(quad_w * (float)z + z_offset); }
 	for (int z = 0; z + 1 < width; ++z) for (int x = 0; x + 1 < width; ++x) {
 		const uint32 a = (uint32)(z * width + x), b = a + 1, c = a + (uint32)width, d = c + 1;      // a (x,z)  b (x+1,z)  c (x,z+1)  d (x+1,z+1)
 		tris.push_back(a); tris.push_back(c); tris.push_back(d);          // facing +y
 		tris.push_back(a); tris.push_back(d); tris.push_back(b);
 	}
-	return createMeshShape(verts, tris);
+}
+
+// The samples are kept, not a triangulation: each (world, scale) instance is a native height field (meshInstance).
+PhysicsShape PhysicsWorld::createJoltHeightFieldShape(int vert_res, const std::vector<float>& heightfield, int width, float quad_w)
+{
+	if (width < 2 || vert_res > width || (size_t)width * (size_t)width > heightfield.size()) throw glare::Exception("Error building Jolt heightfield shape: bad sample count");
+	PhysicsShape s; s.kind = 4;
+	s.mesh = std::make_shared<PhysicsMeshData>();
+	s.mesh->heights.assign(heightfield.begin(), heightfield.begin() + (size_t)width * width);
+	s.mesh->field_w = (uint32_t)width; s.mesh->quad_w = quad_w;
+	s.size_B = sizeof(PhysicsShape) + s.mesh->heights.size() * sizeof(float);
+	setJoltShape(s);
+	return s;
 }
 
 static PhysicsMeshData::Instance* meshInstance(sgp_world* world, const PhysicsShape& shape, const Vec3f& scale)
@@ -156,11 +169,24 @@ static PhysicsMeshData::Instance* meshInstance(sgp_world* world, const PhysicsSh
 		PhysicsMeshData::Instance& in = m.instances[i];
 		if (in.world == world && in.scale[0] == scale.x && in.scale[1] == scale.y && in.scale[2] == scale.z) return &in;
 	}
-	std::vector<float> v(m.vertices);
-	for (size_t i = 0; i + 2 < v.size(); i += 3) { v[i] *= scale.x; v[i + 1] *= scale.y; v[i + 2] *= scale.z; }
-	std::vector<uint32_t> idx(m.indices);
-	if (scale.x * scale.y * scale.z < 0.f) for (size_t i = 0; i + 2 < idx.size(); i += 3) std::swap(idx[i + 1], idx[i + 2]);      // a mirroring scale turns the triangles inside out
 	sgp_mesh_info info;
+	if (m.field_w >= 2 && scale.x > 0.f && scale.y > 0.f && scale.z > 0.f) {
+		// a height field: offset (0, 0, -quad_w (W - 1)) and spacing quad_w give the vertices of triangulateField times the scale, bit for bit
+		sgp_heightfield_desc hd; memset(&hd, 0, sizeof(hd));
+		hd.heights = m.heights.data(); hd.sample_count = m.field_w;
+		hd.offset[2] = -m.quad_w * (float)(m.field_w - 1);
+		hd.spacing[0] = hd.spacing[1] = m.quad_w;
+		hd.scale[0] = scale.x; hd.scale[1] = scale.y; hd.scale[2] = scale.z;
+		if (sgp_heightfield_create(world, &hd, &info) != SGP_OK) { reportShapeFailure("height field"); return nullptr; }
+		PhysicsMeshData::Instance in; in.world = world; in.scale[0] = scale.x; in.scale[1] = scale.y; in.scale[2] = scale.z; in.mesh_id = info.mesh_id; in.users = 0;
+		m.instances.push_back(in);
+		return &m.instances.back();
+	}
+	std::vector<float> v(m.vertices);
+	std::vector<uint32_t> idx(m.indices);
+	if (m.field_w >= 2) triangulateField(m, v, idx);      // (a height field under a mirroring or degenerate scale)
+	for (size_t i = 0; i + 2 < v.size(); i += 3) { v[i] *= scale.x; v[i + 1] *= scale.y; v[i + 2] *= scale.z; }
+	if (scale.x * scale.y * scale.z < 0.f) for (size_t i = 0; i + 2 < idx.size(); i += 3) std::swap(idx[i + 1], idx[i + 2]);      // a mirroring scale turns the triangles inside out
 	if (sgp_mesh_create_with_materials(world, v.data(), (uint32_t)(v.size() / 3), idx.data(), (uint32_t)(idx.size() / 3),
 		m.materials.size() == idx.size() / 3 ? m.materials.data() : nullptr, &info) != SGP_OK) { reportShapeFailure("mesh"); return nullptr; }
 	PhysicsMeshData::Instance in; in.world = world; in.scale[0] = scale.x; in.scale[1] = scale.y; in.scale[2] = scale.z; in.mesh_id = info.mesh_id; in.users = 0;
@@ -184,8 +210,9 @@ PhysicsShape PhysicsWorld::createScaledAndTranslatedShapeForShape(const PhysicsS
 	} else if (original_shape.kind == 4 && original_shape.mesh) {
 		s.mesh = std::make_shared<PhysicsMeshData>();
 		s.mesh->vertices = original_shape.mesh->vertices;
-		for (size_t i = 0; i < s.mesh->vertices.size(); ++i) s.mesh->vertices[i] = tr[i % 3] + sc[i % 3] * s.mesh->vertices[i];
 		s.mesh->indices = original_shape.mesh->indices;
+		if (original_shape.mesh->field_w >= 2) triangulateField(*original_shape.mesh, s.mesh->vertices, s.mesh->indices);      // (a height field: its triangles, decorated)
+		for (size_t i = 0; i < s.mesh->vertices.size(); ++i) s.mesh->vertices[i] = tr[i % 3] + sc[i % 3] * s.mesh->vertices[i];
 		s.mesh->materials = original_shape.mesh->materials;
 		if (scale.x * scale.y * scale.z < 0.f) for (size_t i = 0; i + 2 < s.mesh->indices.size(); i += 3) std::swap(s.mesh->indices[i + 1], s.mesh->indices[i + 2]);
 	} else throw glare::Exception("Error building Jolt shape: scale / translate decorators are implemented for convex hull and mesh shapes");
@@ -708,7 +735,7 @@ size_t PhysicsWorld::computeSizeBForShape(JPH::Ref<JPH::Shape> jolt_shape)
 {
 	if (!jolt_shape.GetPtr()) return 0;
 	size_t b = sizeof(JPH::Shape) + jolt_shape->hull_points.size() * sizeof(float);
-	if (jolt_shape->mesh) b += jolt_shape->mesh->vertices.size() * sizeof(float) + (jolt_shape->mesh->indices.size() + jolt_shape->mesh->materials.size()) * sizeof(uint32_t);
+	if (jolt_shape->mesh) b += (jolt_shape->mesh->vertices.size() + jolt_shape->mesh->heights.size()) * sizeof(float) + (jolt_shape->mesh->indices.size() + jolt_shape->mesh->materials.size()) * sizeof(uint32_t);
 	for (const JPH::Shape::SubShape& c : jolt_shape->children) b += computeSizeBForShape(JPH::Ref<JPH::Shape>(const_cast<JPH::Shape*>(c.shape.GetPtr())));
 	return b;
 }
@@ -716,7 +743,7 @@ size_t PhysicsWorld::computeSizeBForShape(const PhysicsShape& shape)
 {
 	size_t b = sizeof(PhysicsShape);
 	if (shape.hull) b += shape.hull->points.size() * sizeof(float);
-	if (shape.mesh) b += shape.mesh->vertices.size() * sizeof(float) + shape.mesh->indices.size() * sizeof(uint32_t);
+	if (shape.mesh) b += (shape.mesh->vertices.size() + shape.mesh->heights.size()) * sizeof(float) + shape.mesh->indices.size() * sizeof(uint32_t);
 	return b;
 }
 

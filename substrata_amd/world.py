@@ -277,6 +277,39 @@ class CWorld:
                         "mesh_create_with_materials")
         return info
 
+    def heightfield_create(self, heights, offset, spacing, scale=(1.0, 1.0, 1.0), quad_materials=None):
+        """HeightFieldShapeSettings(heights, offset, spacing).Create() for a static terrain chunk: a W x W array of heights (row z, column x),
+        heights along local +y.  Returns abi.MeshInfo: the field is an entry of the mesh table (SGP_SHAPE_MESH, shape[0] = mesh_id).
+        `spacing`: a number or (x, z); `quad_materials`: one word per quad, (W - 1) x (W - 1), or None."""
+        h = np.ascontiguousarray(heights, dtype=np.float32)
+        if h.ndim == 2:
+            if h.shape[0] != h.shape[1]:
+                raise ValueError(f"heightfield_create: heights must be square, got {h.shape}")
+            w = int(h.shape[0])
+        elif h.ndim == 1:
+            w = int(round(np.sqrt(h.size)))
+            if w * w != h.size:
+                raise ValueError(f"heightfield_create: {h.size} heights is not W * W")
+        else:
+            raise ValueError(f"heightfield_create: heights must be W x W or W * W values, got shape {h.shape}")
+        h = h.reshape(-1)
+        sp = (float(spacing), float(spacing)) if np.ndim(spacing) == 0 else tuple(float(x) for x in spacing)
+        d = abi.HeightfieldDesc()
+        d.heights = h.ctypes.data
+        d.sample_count = w
+        d.offset[:] = [float(x) for x in offset]
+        d.spacing[:] = sp
+        d.scale[:] = [float(x) for x in scale]
+        m = None
+        if quad_materials is not None:
+            m = np.ascontiguousarray(quad_materials, dtype=np.uint32).reshape(-1)
+            if w < 2 or m.size != (w - 1) * (w - 1):
+                raise ValueError(f"heightfield_create: {m.size} quad materials for a {w} x {w} field, (W - 1)^2 expected")
+            d.quad_materials = m.ctypes.data
+        info = abi.MeshInfo()
+        self._check(self._fn("heightfield_create")(self._h, C.byref(d), C.byref(info)), "heightfield_create")
+        return info
+
     def mesh_destroy(self, mesh_id):
         self._check(self._fn("mesh_destroy")(self._h, int(mesh_id)), "mesh_destroy")
 
