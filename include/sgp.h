@@ -714,6 +714,43 @@ int  sgp_world_device_array(sgp_world* w, int which, void** dev_ptr_out, uint32_
 /* hipStream_t the world launches on (as void*). */
 int  sgp_world_stream(sgp_world* w, void** stream_out);
 
+/* ---- world checkpoints: capture, rollback, restore (JPH::PhysicsSystem::SaveState / RestoreState with a StateRecorder) ---- */
+/* A checkpoint holds everything the next step, query or getter can observe of a world (docs/CONTRACT.md, "Checkpoints"): a step is a deterministic
+ * function of that state, so a world that is rolled back -- or restored into a fresh world, in this process or another -- continues bit for bit as the
+ * world that was never interrupted.  Capturing has no effect on the physics.  A checkpoint is opaque, owns device and host memory and belongs to the
+ * world that made it; sgp_checkpoint_write turns it into a pointer-free little-endian blob of this library's own, versioned format (no relation to
+ * Jolt's PhysicsScene stream) that sgp_world_restore loads into a world just created with the same sgp_world_desc.
+ * Worlds that hold ghost bodies (tiles) are refused.  Environment SGP_CHECKPOINT_FULL=1 (read at world creation): capture and rollback copy every
+ * device allocation of the world whole instead of the part the next step reads -- the obviously correct statement, same bits. */
+typedef struct sgp_checkpoint sgp_checkpoint;
+typedef struct sgp_checkpoint_info {
+	uint64_t device_bytes;          /* device memory the checkpoint holds                                                    */
+	uint64_t host_bytes;            /* host memory it holds (mirrors, pending events, shape tables and pools)                */
+	uint64_t blob_bytes;            /* what sgp_checkpoint_write writes                                                      */
+	uint64_t world_device_bytes;    /* the world's own device allocation, for comparison                                     */
+	uint64_t shape_bytes_copied;    /* shape-pool bytes the LAST capture into, or rollback from, this checkpoint moved        */
+	uint32_t num_bodies, high_slot, num_cached_contacts, num_vehicles, num_meshes, num_hulls, num_compounds;
+	uint32_t steps_taken;           /* steps the world had taken when it was captured                                        */
+} sgp_checkpoint_info;
+
+/* *io == NULL: creates a checkpoint; else overwrites *io in place, re-using its buffers.  Flushes pending edits first (as a step would). */
+int  sgp_world_checkpoint(sgp_world* w, sgp_checkpoint** io);
+/* w becomes exactly what it was at the capture: bodies, contact cache, vehicles, shapes, pending events, ids handed out afterwards.
+ * SGP_ERR_INVALID (world untouched) for a checkpoint made by another world.  A runtime failure on the way (SGP_ERR_HIP) leaves the world undefined:
+ * destroy it. */
+int  sgp_world_rollback(sgp_world* w, const sgp_checkpoint* cp);
+int  sgp_checkpoint_destroy(sgp_checkpoint* cp);      /* NULL: SGP_OK */
+int  sgp_checkpoint_get_info(const sgp_checkpoint* cp, sgp_checkpoint_info* out);
+/* out == NULL or cap too small: only *bytes_out is set (SGP_ERR_CAPACITY when out was given).  A checkpoint may outlive its world (get_info and destroy
+ * still work); writing it needs the world: SGP_ERR_INVALID once the world has been destroyed. */
+int  sgp_checkpoint_write(const sgp_checkpoint* cp, void* out, uint64_t cap, uint64_t* bytes_out);
+/* Into a world in which no body or shape has ever been created and whose desc equals the blob's; anything else, and every malformed blob
+ * (truncated, wrong magic or version, sizes that do not add up), is SGP_ERR_INVALID with the world untouched.  SGP_ERR_HIP (an allocation or a copy
+ * failed half way) leaves the world undefined: destroy it. */
+int  sgp_world_restore(sgp_world* fresh, const void* blob, uint64_t bytes);
+/* Validates a blob and reads its counts.  Host only: needs no device. */
+int  sgp_checkpoint_blob_info(const void* blob, uint64_t bytes, sgp_checkpoint_info* out);
+
 #ifdef __cplusplus
 }
 #endif

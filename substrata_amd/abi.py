@@ -215,17 +215,28 @@ class QueryContact(C.Structure):
                 ("userdata", u64)]
 
 
+class CheckpointInfo(C.Structure):
+    """sgp_checkpoint_info: what a world checkpoint (or its blob) holds."""
+    _fields_ = [("device_bytes", u64), ("host_bytes", u64), ("blob_bytes", u64), ("world_device_bytes", u64),
+                ("shape_bytes_copied", u64), ("num_bodies", u32), ("high_slot", u32), ("num_cached_contacts", u32),
+                ("num_vehicles", u32), ("num_meshes", u32), ("num_hulls", u32), ("num_compounds", u32), ("steps_taken", u32)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 ABI_SIZEOF_ORDER = ["sgp_settings", "sgp_world_desc", "sgp_body_desc", "sgp_body_state", "sgp_body_event",
                     "sgp_contact_event", "sgp_ray", "sgp_hit", "sgp_step_stats", "sgp_step_profile", "sgp_ghost_record",
                     "sgp_vehicle_desc", "sgp_vehicle_input", "sgp_vehicle_state", "sgp_hull_info",
-                    "sgp_capsule_query", "sgp_query_contact", "sgp_mesh_info", "sgp_heightfield_desc"]
+                    "sgp_capsule_query", "sgp_query_contact", "sgp_mesh_info", "sgp_heightfield_desc", "sgp_checkpoint_info"]
 
 STRUCTS = {"sgp_settings": Settings, "sgp_world_desc": WorldDesc, "sgp_body_desc": BodyDesc,
            "sgp_body_state": BodyState, "sgp_body_event": BodyEvent, "sgp_contact_event": ContactEvent,
            "sgp_ray": Ray, "sgp_hit": Hit, "sgp_step_stats": StepStats, "sgp_step_profile": StepProfile,
            "sgp_ghost_record": GhostRecord, "sgp_vehicle_desc": VehicleDesc, "sgp_vehicle_input": VehicleInput,
            "sgp_vehicle_state": VehicleState, "sgp_hull_info": HullInfo, "sgp_capsule_query": CapsuleQuery,
-           "sgp_query_contact": QueryContact, "sgp_mesh_info": MeshInfo, "sgp_heightfield_desc": HeightfieldDesc}
+           "sgp_query_contact": QueryContact, "sgp_mesh_info": MeshInfo, "sgp_heightfield_desc": HeightfieldDesc,
+           "sgp_checkpoint_info": CheckpointInfo}
 
 body_desc_dtype = np.dtype(BodyDesc)
 body_state_dtype = np.dtype(BodyState)
@@ -339,6 +350,14 @@ PROTOTYPES = {
     "vehicle_get_states": (C.c_int, [vp, u32, u32, vp]),
     "vehicle_reset_drivetrain": (C.c_int, [vp, u32, f32, f32]),
     "vehicle_enable_lean_controller": (C.c_int, [vp, u32, C.c_int]),
+    # world checkpoints
+    "world_checkpoint": (C.c_int, [vp, P(vp)]),
+    "world_rollback": (C.c_int, [vp, vp]),
+    "checkpoint_destroy": (C.c_int, [vp]),
+    "checkpoint_get_info": (C.c_int, [vp, P(CheckpointInfo)]),
+    "checkpoint_write": (C.c_int, [vp, vp, u64, P(u64)]),
+    "world_restore": (C.c_int, [vp, vp, u64]),
+    "checkpoint_blob_info": (C.c_int, [vp, u64, P(CheckpointInfo)]),
     # test/debug helper, not a facade entry point
     "world_dump_constraints": (C.c_int, [vp, vp, u32, P(u32)]),
 }
@@ -357,3 +376,21 @@ def bind(lib, prefix, names=None):
         fn.argtypes = args
         bound.append(name)
     return bound
+
+
+def blob_info(blob, lib=None, prefix="sgp_"):
+    """sgp_checkpoint_blob_info: validates a checkpoint blob and returns its counts as a dict.  Host only (no device needed)."""
+    if lib is None:
+        from . import lib as _l
+        lib = _l.load()
+    buf = bytes(blob)
+    info = CheckpointInfo()
+    fn = getattr(lib, prefix + "checkpoint_blob_info")
+    fn.restype, fn.argtypes = PROTOTYPES["checkpoint_blob_info"]
+    rc = fn(C.cast(C.c_char_p(buf), vp), len(buf), C.byref(info))
+    if rc != OK:
+        from .world import SgpError
+        msg = getattr(lib, prefix + "last_error")
+        msg.restype = C.c_char_p
+        raise SgpError(f"{prefix}checkpoint_blob_info failed: rc={rc} {(msg() or b'').decode()}")
+    return info.as_dict()

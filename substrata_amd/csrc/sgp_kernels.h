@@ -14,6 +14,7 @@
 //   sgp_k_queries.hip      A7     k_raycast, k_collide_capsules, k_spherecast
 //   sgp_k_edits.hip        A5/A6  k_apply_cmds, k_ghost_refresh, read-back
 //   sgp_k_tiles.hip        (e)    tile export / routing, re-tiling histograms
+//   sgp_k_checkpoint.hip          k_ckpt_copy: the segmented copy of sgp_world_checkpoint / sgp_world_rollback
 //   sgp_dev_*.h            device-inline functions shared between stage files (sgp_dev_all.h includes them in dependency order)
 // All body state is SoA float4 / 32-byte records in HBM; every per-body kernel is a coalesced 16 B/lane sweep.
 #pragma once
@@ -474,3 +475,12 @@ void launch_create_from_records(const DV& d, const sgp_ghost_record* recs, const
 #define GKEY_FLAGS_SHIFT 4
 #define GKEY_IN_REGION  (1u << 10)
 void launch_ghost_refresh_records(const DV& d, const sgp_ghost_record* recs, const uint32_t* ids, uint32_t n, hipStream_t s);
+
+// ---- world checkpoints (sgp_k_checkpoint.hip) ---------------------------------------------------------------------------------------------------------
+// The pieces one launch of the segmented copy moves, laid end to end in 16-byte units: piece i is units [start[i], start[i + 1]) and goes from src[i] to
+// dst[i] (both 16-byte aligned).  Travels as a kernel argument (about 3 KB).
+#define SGP_CKPT_MAX_SEGS 160
+struct CkptTable { uint32_t n; uint32_t start[SGP_CKPT_MAX_SEGS + 1]; const void* src[SGP_CKPT_MAX_SEGS]; void* dst[SGP_CKPT_MAX_SEGS]; };
+void launch_ckpt_copy(const CkptTable& t, uint32_t n_cus, hipStream_t s);
+// clears what the current broad-phase grid would leave for the next step to clear, and records that nothing is left (rollback / restore)
+void launch_ckpt_grid_reset(const DV& d, hipStream_t s);

@@ -14,5 +14,6 @@
 #include "sgp_k_queries.hip"
 #include "sgp_k_vehicle.hip"
 #include "sgp_k_tiles.hip"
+#include "sgp_k_checkpoint.hip"
 #include "experiments/sgp_solver_probe.inc"
 #include "experiments/sgp_tile_solver.inc"

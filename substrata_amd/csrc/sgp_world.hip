@@ -11,6 +11,14 @@
 thread_local std::string g_last_error;
 int g_device_count = -1;
 
+// Which worlds of this process exist (by serial): a checkpoint may outlive the world that made it, and must then not reach into it.
+static std::mutex g_worlds_mutex;
+static std::set<uint64_t> g_worlds;
+static uint64_t g_next_serial = 0;
+uint64_t world_register() { std::lock_guard<std::mutex> l(g_worlds_mutex); const uint64_t s = ++g_next_serial; g_worlds.insert(s); return s; }
+void world_unregister(uint64_t serial) { std::lock_guard<std::mutex> l(g_worlds_mutex); g_worlds.erase(serial); }
+bool world_alive(uint64_t serial) { std::lock_guard<std::mutex> l(g_worlds_mutex); return g_worlds.count(serial) != 0; }
+
 // ---------------------------------------------------------------------------------------------------------------
 // defaults (Jolt v5.3.0 PhysicsSettings; Substrata never overrides them)
 
@@ -70,7 +78,7 @@ SGP_API int sgp_abi_sizeof(int which)
 	case 9: return (int)sizeof(sgp_step_profile); case 10: return (int)sizeof(sgp_ghost_record);
 	case 11: return (int)sizeof(sgp_vehicle_desc); case 12: return (int)sizeof(sgp_vehicle_input); case 13: return (int)sizeof(sgp_vehicle_state);
 	case 14: return (int)sizeof(sgp_hull_info); case 15: return (int)sizeof(sgp_capsule_query); case 16: return (int)sizeof(sgp_query_contact); case 17: return (int)sizeof(sgp_mesh_info);
-	case 18: return (int)sizeof(sgp_heightfield_desc);
+	case 18: return (int)sizeof(sgp_heightfield_desc); case 19: return (int)sizeof(sgp_checkpoint_info);
 	default: return -1;
 	}
 }
@@ -162,7 +170,7 @@ SGP_API int sgp_world_create(const sgp_world_desc* desc, sgp_world** out)
 	{ void* q = nullptr; w->cap_hull_table = 64; HIP_TRY(hipMalloc(&q, sizeof(sgd_hull) * w->cap_hull_table)); HIP_TRY(hipMemsetAsync(q, 0, sizeof(sgd_hull) * w->cap_hull_table, w->stream)); w->d_hulls = (sgd_hull*)q; w->device_bytes += sizeof(sgd_hull) * w->cap_hull_table; }
 	d.hulls = w->d_hulls;
 	d.cap_hull_pairs = P / 4 + 1024; DEV_ALLOC(d.hull_pairs, d.cap_hull_pairs);
-	{ void* hw = nullptr; const size_t bytes = (size_t)d.cap_hull_pairs * 64; HIP_TRY(hipMalloc(&hw, bytes)); w->allocs.push_back(hw); w->device_bytes += bytes; d.hull_work = (HullWork*)hw; }      // sizeof(HullWork) = 56
+	{ void* hw = nullptr; const size_t bytes = (size_t)d.cap_hull_pairs * 64; HIP_TRY(hipMalloc(&hw, bytes)); w->allocs.push_back(hw); w->alloc_bytes[hw] = bytes; w->device_bytes += bytes; d.hull_work = (HullWork*)hw; }      // sizeof(HullWork) = 56
 	{
 		sgd_hull cube; sgd_hull_cube_template(&cube);
 		w->hulls.push_back(cube); w->hull_refs.push_back(1);      // (the cube template is never destroyed)
@@ -224,6 +232,8 @@ SGP_API int sgp_world_create(const sgp_world_desc* desc, sgp_world** out)
 	{ const char* e = getenv("SGP_NO_SMALL_WORLD"); if (e && e[0] == '1') w->use_small_world = false; }
 	{ const char* e = getenv("SGP_NO_RAY_SERVER"); if (e && e[0] == '1') w->ray_server_enabled = false; }      // (single rays then cost a launch + a sync each)
 	{ const char* e = getenv("SGP_NO_WAKE_ROUND"); if (e && e[0] == '1') w->use_wake_round = false; }      // (measurements only: the CPU statement has its own switch)
+	{ const char* e = getenv("SGP_CHECKPOINT_FULL"); if (e && e[0] == '1') w->checkpoint_full = true; }      // (checkpoints copy every device allocation whole: the A side of profiles/r08_checkpoint.md)
+	w->serial = world_register();
 	{ const char* e = getenv("SGP_DEBUG_FLAGS"); w->dv.dbg_flags = e ? (uint32_t)atoi(e) : 0u; }
 #ifdef SGP_EXPERIMENTS
 	{ const char* e = getenv("SGP_TILE_SOLVER"); if (e) w->use_tile_solver = atoi(e); }
@@ -250,6 +260,7 @@ SGP_API int sgp_world_create(const sgp_world_desc* desc, sgp_world** out)
 SGP_API int sgp_world_destroy(sgp_world* w)
 {
 	if (!w) return fail(SGP_ERR_INVALID, "sgp_world_destroy: NULL");
+	if (w->serial) world_unregister(w->serial);      // (its checkpoints can still be examined and destroyed, not written or rolled back to)
 	hipSetDevice(w->device);
 	ray_server_stop(w);
 	if (w->stream) hipStreamSynchronize(w->stream);
@@ -392,8 +403,8 @@ static int rebuild_large_grid(sgp_world* w)
 		uint32_t* ni = nullptr;
 		HIP_TRY(hipMalloc((void**)&ni, sizeof(uint32_t) * (size_t)w->cap_lg_items));
 		// (the previous buffer is freed here, after the synchronisation above: it used to be parked in `allocs` at every growth; advisor r03)
-		if (w->d_lg_items) { auto it = std::find(w->allocs.begin(), w->allocs.end(), (void*)w->d_lg_items); if (it != w->allocs.end()) w->allocs.erase(it); hipFree(w->d_lg_items); }
-		w->allocs.push_back(ni); w->device_bytes += sizeof(uint32_t) * (size_t)w->cap_lg_items;
+		if (w->d_lg_items) { auto it = std::find(w->allocs.begin(), w->allocs.end(), (void*)w->d_lg_items); if (it != w->allocs.end()) w->allocs.erase(it); w->alloc_bytes.erase((void*)w->d_lg_items); hipFree(w->d_lg_items); }
+		w->allocs.push_back(ni); w->alloc_bytes[ni] = sizeof(uint32_t) * (size_t)w->cap_lg_items; w->device_bytes += sizeof(uint32_t) * (size_t)w->cap_lg_items;
 		w->d_lg_items = ni; d.lg_items = ni;
 		invalidate_graphs(w);
 	}
@@ -764,11 +775,12 @@ static int step_impl(sgp_world* w, float dt, bool final_readback)
 		uint32_t lc[SGP_NUM_LAYERS]; memcpy(lc, st.layer_counts, sizeof(lc));
 		memset(&st, 0, sizeof(st));
 		st.num_bodies = nb_; memcpy(st.layer_counts, lc, sizeof(lc)); st.device_bytes = w->device_bytes;
-		w->idle_steps++; w->last_step_idle = true;
+		w->idle_steps++; w->last_step_idle = true; w->steps_taken++;
 		// (the contact cache stays as the last step with somebody awake left it: what wakes up later finds the contacts it fell asleep with)
 		return SGP_OK;
 	}
 	w->last_step_idle = false;
+	w->steps_taken++;
 	if (w->veh_inputs_dirty && w->n_vehicles) {
 		HIP_TRY(hipMemcpyAsync(w->d_veh_inputs, w->veh_inputs.data(), sizeof(sgp_vehicle_input) * w->n_vehicles, hipMemcpyHostToDevice, w->stream));
 		w->veh_inputs_dirty = false;

@@ -6,6 +6,7 @@
 //   sgp_world_queries.hip    rays, capsule queries, sphere casts
 //   sgp_world_tiles.hip      ghost import / export, the tile exchange over RCCL, re-tiling
 //   sgp_world_snapshots.hip  the network snapshot codec and the de-jitter queue (host only)
+//   sgp_world_checkpoint.hip capture, rollback, the checkpoint blob and restore
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -18,6 +19,9 @@
 #include <unordered_map>
 #include <map>
 #include <chrono>
+#include <memory>
+#include <mutex>
+#include <set>
 #include "sgp_kernels.h"
 #include "sgp_device_vehicle.h"
 #include "sgp_hull_build.h"
@@ -71,6 +75,13 @@ struct sgp_world {
 	hipStream_t capture_stream = nullptr;      // launch plans are captured here while the step they belong to already runs, issued eagerly, on `stream`
 	DV dv;
 	std::vector<void*> allocs;
+	std::unordered_map<void*, size_t> alloc_bytes;      // size of every entry of `allocs` (checkpoints: what a full copy moves, and the bound of every lean piece)
+	bool checkpoint_full = false;                        // SGP_CHECKPOINT_FULL=1
+	uint64_t serial = 0;                                 // which world of this process this is (a checkpoint names the world that made it)
+	uint64_t shape_epoch = 0, shape_epoch_counter = 0;   // every shape create / destroy gives the shape tables a new epoch (a number never used before in this world): a rollback
+	                                                     //   to a checkpoint of the current epoch leaves the shape pools alone; a rollback sets the epoch back, never the counter
+	std::shared_ptr<const struct CkptShapes> shape_snapshot;      // host copy of the shape tables and pools of `shape_epoch`, shared by the checkpoints of that epoch (made by the first of them)
+	uint32_t steps_taken = 0;
 	uint64_t device_bytes = 0;
 	// host mirrors
 	std::vector<HostBody> hb;
@@ -170,12 +181,13 @@ struct sgp_world {
 template <typename T> inline int dev_alloc(sgp_world* w, T*& p, size_t n)
 {
 	void* q = nullptr;
-	const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
+	const size_t bytes = (std::max<size_t>(n, 1) * sizeof(T) + 15) & ~size_t(15);      // whole 16-byte units: the checkpoint copy moves 16 bytes per lane
 	hipError_t e = hipMalloc(&q, bytes);
 	if (e != hipSuccess) return fail(SGP_ERR_HIP, "hipMalloc", e);
 	e = hipMemsetAsync(q, 0, bytes, w->stream);
 	if (e != hipSuccess) return fail(SGP_ERR_HIP, "hipMemsetAsync", e);
 	w->allocs.push_back(q);
+	w->alloc_bytes[q] = bytes;
 	w->device_bytes += bytes;
 	p = (T*)q;
 	return SGP_OK;
@@ -226,6 +238,11 @@ void invalidate_graphs(sgp_world* w);
 int flush_cmds(sgp_world* w);
 int collect_events(sgp_world* w, bool counters_fresh = false);
 int read_counters(sgp_world* w);
+// defined in sgp_world.hip: the worlds of this process that exist, by serial
+uint64_t world_register(); void world_unregister(uint64_t serial); bool world_alive(uint64_t serial);
+// defined in sgp_world_shapes.hip
+int ensure_vehicle_capacity(sgp_world* w, uint32_t need);      // grows the vehicle arrays (device pointers change: graphs are invalidated by the caller)
+int shapes_upload_all(sgp_world* w);                           // the host mirrors of the shape tables and pools -> the device (pools grow through the usual path), DV updated, graphs invalidated
 // defined in sgp_world_bodies.hip
 int add_one(sgp_world* w, const sgp_body_desc* d, uint32_t* id_out, bool ghost);
 int book_record_body(sgp_world* w, uint32_t* flags_io, uint64_t userdata, float radius, float volume, bool ghost, uint32_t* id_out);      // (the host's share of add_one for a body created on the device from a record)

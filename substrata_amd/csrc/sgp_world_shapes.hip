@@ -183,6 +183,7 @@ SGP_API int sgp_mesh_create_with_materials(sgp_world* w, const float* verts, uin
 	uint32_t id;
 	if (!w->free_mesh_ids.empty()) { id = w->free_mesh_ids.back(); w->free_mesh_ids.pop_back(); w->meshes[id] = mh; w->mesh_refs[id] = 0; }
 	else { id = (uint32_t)w->meshes.size(); w->meshes.push_back(mh); w->mesh_refs.push_back(0); }
+	w->shape_epoch = ++w->shape_epoch_counter;
 	{ int r = grow_table(w, w->d_meshes, w->cap_mesh_table, w->meshes.size()); if (r != SGP_OK) return r; }
 	w->dv.meshes = w->d_meshes;
 	HIP_TRY(hipMemcpyAsync(&w->d_meshes[id], &w->meshes[id], sizeof(MeshHeader), hipMemcpyHostToDevice, w->stream));
@@ -270,6 +271,7 @@ SGP_API int sgp_heightfield_create(sgp_world* w, const sgp_heightfield_desc* hd,
 	uint32_t id;
 	if (!w->free_mesh_ids.empty()) { id = w->free_mesh_ids.back(); w->free_mesh_ids.pop_back(); w->meshes[id] = mh; w->mesh_refs[id] = 0; }
 	else { id = (uint32_t)w->meshes.size(); w->meshes.push_back(mh); w->mesh_refs.push_back(0); }
+	w->shape_epoch = ++w->shape_epoch_counter;
 	{ int r = grow_table(w, w->d_meshes, w->cap_mesh_table, w->meshes.size()); if (r != SGP_OK) return r; }
 	w->dv.meshes = w->d_meshes;
 	HIP_TRY(hipMemcpyAsync(&w->d_meshes[id], &w->meshes[id], sizeof(MeshHeader), hipMemcpyHostToDevice, w->stream));
@@ -306,6 +308,7 @@ SGP_API int sgp_mesh_destroy(sgp_world* w, uint32_t id)
 	if (mh.kind == MESH_KIND_FIELD) give_range(w->free_field_ranges, mh.field_off, mh.field_words);
 	else { give_range(w->free_vert_ranges, mh.vert_off, mh.nv); give_range(w->free_tri_ranges, mh.tri_off, mh.nt); give_range(w->free_node_ranges, mh.node_off, mh.n_nodes); }
 	w->meshes[id] = MeshHeader{};
+	w->shape_epoch = ++w->shape_epoch_counter;
 	HIP_TRY(hipMemcpyAsync(&w->d_meshes[id], &w->meshes[id], sizeof(MeshHeader), hipMemcpyHostToDevice, w->stream));
 	HIP_TRY(hipStreamSynchronize(w->stream));
 	w->free_mesh_ids.push_back(id);
@@ -327,6 +330,7 @@ SGP_API int sgp_hull_create_com(sgp_world* w, const float* pts, uint32_t n, cons
 	uint32_t id;
 	if (!w->free_hull_ids.empty()) { id = w->free_hull_ids.back(); w->free_hull_ids.pop_back(); w->hulls[id] = h; w->hull_refs[id] = 0; }
 	else { id = (uint32_t)w->hulls.size(); w->hulls.push_back(h); w->hull_refs.push_back(0); }
+	w->shape_epoch = ++w->shape_epoch_counter;
 	{ int r = grow_table(w, w->d_hulls, w->cap_hull_table, w->hulls.size()); if (r != SGP_OK) return r; }
 	w->dv.hulls = w->d_hulls;
 	HIP_TRY(hipMemcpyAsync(&w->d_hulls[id], &w->hulls[id], sizeof(sgd_hull), hipMemcpyHostToDevice, w->stream));
@@ -353,6 +357,7 @@ SGP_API int sgp_hull_destroy(sgp_world* w, uint32_t id)
 	hipSetDevice(w->device);
 	if (w->hulls[id].nv > SGD_HULL_SMALL_VERTS) --w->n_big_hulls;
 	memset(&w->hulls[id], 0, sizeof(sgd_hull));
+	w->shape_epoch = ++w->shape_epoch_counter;
 	HIP_TRY(hipMemcpyAsync(&w->d_hulls[id], &w->hulls[id], sizeof(sgd_hull), hipMemcpyHostToDevice, w->stream));
 	HIP_TRY(hipStreamSynchronize(w->stream));
 	w->free_hull_ids.push_back(id);
@@ -518,6 +523,65 @@ static void vehicle_record_from_desc(sgd_vehicle* v, const sgp_vehicle_desc* d)
 
 static inline bool vehicle_live(const sgp_world* w, uint32_t id) { return w && id < w->n_vehicles && w->veh_alive[id]; }
 
+// Room for `need` vehicle slots on the device (the step's captured graphs carry the old pointers: the caller invalidates them)
+int ensure_vehicle_capacity(sgp_world* w, uint32_t need)
+{
+	while (need > w->cap_vehicles) {
+		const uint32_t nc = w->cap_vehicles ? w->cap_vehicles * 2 : 64;
+		sgd_vehicle* nv = nullptr; sgp_vehicle_input* ni = nullptr;
+		HIP_TRY(hipMalloc((void**)&nv, sizeof(sgd_vehicle) * nc));
+		HIP_TRY(hipMalloc((void**)&ni, sizeof(sgp_vehicle_input) * nc));
+		HIP_TRY(hipMemsetAsync(nv, 0, sizeof(sgd_vehicle) * nc, w->stream));
+		HIP_TRY(hipMemsetAsync(ni, 0, sizeof(sgp_vehicle_input) * nc, w->stream));
+		if (w->n_vehicles) HIP_TRY(hipMemcpyAsync(nv, w->d_vehicles, sizeof(sgd_vehicle) * w->n_vehicles, hipMemcpyDeviceToDevice, w->stream));
+		HIP_TRY(hipStreamSynchronize(w->stream));
+		// (the row export of the solver passes is rebuilt by every step's controller kernel: nothing to carry over)
+		const size_t row_bytes = sizeof(float4) * 16u * 4u * nc, head_bytes = sizeof(float4) * 5u * nc + sizeof(uint32_t) * (nc / 32u + 4u);      // (+ one bit per slot behind the heads: DV::veh_defer_bits)
+		float4* nr = nullptr; float4* nh = nullptr;
+		HIP_TRY(hipMalloc((void**)&nr, row_bytes));
+		HIP_TRY(hipMalloc((void**)&nh, head_bytes));
+		HIP_TRY(hipMemsetAsync(nr, 0, row_bytes, w->stream));
+		HIP_TRY(hipMemsetAsync(nh, 0, head_bytes, w->stream));
+		HIP_TRY(hipStreamSynchronize(w->stream));
+		const size_t per_vehicle = sizeof(sgd_vehicle) + sizeof(sgp_vehicle_input) + sizeof(float4) * (16u * 4u + 5u);
+		if (w->d_vehicles) { hipFree(w->d_vehicles); hipFree(w->d_veh_inputs); hipFree(w->d_veh_rows); hipFree(w->d_veh_head); w->device_bytes -= per_vehicle * w->cap_vehicles; }
+		w->d_vehicles = nv; w->d_veh_inputs = ni; w->d_veh_rows = nr; w->d_veh_head = nh; w->cap_vehicles = nc;
+		w->device_bytes += per_vehicle * nc;
+		w->veh_inputs_dirty = true;
+	}
+	w->dv.vehicles = w->d_vehicles; w->dv.vehicle_inputs = w->d_veh_inputs;
+	w->dv.veh_rows = w->d_veh_rows; w->dv.veh_head = w->d_veh_head; w->dv.veh_cap = w->cap_vehicles;
+	w->dv.veh_defer_bits = w->d_veh_head ? (uint32_t*)(w->d_veh_head + 5u * (size_t)w->cap_vehicles) : nullptr;
+	return SGP_OK;
+}
+
+// The host mirrors of the shape tables and pools are the truth (shapes are immutable once created): everything of them to the device.  Used when a rollback
+// crosses a shape create / destroy, and by sgp_world_restore.  Pools and tables grow through the same helpers the create calls use.
+int shapes_upload_all(sgp_world* w)
+{
+	{ int r = grow_pool(w, w->d_mesh_verts, w->cap_mesh_verts, w->mesh_verts.size(), (size_t)0); if (r != SGP_OK) return r; }
+	{ int r = grow_pool(w, w->d_mesh_tris, w->cap_mesh_tris, w->mesh_tris.size(), (size_t)0); if (r != SGP_OK) return r; }
+	{ int r = grow_pool(w, w->d_mesh_tri_mat, w->cap_mesh_tri_mat, w->mesh_tri_mat.size(), (size_t)0); if (r != SGP_OK) return r; }
+	{ int r = grow_pool(w, w->d_mesh_nodes, w->cap_mesh_nodes, w->mesh_nodes.size(), (size_t)0); if (r != SGP_OK) return r; }
+	{ int r = grow_pool(w, w->d_mesh_field, w->cap_mesh_field, w->mesh_field.size(), (size_t)0); if (r != SGP_OK) return r; }
+	{ int r = grow_table(w, w->d_meshes, w->cap_mesh_table, w->meshes.size()); if (r != SGP_OK) return r; }
+	{ int r = grow_table(w, w->d_hulls, w->cap_hull_table, w->hulls.size()); if (r != SGP_OK) return r; }
+	if (!w->mesh_verts.empty()) HIP_TRY(hipMemcpyAsync(w->d_mesh_verts, w->mesh_verts.data(), sizeof(float4) * w->mesh_verts.size(), hipMemcpyHostToDevice, w->stream));
+	if (!w->mesh_tris.empty()) HIP_TRY(hipMemcpyAsync(w->d_mesh_tris, w->mesh_tris.data(), sizeof(uint4) * w->mesh_tris.size(), hipMemcpyHostToDevice, w->stream));
+	if (!w->mesh_tri_mat.empty()) HIP_TRY(hipMemcpyAsync(w->d_mesh_tri_mat, w->mesh_tri_mat.data(), sizeof(uint32_t) * w->mesh_tri_mat.size(), hipMemcpyHostToDevice, w->stream));
+	if (!w->mesh_nodes.empty()) HIP_TRY(hipMemcpyAsync(w->d_mesh_nodes, w->mesh_nodes.data(), sizeof(MeshNode) * w->mesh_nodes.size(), hipMemcpyHostToDevice, w->stream));
+	if (!w->mesh_field.empty()) HIP_TRY(hipMemcpyAsync(w->d_mesh_field, w->mesh_field.data(), sizeof(uint32_t) * w->mesh_field.size(), hipMemcpyHostToDevice, w->stream));
+	// (table entries beyond the restored counts may describe shapes created after the capture: no body of the restored state names them)
+	HIP_TRY(hipMemcpyAsync(w->d_meshes, w->meshes.data(), sizeof(MeshHeader) * w->meshes.size(), hipMemcpyHostToDevice, w->stream));
+	HIP_TRY(hipMemcpyAsync(w->d_hulls, w->hulls.data(), sizeof(sgd_hull) * w->hulls.size(), hipMemcpyHostToDevice, w->stream));
+	HIP_TRY(hipStreamSynchronize(w->stream));      // (pageable host vectors)
+	w->dv.meshes = w->d_meshes; w->dv.hulls = w->d_hulls;
+	w->dv.mesh_verts = w->d_mesh_verts; w->dv.mesh_tris = w->d_mesh_tris; w->dv.mesh_tri_mat = w->d_mesh_tri_mat; w->dv.mesh_nodes = w->d_mesh_nodes; w->dv.mesh_field = w->d_mesh_field;
+	w->dv.n_meshes = (uint32_t)w->meshes.size(); w->dv.n_hulls = (uint32_t)w->hulls.size();
+	invalidate_graphs(w);
+	return SGP_OK;
+}
+
 SGP_API int sgp_vehicle_create(sgp_world* w, const sgp_vehicle_desc* d, uint32_t* id_out)
 {
 	if (w) ray_server_stop(w);      // (a resident ray server must not keep this call's stream work waiting: ADVICE r05)
@@ -528,30 +592,7 @@ SGP_API int sgp_vehicle_create(sgp_world* w, const sgp_vehicle_desc* d, uint32_t
 	uint32_t id = w->n_vehicles;
 	for (uint32_t k = 0; k < w->n_vehicles; ++k) if (!w->veh_alive[k]) { id = k; break; }     // lowest free slot
 	if (id == w->n_vehicles) {
-		if (w->n_vehicles == w->cap_vehicles) {
-			// grow the device arrays (the step's captured graphs carry the old pointers)
-			const uint32_t nc = w->cap_vehicles ? w->cap_vehicles * 2 : 64;
-			sgd_vehicle* nv = nullptr; sgp_vehicle_input* ni = nullptr;
-			HIP_TRY(hipMalloc((void**)&nv, sizeof(sgd_vehicle) * nc));
-			HIP_TRY(hipMalloc((void**)&ni, sizeof(sgp_vehicle_input) * nc));
-			HIP_TRY(hipMemsetAsync(nv, 0, sizeof(sgd_vehicle) * nc, w->stream));
-			HIP_TRY(hipMemsetAsync(ni, 0, sizeof(sgp_vehicle_input) * nc, w->stream));
-			if (w->n_vehicles) HIP_TRY(hipMemcpyAsync(nv, w->d_vehicles, sizeof(sgd_vehicle) * w->n_vehicles, hipMemcpyDeviceToDevice, w->stream));
-			HIP_TRY(hipStreamSynchronize(w->stream));
-			// (the row export of the solver passes is rebuilt by every step's controller kernel: nothing to carry over)
-			const size_t row_bytes = sizeof(float4) * 16u * 4u * nc, head_bytes = sizeof(float4) * 5u * nc + sizeof(uint32_t) * (nc / 32u + 4u);      // (+ one bit per slot behind the heads: DV::veh_defer_bits)
-			float4* nr = nullptr; float4* nh = nullptr;
-			HIP_TRY(hipMalloc((void**)&nr, row_bytes));
-			HIP_TRY(hipMalloc((void**)&nh, head_bytes));
-			HIP_TRY(hipMemsetAsync(nr, 0, row_bytes, w->stream));
-			HIP_TRY(hipMemsetAsync(nh, 0, head_bytes, w->stream));
-			HIP_TRY(hipStreamSynchronize(w->stream));
-			const size_t per_vehicle = sizeof(sgd_vehicle) + sizeof(sgp_vehicle_input) + sizeof(float4) * (16u * 4u + 5u);
-			if (w->d_vehicles) { hipFree(w->d_vehicles); hipFree(w->d_veh_inputs); hipFree(w->d_veh_rows); hipFree(w->d_veh_head); w->device_bytes -= per_vehicle * w->cap_vehicles; }
-			w->d_vehicles = nv; w->d_veh_inputs = ni; w->d_veh_rows = nr; w->d_veh_head = nh; w->cap_vehicles = nc;
-			w->device_bytes += per_vehicle * nc;
-			w->veh_inputs_dirty = true;
-		}
+		{ int r = ensure_vehicle_capacity(w, w->n_vehicles + 1); if (r != SGP_OK) return r; }
 		w->n_vehicles++;
 		w->veh_alive.push_back(0); w->veh_body.push_back(SGP_INVALID_ID); w->veh_inputs.push_back(sgp_vehicle_input{ 0.0f, 0.0f, 0.0f, 0.0f });
 	}

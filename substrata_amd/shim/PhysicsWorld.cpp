@@ -279,7 +279,7 @@ void PhysicsWorld::addObject(const Reference<PhysicsObject>& object)
 			object->body_rot_os = Quatf(f->rot.x, f->rot.y, f->rot.z, f->rot.w);
 		}
 		const uint32_t bid = object->jolt_body_id.GetIndex();
-		if (bid < id_to_ob.size()) id_to_ob[bid] = object.ptr();
+		if (bid < id_to_ob.size() && id_to_ob[bid] != object.ptr()) { id_to_ob[bid] = object.ptr(); ++object_set_changes; }
 		return;
 	}
 	sgp_body_desc d;
@@ -342,6 +342,7 @@ void PhysicsWorld::addObject(const Reference<PhysicsObject>& object)
 	if (hull_in) holdHullInstance(*object, object->shape.hull, hull_in);
 	object->jolt_body_id = JPH::BodyID(id);
 	if (id < id_to_ob.size()) id_to_ob[id] = object.ptr();
+	++object_set_changes;
 	// the look-alike BodyInterface answers in the shape's space: it needs the body frame of hull bodies
 	if (object->shape.kind == 3 && !object->is_sphere && !object->is_cube)
 		physics_system->GetBodyInterface().setFrame(object->jolt_body_id, JPH::Vec3(object->body_com_os[0], object->body_com_os[1], object->body_com_os[2]),
@@ -391,6 +392,7 @@ void PhysicsWorld::addCompoundObject(const Reference<PhysicsObject>& object, sgp
 	for (auto& hh : held_hulls) for (PhysicsHullData::Instance& in : hh.first->instances) if (in.world == world && in.hull_id == hh.second) { holdHullInstance(*object, hh.first, &in); break; }
 	object->jolt_body_id = JPH::BodyID(id);
 	if (id < id_to_ob.size()) id_to_ob[id] = object.ptr();
+	++object_set_changes;
 	physics_system->registerCompound(object->jolt_body_id, (uint32_t)children.size());
 }
 
@@ -415,6 +417,7 @@ void PhysicsWorld::removeObject(const Reference<PhysicsObject>& object)
 		for (auto& release : object->shape_instance_releases) release();
 		object->shape_instance_releases.clear();
 		if (id < id_to_ob.size()) id_to_ob[id] = NULL;
+		++object_set_changes;
 		object->jolt_body_id = JPH::BodyID();
 	}
 	{
@@ -728,6 +731,63 @@ void PhysicsWorld::writeJoltSnapshotToDisk(const std::string& path)
 	fwrite(magic, 1, 8, f); fwrite(header, sizeof(uint32_t), 2, f);
 	if (n) fwrite(states.data(), sizeof(sgp_body_state), n, f);
 	fclose(f);
+}
+
+// ---- checkpoints (beyond the reference's members: JPH::PhysicsSystem::SaveState / RestoreState is how Jolt applications roll back) ----
+PhysicsWorldCheckpoint::~PhysicsWorldCheckpoint() { sgp_checkpoint_destroy(cp); }
+
+// The whole world as the blob sgp_world_restore loads (include/sgp.h).  The blob carries every body's userdata as the number it is -- here the
+// address of its PhysicsObject --, so it can be examined (sgp_checkpoint_blob_info) or loaded through the C ABI, but not through this facade in
+// another process.
+bool PhysicsWorld::saveState(const std::string& path)
+{
+	sgp_checkpoint* cp = NULL;
+	if (sgp_world_checkpoint(world, &cp) != SGP_OK) return false;
+	uint64_t n = 0;
+	bool ok = sgp_checkpoint_write(cp, NULL, 0, &n) == SGP_OK;
+	std::vector<unsigned char> blob(ok ? (size_t)n : 0);
+	ok = ok && sgp_checkpoint_write(cp, blob.data(), blob.size(), &n) == SGP_OK;
+	sgp_checkpoint_destroy(cp);
+	if (!ok) return false;
+	FILE* f = fopen(path.c_str(), "wb");
+	if (!f) return false;
+	ok = fwrite(blob.data(), 1, blob.size(), f) == blob.size();
+	fclose(f);
+	return ok;
+}
+
+Reference<PhysicsWorldCheckpoint> PhysicsWorld::checkpoint()
+{
+	Reference<PhysicsWorldCheckpoint> c = new PhysicsWorldCheckpoint();
+	checkSGP(sgp_world_checkpoint(world, &c->cp), "checkpoint");
+	c->object_set_changes = object_set_changes;
+	// what the caller sees of the objects that are asleep: their cached transforms (an object that fell asleep keeps the pose of its last read-back)
+	for (size_t i = 0; i < id_to_ob.size(); ++i) if (id_to_ob[i]) { PhysicsWorldCheckpoint::CachedPose p; p.ob = id_to_ob[i]; p.pos = id_to_ob[i]->pos; p.rot = id_to_ob[i]->rot; c->cached_poses.push_back(p); }
+	return c;
+}
+
+// The PhysicsObject records belong to the caller: a checkpoint taken before an object was added or removed cannot be rolled back to (the world would name
+// objects that are gone, or miss ones that exist) -- false, nothing changed.
+bool PhysicsWorld::rollback(const PhysicsWorldCheckpoint& c)
+{
+	if (!c.cp || c.object_set_changes != object_set_changes) return false;
+	if (sgp_world_rollback(world, c.cp) != SGP_OK) return false;
+	physics_system->onStep();                                   // cached body / vehicle read-backs are stale now
+	// every active object's cached transform from the device (as think() + readBackActivatedObjectTransforms do), every sleeping object's as the
+	// caller had it at the capture, and the activated set from the restored active flags
+	std::vector<uint32_t> ids; std::vector<PhysicsObject*> obs;
+	for (size_t i = 0; i < id_to_ob.size(); ++i) if (id_to_ob[i] && !id_to_ob[i]->jolt_body_id.IsInvalid() && id_to_ob[i]->jolt_body_id.GetIndex() == (uint32_t)i) { ids.push_back((uint32_t)i); obs.push_back(id_to_ob[i]); }
+	std::vector<sgp_body_state> st(ids.size());
+	if (!ids.empty()) checkSGP(sgp_body_get_state(world, ids.data(), (uint32_t)ids.size(), st.data()), "rollback");
+	Lock lock(activated_obs_mutex);
+	activated_obs.clear(); newly_activated_obs.clear();
+	for (const PhysicsWorldCheckpoint::CachedPose& p : c.cached_poses) { p.ob->pos = p.pos; p.ob->rot = p.rot; }      // (the object set is the capture's: checked above)
+	for (size_t i = 0; i < ids.size(); ++i) {
+		if (st[i].active) toObjectPose(*obs[i], st[i].pos, st[i].rot, obs[i]->pos, obs[i]->rot);
+		obs[i]->underwater = st[i].underwater != 0; obs[i]->last_submerged_volume = st[i].submerged_volume;
+		if (st[i].active) activated_obs.insert(obs[i]);
+	}
+	return true;
 }
 
 // PhysicsWorld.cpp:725-732

@@ -64,6 +64,21 @@ public:
 
 void computeToWorldAndToObMatrices(const Vec4f& translation, const Quatf& rot_quat, const Vec4f& scale, Matrix4f& ob_to_world_out, Matrix4f& world_to_ob_out);
 
+// A captured world state (sgp_checkpoint, include/sgp.h) with the facade's object-set counter at the capture.  Not in the reference.
+class PhysicsWorldCheckpoint : public ThreadSafeRefCounted
+{
+public:
+	PhysicsWorldCheckpoint() : cp(NULL), object_set_changes(0) {}
+	~PhysicsWorldCheckpoint();
+	struct sgp_checkpoint* cp;
+	uint64_t object_set_changes;
+	struct CachedPose { PhysicsObject* ob; Vec4f pos; Quatf rot; };
+	std::vector<CachedPose> cached_poses;      // PhysicsObject::pos / rot at the capture (what a sleeping object shows)
+private:
+	PhysicsWorldCheckpoint(const PhysicsWorldCheckpoint&);
+	PhysicsWorldCheckpoint& operator=(const PhysicsWorldCheckpoint&);
+};
+
 class PhysicsWorld : public ThreadSafeRefCounted
 {
 public:
@@ -265,6 +280,13 @@ public:
 	// Debug helpers (PhysicsWorld.h:187-189).  The snapshot is this library's own flat dump (a header + one sgp_body_state per body slot),
 	// not Jolt's PhysicsScene stream; computeSizeBForShape reports the bytes the shape description holds.
 	void writeJoltSnapshotToDisk(const std::string& path);
+	// Extensions (not in the reference; Jolt applications use PhysicsSystem::SaveState / RestoreState for this).  saveState: the whole world as the
+	// blob of sgp_checkpoint_write.  checkpoint / rollback: the world goes back to exactly what it was, and continues bit for bit as if never
+	// interrupted; rollback returns false and changes nothing when an object was added or removed since the capture.  On success every active
+	// object's cached pos / rot is rewritten from the device (a sleeping object's is what it was at the capture), activated_obs is rebuilt from the restored active flags and newly_activated_obs is cleared.
+	bool saveState(const std::string& path);
+	Reference<PhysicsWorldCheckpoint> checkpoint();
+	bool rollback(const PhysicsWorldCheckpoint& checkpoint);
 	static size_t computeSizeBForShape(const PhysicsShape& shape);
 	static size_t computeSizeBForShape(JPH::Ref<JPH::Shape> jolt_shape);      // PhysicsWorld.h:189
 
@@ -303,6 +325,7 @@ private:
 	glare::TaskManager* task_manager;
 	glare::StackAllocator* stack_allocator;
 	std::vector<PhysicsObject*> id_to_ob;
+	uint64_t object_set_changes = 0;      // objects added or removed so far (a checkpoint remembers it)
 	// per-step scratch of think(): kept between calls, sized to what the steps really produce (never to the world's capacity, never zero-filled)
 	std::vector<struct sgp_body_event> body_event_buf;
 	std::vector<struct sgp_contact_event> contact_event_buf;

@@ -25,6 +25,37 @@ def _f4(v):
     return np.ascontiguousarray(v, dtype=np.float32).reshape(4)
 
 
+class Checkpoint:
+    """A captured world state (sgp_checkpoint): owns device and host memory, belongs to the world that made it."""
+
+    def __init__(self, world, handle):
+        self._w, self._h = world, handle
+
+    def info(self):
+        i = abi.CheckpointInfo()
+        self._w._check(self._w._fn("checkpoint_get_info")(self._h, C.byref(i)), "checkpoint_get_info")
+        return i.as_dict()
+
+    def to_bytes(self):
+        """The pointer-free blob CWorld.restore loads into a fresh world with the same description."""
+        n = C.c_uint64(0)
+        self._w._check(self._w._fn("checkpoint_write")(self._h, None, 0, C.byref(n)), "checkpoint_write")
+        buf = np.empty(n.value, dtype=np.uint8)
+        self._w._check(self._w._fn("checkpoint_write")(self._h, buf.ctypes.data, buf.nbytes, C.byref(n)), "checkpoint_write")
+        return buf.tobytes()
+
+    def close(self):
+        if self._h:
+            self._w._fn("checkpoint_destroy")(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class CWorld:
     def __init__(self, lib, prefix, max_bodies=65536, gravity=(0.0, 0.0, -9.81), device=0, settings=None,
                  max_body_pairs=0, max_manifolds=0, large_body_radius=0.0):
@@ -213,6 +244,28 @@ class CWorld:
 
     def set_contact_events(self, enabled):
         self._check(self._fn("world_set_contact_events")(self._h, int(bool(enabled))), "world_set_contact_events")
+
+    # -- checkpoints ----------------------------------------------------------------------------------------
+    def checkpoint(self, cp=None):
+        """Captures the world's state; cp: a Checkpoint of this world to overwrite in place (its buffers are re-used)."""
+        if cp is None:
+            h = C.c_void_p()
+            self._check(self._fn("world_checkpoint")(self._h, C.byref(h)), "world_checkpoint")
+            return Checkpoint(self, h)
+        if not cp._h:
+            raise SgpError("checkpoint: the Checkpoint to overwrite has been closed")
+        self._check(self._fn("world_checkpoint")(self._h, C.byref(cp._h)), "world_checkpoint")      # (the library writes the handle it used back)
+        return cp
+
+    def rollback(self, cp):
+        if not cp._h:
+            raise SgpError("rollback: the Checkpoint has been closed")
+        self._check(self._fn("world_rollback")(self._h, cp._h), "world_rollback")
+
+    def restore(self, blob):
+        """Loads a Checkpoint.to_bytes() blob into this world, which must be fresh and have the blob's description."""
+        buf = np.frombuffer(bytes(blob), dtype=np.uint8)
+        self._check(self._fn("world_restore")(self._h, buf.ctypes.data, buf.nbytes), "world_restore")
 
     def step(self, dt=1.0 / 60.0):
         self._check(self._fn("world_step")(self._h, float(dt)), "world_step")
