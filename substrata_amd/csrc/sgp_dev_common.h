@@ -133,6 +133,25 @@ SGP_DEV void push_event(uint32_t* list, uint32_t* counter, uint32_t cap, uint32_
 	if (k < cap) list[k] = id;
 }
 
+// One workgroup of the step's last launch: the step's counters, the event counters and the head of each body-event list go to host-mapped memory,
+// where the host finds them after its wait.  All of it was final before that launch started.
+SGP_DEV void step_end_block(const DV& d, StepCounters* host_mapped, EventWindow* host_events)
+{
+	const uint32_t* src = (const uint32_t*)d.ctr;
+	uint32_t* dst = (uint32_t*)host_mapped;
+	for (uint32_t i = threadIdx.x; i < sizeof(StepCounters) / 4; i += blockDim.x) dst[i] = src[i];
+	__syncthreads();
+	if (threadIdx.x == 0 && d.ts_nt) { host_mapped->ts_error = d.ts_flags[0]; host_mapped->ts_all_adjacent = d.ts_flags[1]; }
+	if (threadIdx.x < sizeof(EventCounters) / 4) ((uint32_t*)&host_events->c)[threadIdx.x] = ((const uint32_t*)d.evc)[threadIdx.x];
+	const uint32_t win = min(min(d.ev_window, SGP_EVENT_WINDOW), d.cap_bodies);
+	const uint32_t* lists[3] = { d.ev_activated, d.ev_deactivated, d.ev_water };
+	const uint32_t counts[3] = { d.evc->n_activated, d.evc->n_deactivated, d.evc->n_water };
+	for (int l = 0; l < 3; ++l) {
+		if (counts[l] > win) continue;      // (the host fetches a longer list itself)
+		for (uint32_t i = threadIdx.x; i < counts[l]; i += blockDim.x) host_events->ids[l][i] = lists[l][i];
+	}
+}
+
 // "The last workgroup to finish does what needs everybody's results": every thread of the workgroup calls this at the end of the kernel's parallel part;
 // true (for the whole workgroup) in the workgroup that took the last ticket.  The tickets live in StepCounters (zeroed by the step's first launch) and
 // are used once per step each.  A dependent kernel boundary costs ~4.5 us at the launch floor; this costs a fence and an atomic.

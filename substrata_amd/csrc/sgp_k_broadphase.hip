@@ -7,9 +7,12 @@
 // Round 4: the same launch also finds the bounds of the small bodies' AABB centres (the broad-phase grid's extent), which was a launch of its own: the first
 // `bounds_blocks` workgroups sweep the bodies and fold their six extrema into DV::bounds_acc (ordered-int atomics; reset by k_bp_scatter, which runs after
 // the grid parameters have been derived from them).
-__global__ void __launch_bounds__(TPB) k_step_begin(DV d, StepParams sp, uint32_t nb, int reset_scratch, uint32_t bounds_blocks)
+__global__ void __launch_bounds__(TPB) k_step_begin(DV d, StepParams sp, uint32_t nb, int reset_scratch, uint32_t bounds_blocks, int ev_reset)
 {
 	const uint32_t tid = blockIdx.x * TPB + threadIdx.x, stride = gridDim.x * TPB;
+	// the host holds everything the event lists had (it says so through the launch plan: one more graph variant, no per-step value in a captured argument):
+	// they start empty.  Nothing of this launch raises an event, and the previous step's last launch has read the counters.
+	if (ev_reset && tid < sizeof(EventCounters) / 4) ((uint32_t*)d.evc)[tid] = 0u;
 	if (tid == 0) {
 		// the buffer parity lives on the device and flips with every step (reset_scratch: a step, not a re-binning between steps): were it a by-value
 		// argument, every launch plan would need two captured graphs -- one per parity -- and a plan change would cost two captures
@@ -61,15 +64,7 @@ __global__ void __launch_bounds__(TPB) k_step_begin(DV d, StepParams sp, uint32_
 __global__ void k_set_params(DV d, StepParams sp) { if (threadIdx.x == 0 && blockIdx.x == 0) *d.sp = sp; }
 
 // Last launch of a step: the counters go straight into host-mapped pinned memory (no copy node).
-__global__ void __launch_bounds__(TPB) k_step_end(DV d, StepCounters* host_mapped, EventCounters* host_events)
-{
-	const uint32_t* src = (const uint32_t*)d.ctr;
-	uint32_t* dst = (uint32_t*)host_mapped;
-	for (uint32_t i = threadIdx.x; i < sizeof(StepCounters) / 4; i += TPB) dst[i] = src[i];
-	__syncthreads();
-	if (threadIdx.x == 0 && d.ts_nt) { host_mapped->ts_error = d.ts_flags[0]; host_mapped->ts_all_adjacent = d.ts_flags[1]; }
-	if (threadIdx.x < sizeof(EventCounters) / 4) ((uint32_t*)host_events)[threadIdx.x] = ((const uint32_t*)d.evc)[threadIdx.x];
-}
+__global__ void __launch_bounds__(TPB) k_step_end(DV d, StepCounters* host_mapped, EventWindow* host_events) { step_end_block(d, host_mapped, host_events); }
 
 __global__ void __launch_bounds__(TPB) k_fill_u64(uint64_t* p, uint64_t v, size_t n)
 {
@@ -544,15 +539,15 @@ __global__ void __launch_bounds__(TPB) k_bp_large(DV d) { bp_large_one(d, blockI
 // other writes): a launch less on the step's chain (round 4).
 __global__ void __launch_bounds__(TPB) k_bp_scatter_large(DV d) { const uint32_t i = blockIdx.x * TPB + threadIdx.x; bp_scatter_one(d, i); bp_large_one(d, i); }
 
-void launch_step_begin(const DV& d, const StepParams& sp, uint32_t nb, bool reset_step_scratch, hipStream_t s)
+void launch_step_begin(const DV& d, const StepParams& sp, uint32_t nb, bool reset_step_scratch, bool ev_reset, hipStream_t s)
 {
 	const uint32_t work = std::max(d.table_size + 4, reset_step_scratch ? nb : 0u);
 	uint32_t blocks = (work + TPB * 4 - 1) / (TPB * 4);
 	if (blocks < 1) blocks = 1; if (blocks > 1024) blocks = 1024;
-	hipLaunchKernelGGL(k_step_begin, dim3(blocks), dim3(TPB), 0, s, d, sp, nb, reset_step_scratch ? 1 : 0, std::min(blocks, std::min(blocks_for(nb), 128u)));
+	hipLaunchKernelGGL(k_step_begin, dim3(blocks), dim3(TPB), 0, s, d, sp, nb, reset_step_scratch ? 1 : 0, std::min(blocks, std::min(blocks_for(nb), 128u)), ev_reset ? 1 : 0);
 }
 void launch_set_params(const DV& d, const StepParams& sp, hipStream_t s) { hipLaunchKernelGGL(k_set_params, dim3(1), dim3(64), 0, s, d, sp); }
-void launch_step_end(const DV& d, StepCounters* host_mapped, EventCounters* host_events, hipStream_t s) { hipLaunchKernelGGL(k_step_end, dim3(1), dim3(TPB), 0, s, d, host_mapped, host_events); }
+void launch_step_end(const DV& d, StepCounters* host_mapped, EventWindow* host_events, hipStream_t s) { hipLaunchKernelGGL(k_step_end, dim3(1), dim3(TPB), 0, s, d, host_mapped, host_events); }
 void launch_fill_u64(uint64_t* p, uint64_t v, size_t n, hipStream_t s)
 {
 	size_t blocks = (n + TPB * 8 - 1) / (TPB * 8);

@@ -407,18 +407,8 @@ __global__ void __launch_bounds__(TPB) k_setup(DV d)
 		}
 	}
 }
-SGP_DEV void step_end_block(const DV& d, StepCounters* host_mapped, EventCounters* host_events)
-{
-	const uint32_t* src = (const uint32_t*)d.ctr;
-	uint32_t* dst = (uint32_t*)host_mapped;
-	for (uint32_t i = threadIdx.x; i < sizeof(StepCounters) / 4; i += TPB) dst[i] = src[i];
-	__syncthreads();
-	if (threadIdx.x == 0 && d.ts_nt) { host_mapped->ts_error = d.ts_flags[0]; host_mapped->ts_all_adjacent = d.ts_flags[1]; }
-	if (threadIdx.x < sizeof(EventCounters) / 4) ((uint32_t*)host_events)[threadIdx.x] = ((const uint32_t*)d.evc)[threadIdx.x];
-}
-
 // (round 4: the step's counters go to the host from workgroup 0 of this, the step's last, launch: k_step_end was a launch of its own)
-__global__ void __launch_bounds__(TPB) k_cache_build(DV d, StepCounters* host_mapped, EventCounters* host_events)
+__global__ void __launch_bounds__(TPB) k_cache_build(DV d, StepCounters* host_mapped, EventWindow* host_events)
 {
 	// nobody was awake in this step (StepCounters::any_awake): it made no constraint, the table was not emptied, and the buffer parity goes back to what it was --
 	// the next step finds the cache this one found
@@ -533,7 +523,7 @@ void launch_setup(const DV& d, uint32_t n_man, hipStream_t s)
 	hipLaunchKernelGGL(k_setup_slots, dim3(std::max(64u, std::min(4096u, (n_man + TPB * SLOTS_PER_THREAD - 1) / (TPB * SLOTS_PER_THREAD)))), dim3(TPB), 0, s, d);
 	hipLaunchKernelGGL(k_setup, dim3(stride_grid(n_man)), dim3(TPB), 0, s, d);
 }
-void launch_cache_build(const DV& d, uint32_t n_con, StepCounters* host_mapped, EventCounters* host_events, hipStream_t s)
+void launch_cache_build(const DV& d, uint32_t n_con, StepCounters* host_mapped, EventWindow* host_events, hipStream_t s)
 {
 	// (the table was emptied by the first k_island_mark launch of the step)
 	hipLaunchKernelGGL(k_cache_build, dim3(stride_grid(n_con)), dim3(TPB), 0, s, d, host_mapped, host_events);

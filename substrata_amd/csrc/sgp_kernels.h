@@ -166,6 +166,15 @@ struct EventCounters {
 	uint32_t n_contact_persisted;
 	uint32_t pad[3];
 };
+// What the step's last launch leaves in host-mapped memory for the host's one wait: the event counters and the first ids of each body-event list
+// (activated / deactivated / entered water, in list order).  A steady step raises a handful of body events (the 100k pile of the benchmark: one to four
+// bodies fall asleep per step, a settling scene of a few thousand bodies a few dozen at its peak), which the host then reads from here instead of
+// fetching each list with a copy and a wait of its own; a list longer than the window (a pile that falls asleep or wakes as a whole) is fetched as before.
+#define SGP_EVENT_WINDOW 256u
+struct EventWindow {
+	EventCounters c;
+	uint32_t ids[3][SGP_EVENT_WINDOW];
+};
 
 // Host -> device body edit command (applied in order, one thread per body run).
 #define CMD_SET_POS      (1u << 0)
@@ -344,6 +353,7 @@ struct DV {
 	StepCounters* ctr;
 	EventCounters* evc;
 	uint32_t* ev_activated; uint32_t* ev_deactivated; uint32_t* ev_water;
+	uint32_t ev_window;        // ids per list that the step's last launch copies into the host's EventWindow (<= SGP_EVENT_WINDOW; 0: counters only)
 	sgp_contact_event* ev_contacts_added; sgp_contact_event* ev_contacts_persisted; uint32_t cap_contact_events;
 	// convex hull shapes (sgp_device_hull.h): fixed-capacity table, hull 0 = the +-1 cube template every box is a scaled copy of
 	const struct sgd_hull_s* hulls; uint32_t n_hulls;
@@ -370,9 +380,10 @@ struct DV {
 // ---- launch wrappers (each defined at the end of the stage file that holds its kernels) ---------------------------------------------------------------
 // `nb` = number of body slots the per-body grids must cover (a bucketed upper bound of StepParams::n_slots)
 // first / last launch of a step: per-step scalars in by value + scratch reset; counters out to host-mapped memory
-void launch_step_begin(const DV& d, const StepParams& sp, uint32_t nb, bool reset_step_scratch, hipStream_t s);
+// ev_reset: the host has pulled every event the device lists held, so this launch empties them (the event counters are otherwise left alone: they accumulate until pulled)
+void launch_step_begin(const DV& d, const StepParams& sp, uint32_t nb, bool reset_step_scratch, bool ev_reset, hipStream_t s);
 void launch_set_params(const DV& d, const StepParams& sp, hipStream_t s);
-void launch_step_end(const DV& d, StepCounters* host_mapped, EventCounters* host_events, hipStream_t s);
+void launch_step_end(const DV& d, StepCounters* host_mapped, EventWindow* host_events, hipStream_t s);
 void launch_fill_u64(uint64_t* p, uint64_t v, size_t n, hipStream_t s);
 void launch_pre_solve(const DV& d, uint32_t nb, hipStream_t s);      // wake-ups + forces + per-step solver records (after the narrow phase)
 void launch_bp_bounds(const DV& d, uint32_t nb, hipStream_t s);
@@ -415,7 +426,7 @@ void launch_island_hook(const DV& d, uint32_t n_con, hipStream_t s);
 void launch_island_flag(const DV& d, uint32_t n_con, hipStream_t s);
 void launch_sleep_apply(const DV& d, uint32_t nb, hipStream_t s);
 void launch_buoyancy(const DV& d, uint32_t nb, hipStream_t s);
-void launch_cache_build(const DV& d, uint32_t n_con, StepCounters* host_mapped, EventCounters* host_events, hipStream_t s);      // + the step's counters to the host (its last workgroup)
+void launch_cache_build(const DV& d, uint32_t n_con, StepCounters* host_mapped, EventWindow* host_events, hipStream_t s);      // + the step's counters to the host (its last workgroup)
 void launch_contact_events(const DV& d, uint32_t n_man, hipStream_t s);
 void launch_ghost_refresh(const DV& d, const GhostRefresh* recs, uint32_t n, hipStream_t s);
 void launch_apply_cmds(const DV& d, const BodyCmd* cmds, const uint32_t* run_start, uint32_t n_runs, hipStream_t s);

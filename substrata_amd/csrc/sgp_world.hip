@@ -220,8 +220,12 @@ SGP_API int sgp_world_create(const sgp_world_desc* desc, sgp_world** out)
 	DEV_ALLOC(d.ev_activated, N); DEV_ALLOC(d.ev_deactivated, N); DEV_ALLOC(d.ev_water, N);
 	HIP_TRY(hipHostMalloc((void**)&w->h_ctr, sizeof(StepCounters), hipHostMallocMapped));
 	HIP_TRY(hipHostGetDevicePointer((void**)&w->h_ctr_dev, w->h_ctr, 0));
-	HIP_TRY(hipHostMalloc((void**)&w->h_evc, sizeof(EventCounters), hipHostMallocMapped));
-	HIP_TRY(hipHostGetDevicePointer((void**)&w->h_evc_dev, w->h_evc, 0));
+	HIP_TRY(hipHostMalloc((void**)&w->h_evw, sizeof(EventWindow), hipHostMallocMapped));
+	HIP_TRY(hipHostGetDevicePointer((void**)&w->h_evw_dev, w->h_evw, 0));
+	memset(w->h_evw, 0, sizeof(EventWindow)); w->h_evc = &w->h_evw->c;
+	// SGP_EVENT_WINDOW=n (tests): ids per list the step's last launch hands over; 0 = every list is fetched with a copy of its own
+	d.ev_window = SGP_EVENT_WINDOW;
+	{ const char* e = getenv("SGP_EVENT_WINDOW"); if (e && atoi(e) >= 0) d.ev_window = std::min((uint32_t)atoi(e), SGP_EVENT_WINDOW); }
 	HIP_TRY(hipHostMalloc((void**)&w->h_sp, sizeof(StepParams), hipHostMallocDefault));
 	memset(w->h_sp, 0, sizeof(StepParams));
 	DEV_ALLOC(w->d_sp, 1);
@@ -280,7 +284,7 @@ SGP_API int sgp_world_destroy(sgp_world* w)
 	if (w->stage_host) hipHostFree(w->stage_host);
 	if (w->view_host) hipHostFree(w->view_host);
 	if (w->h_ctr) hipHostFree(w->h_ctr);
-	if (w->h_evc) hipHostFree(w->h_evc);
+	if (w->h_evw) hipHostFree(w->h_evw);
 	if (w->h_sp) hipHostFree(w->h_sp);
 	for (auto& kv : w->graphs) hipGraphExecDestroy(kv.second);
 	for (hipEvent_t ev : w->event_pool) hipEventDestroy(ev);
@@ -432,6 +436,7 @@ int flush_cmds(sgp_world* w)
 	hipSetDevice(w->device);
 	DV& d = w->dv;
 	{ int r = upload_sp(w); if (r != SGP_OK) return r; }
+	if (!w->ghost_refresh.empty() || !w->cmds.empty()) { int r = flush_event_reset(w); if (r != SGP_OK) return r; }      // (what is applied below may raise activation events)
 	if (!w->ghost_refresh.empty()) {
 		// ghosts never appear in the command queue while their set is unchanged, so the order against the commands below does not matter
 		const size_t bytes = w->ghost_refresh.size() * sizeof(GhostRefresh);
@@ -484,28 +489,45 @@ int flush_cmds(sgp_world* w)
 	return rebuild_large_grid(w);
 }
 
-// Pull the device event lists into the host vectors and reset the device counters.
+// The host has pulled the device's event lists but their counters still stand (collect_events leaves the reset to the next step's first launch): empty them
+// now, ahead of a launch outside a step that raises events or of a copy of the device state.
+int flush_event_reset(sgp_world* w)
+{
+	if (!w->ev_reset_pending) return SGP_OK;
+	HIP_TRY(hipMemsetAsync(w->dv.evc, 0, sizeof(EventCounters), w->stream));
+	w->ev_reset_pending = false;
+	return SGP_OK;
+}
+
+// Pull the device event lists into the host vectors; the device counters are reset by the next step's first launch (ev_reset_pending).
+// counters_fresh: called by a step after its wait -- the counters and the head of each body-event list are in host-mapped memory (EventWindow), and a list
+// that fits the window costs no copy and no further wait.
 int collect_events(sgp_world* w, bool counters_fresh)
 {
 	DV& d = w->dv;
 	if (!counters_fresh) {
 		if (!w->events_on_device) return SGP_OK;      // nothing ran on the device since the lists were last pulled: no copy, no sync
+		if (w->ev_reset_pending) { w->events_on_device = false; return SGP_OK; }      // (nothing was launched since the pull whose reset is still owed: the counters are stale, the lists hold nothing new)
 		HIP_TRY(hipMemcpyAsync(w->h_evc, d.evc, sizeof(EventCounters), hipMemcpyDeviceToHost, w->stream));
 		HIP_TRY(hipStreamSynchronize(w->stream));
 	}
 	w->events_on_device = false;
 	const EventCounters ec = *w->h_evc;
 	if (!(ec.n_activated | ec.n_deactivated | ec.n_water | ec.n_contact_added | ec.n_contact_persisted)) return SGP_OK;
-	struct L { uint32_t n; uint32_t* dev; std::vector<sgp_body_event>* out; };
-	L lists[3] = { { std::min(ec.n_activated, d.cap_bodies), d.ev_activated, &w->ev_act },
-	               { std::min(ec.n_deactivated, d.cap_bodies), d.ev_deactivated, &w->ev_deact },
-	               { std::min(ec.n_water, d.cap_bodies), d.ev_water, &w->ev_water } };
+	struct L { uint32_t n_raised, n; uint32_t* dev; const uint32_t* win; std::vector<sgp_body_event>* out; };
+	L lists[3] = { { ec.n_activated, std::min(ec.n_activated, d.cap_bodies), d.ev_activated, w->h_evw->ids[0], &w->ev_act },
+	               { ec.n_deactivated, std::min(ec.n_deactivated, d.cap_bodies), d.ev_deactivated, w->h_evw->ids[1], &w->ev_deact },
+	               { ec.n_water, std::min(ec.n_water, d.cap_bodies), d.ev_water, w->h_evw->ids[2], &w->ev_water } };
+	const uint32_t win = std::min(std::min(d.ev_window, SGP_EVENT_WINDOW), d.cap_bodies);      // (as step_end_block computes it)
 	for (L& l : lists) {
 		if (!l.n) continue;
-		{ int r = ensure_stage(w, sizeof(uint32_t) * l.n); if (r != SGP_OK) return r; }
-		HIP_TRY(hipMemcpyAsync(w->stage_host, l.dev, sizeof(uint32_t) * l.n, hipMemcpyDeviceToHost, w->stream));
-		HIP_TRY(hipStreamSynchronize(w->stream));
-		const uint32_t* ids = (const uint32_t*)w->stage_host;
+		const uint32_t* ids = l.win;
+		if (!counters_fresh || l.n_raised > win) {
+			{ int r = ensure_stage(w, sizeof(uint32_t) * l.n); if (r != SGP_OK) return r; }
+			HIP_TRY(hipMemcpyAsync(w->stage_host, l.dev, sizeof(uint32_t) * l.n, hipMemcpyDeviceToHost, w->stream));
+			HIP_TRY(hipStreamSynchronize(w->stream));
+			ids = (const uint32_t*)w->stage_host;
+		}
 		for (uint32_t k = 0; k < l.n; ++k) { sgp_body_event e; e.id = ids[k]; e._pad = 0; e.userdata = w->hb[ids[k]].userdata; l.out->push_back(e); }
 	}
 	struct CL { uint32_t n; sgp_contact_event* dev; std::vector<sgp_contact_event>* out; };
@@ -523,7 +545,7 @@ int collect_events(sgp_world* w, bool counters_fresh)
 			e.id1 = compound_id_of(w, e.id1, nullptr); e.id2 = compound_id_of(w, e.id2, nullptr);   // a compound's children report as the compound
 			e.userdata1 = w->hb[e.id1].userdata; e.userdata2 = w->hb[e.id2].userdata; l.out->push_back(e); }
 	}
-	HIP_TRY(hipMemsetAsync(d.evc, 0, sizeof(EventCounters), w->stream));
+	w->ev_reset_pending = true;
 	return SGP_OK;
 }
 
@@ -587,6 +609,8 @@ struct StepPlan {
 	uint32_t hc_probe_est;
 	int      tile_solver;        // all velocity iterations in the one resident launch of the tile solver (k_ts_solve)
 	int      small_pairs;        // ... with two lanes per constraint (the previous step had <= 384 constraints), else one thread per constraint
+	int      ev_reset;           // the first launch empties the device's event counters (the host pulled the lists after the previous step: every step of a caller that steps one
+	                             //   at a time); 0: they go on accumulating (the later steps of sgp_world_step_n, a step after edits that raised events)
 	StepParams sp;               // by-value kernel argument of the first launch: part of the key of a captured graph
 };
 
@@ -661,6 +685,7 @@ static void make_plan(const sgp_world* w, StepPlan& p)
 	// the passes, and enough body slots for k_ts_label's grid to clear the (colour, tile) histogram
 	p.tile_solver = (w->use_tile_solver && w->dv.ts_nt && !p.small_world && w->n_vehicles == 0 && p.vel_iters > 0 && w->n_con >= w->ts_min_constraints &&
 	                 w->high >= SGP_MAX_COLOURS * w->dv.ts_nt && w->last_active <= w->dv.ts_nt * 1536u && !w->h_sp->compact_rows) ? w->use_tile_solver : 0;      // (2: debugging aid -- the tile order of the slots, solved by the colour launches)
+	p.ev_reset = w->ev_reset_pending ? 1 : 0;
 	p.sp = *w->h_sp;
 	p.sp.parity = 0u;        // (not part of a plan: the device flips its own)
 }
@@ -671,7 +696,7 @@ static int enqueue_step(sgp_world* w, const StepPlan& p)
 	hipStream_t s = w->stream;
 	const uint32_t nb = p.nb;
 	STAGE_MARK(0);
-	{ KScope k(w, KC_MISC); launch_step_begin(d, p.sp, nb, true, s); }
+	{ KScope k(w, KC_MISC); launch_step_begin(d, p.sp, nb, true, p.ev_reset != 0, s); }
 	STAGE_MARK(1);
 	// -- 1/2. broad-phase grid of the current poses (forces do not move bodies), then the step listeners that query it
 	//         (VehicleConstraint::OnStep: wheel casts), then forces, then the pair search
@@ -755,7 +780,7 @@ static int enqueue_step(sgp_world* w, const StepPlan& p)
 	if (p.water) { KScope k(w, KC_BUOYANCY); launch_buoyancy(d, nb, s); }
 	{
 		KScope k(w, KC_CACHE_BUILD);
-		launch_cache_build(d, p.est_man, w->h_ctr_dev, w->h_evc_dev, s);      // (+ the counters to host-mapped memory: the step's last launch)
+		launch_cache_build(d, p.est_man, w->h_ctr_dev, w->h_evw_dev, s);      // (+ the counters to host-mapped memory: the step's last launch)
 	}
 	STAGE_MARK(8);
 	return SGP_OK;
@@ -764,6 +789,11 @@ static int enqueue_step(sgp_world* w, const StepPlan& p)
 static int step_impl(sgp_world* w, float dt, bool final_readback)
 {
 	if (!(dt > 0.0f)) return fail(SGP_ERR_INVALID, "sgp_world_step: dt must be > 0");
+	// SGP_TIMING=1: where the host's share of a step goes (averages over 100 / 500 steps on stderr; profiles/host_tail_breakdown.md)
+	static const bool timing = getenv("SGP_TIMING") != nullptr;
+	static double t_acc[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }; static int t_n = 0; static double t_exit = 0.0;
+	auto now = []() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+	const double ts0 = timing ? now() : 0.0;
 	{ int r = flush_cmds(w); if (r != SGP_OK) return r; }
 	DV& d = w->dv;
 	if (w->high == 0) { memset(&w->stats, 0, sizeof(w->stats)); return SGP_OK; }
@@ -785,9 +815,6 @@ static int step_impl(sgp_world* w, float dt, bool final_readback)
 		HIP_TRY(hipMemcpyAsync(w->d_veh_inputs, w->veh_inputs.data(), sizeof(sgp_vehicle_input) * w->n_vehicles, hipMemcpyHostToDevice, w->stream));
 		w->veh_inputs_dirty = false;
 	}
-	static const bool timing = getenv("SGP_TIMING") != nullptr;
-	static double t_acc[4] = { 0, 0, 0, 0 }; static int t_n = 0;
-	auto now = []() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
 	const double tt0 = timing ? now() : 0.0;
 	w->h_sp->dt = dt;
 	w->h_sp->compact_rows = ((w->high <= SGP_SMALL_WORLD_BODIES && !w->rows_in_small_worlds) || w->n_con == 0u) ? 0u : (w->n_con >= w->compact_rows_min ? w->rows_mode_large : (w->rows_mode_default == 2u && w->n_con < w->rows_mode2_min ? 1u : w->rows_mode_default));      // (decided from the previous step's count, part of the plan's key; no constraints: full rows cost nothing and k_pre_solve need not write the inertia records)
@@ -795,6 +822,7 @@ static int step_impl(sgp_world* w, float dt, bool final_readback)
 	make_plan(w, plan);
 	const std::string key((const char*)&plan, sizeof(plan));
 	bool launched = false;
+	const double ts2 = timing ? now() : 0.0;
 	if (w->use_graphs && !w->profiling) {
 		auto it = w->graphs.find(key);
 		if (it == w->graphs.end()) {
@@ -828,6 +856,7 @@ static int step_impl(sgp_world* w, float dt, bool final_readback)
 	if (!launched) { const int r = enqueue_step(w, plan); if (r != SGP_OK) return r; w->eager_steps++; }
 	w->sp_uploaded = plan.sp; w->sp_uploaded_valid = true;      // (k_step_begin wrote it)
 	w->events_on_device = true;
+	w->ev_reset_pending = false;                                 // (... and emptied the event counters if that was owed)
 	// -- the ONE host sync of the step: counters, events, and the launch plan for the next step
 	const double tt1 = timing ? now() : 0.0;
 	HIP_TRY(hipStreamSynchronize(w->stream));
@@ -884,22 +913,31 @@ static int step_impl(sgp_world* w, float dt, bool final_readback)
 	st.pairs_dropped = c1.pairs_dropped; st.manifolds_dropped = c1.manifolds_dropped;
 	st.device_bytes = w->device_bytes;
 	st.num_active = c1.n_active;
+	const double ts5 = timing ? now() : 0.0;
+	double ts6 = ts5;
 	if (final_readback) {
 		const size_t a0 = w->ev_act.size(), d0 = w->ev_deact.size();
 		{ int r = collect_events(w, /*counters_fresh=*/true); if (r != SGP_OK) return r; }
 		st.num_activated = (uint32_t)(w->ev_act.size() - a0);
 		st.num_deactivated = (uint32_t)(w->ev_deact.size() - d0);
-		for (uint32_t i = 0; i < w->high; ++i) if ((w->hb[i].flags & (BF_ALIVE | BF_ALIAS)) == BF_ALIVE) st.layer_counts[(w->hb[i].flags & BF_LAYER_MASK) >> BF_LAYER_SHIFT]++;
+		if (timing) ts6 = now();
+		memcpy(st.layer_counts, w->layer_counts, sizeof(st.layer_counts));      // (kept as bodies come, go and change layer: set_body_flags)
 	}
 	if (timing) {
 		const double tt3 = now();
 		t_acc[0] += tt1 - tt0; t_acc[1] += tt2 - tt1; t_acc[2] += tt3 - tt2; t_n++;
+		// the parts: flush_cmds and the vehicle inputs | plan and its key | graph lookup and launch (or the eager launches); counters, plan feedback and stats |
+		// events | layer counts; and what the caller spends between two steps
+		t_acc[3] += tt0 - ts0; t_acc[4] += ts2 - tt0; t_acc[5] += ts5 - tt2; t_acc[6] += ts6 - ts5; if (t_exit != 0.0) t_acc[7] += ts0 - t_exit;
 		if (t_n == 500 || t_n == 100) {
 			fprintf(stderr, "[sgp timing] enqueue %.1f us  sync wait %.1f us  post %.1f us; colouring: %u rounds used, %u planned wide, uncoloured at round start:", t_acc[0] / t_n, t_acc[1] / t_n, t_acc[2] / t_n, c1.rounds_used, plan.rounds);
 			for (uint32_t r = 1; r < std::min(c1.rounds_used + 1u, 32u); ++r) fprintf(stderr, " %u", c1.round_n[r]);
 			fprintf(stderr, "\n");
-			if (t_n == 500) { t_acc[0] = t_acc[1] = t_acc[2] = 0; t_n = 0; }
+			fprintf(stderr, "[sgp timing] host parts (us): flush %.1f  plan %.1f  launch %.1f  wait %.1f  stats %.1f  events %.1f  layer counts %.1f  caller %.1f\n",
+			        t_acc[3] / t_n, t_acc[4] / t_n, (t_acc[0] - t_acc[4]) / t_n, t_acc[1] / t_n, t_acc[5] / t_n, t_acc[6] / t_n, (t_acc[2] - t_acc[5] - t_acc[6]) / t_n, t_acc[7] / t_n);
+			if (t_n == 500) { for (double& a : t_acc) a = 0; t_n = 0; }
 		}
+		t_exit = now();
 	}
 	return SGP_OK;
 }

@@ -121,7 +121,7 @@ int add_one(sgp_world* w, const sgp_body_desc* d, uint32_t* id_out, bool ghost)
 	if (d->use_zero_linear_drag) f |= BF_ZERO_LIN_DRAG;
 	if (ghost) f |= BF_GHOST;
 	HostBody& hb = w->hb[id];
-	hb.flags = f; hb.userdata = d->userdata; hb.ghost = ghost; hb.comp_root = SGP_INVALID_ID; hb.comp_child = 0;
+	set_body_flags(w, hb, f); hb.userdata = d->userdata; hb.ghost = ghost; hb.comp_root = SGP_INVALID_ID; hb.comp_child = 0;
 	hb.shape_ref = (is_mesh || d->shape_type == SGP_SHAPE_HULL) ? (uint32_t)d->shape[0] : 0u;
 	if (is_mesh) w->mesh_refs[hb.shape_ref]++; else if (hb.shape_ref) w->hull_refs[hb.shape_ref]++;
 	if (hb.lg_tomb) w->large_dirty = true;      // the slot of a static large body that left a dead entry in the device grid: the grid is rebuilt before anything can find the newcomer through it
@@ -133,7 +133,7 @@ int add_one(sgp_world* w, const sgp_body_desc* d, uint32_t* id_out, bool ghost)
 	if (is_mesh) for (uint32_t k = 1; k <= 2; ++k) {
 		// aliases: same pose and material, flagged large (so never binned) but absent from the large-body list (so never paired or queried)
 		BodyCmd a = c; a.id = id + k; a.flags = hb.flags | BF_ALIAS | BF_LARGE;
-		HostBody& ha = w->hb[id + k]; ha.flags = a.flags; ha.userdata = d->userdata; ha.ghost = false; ha.bound_radius = 0.0f; ha.volume = 0.0f; ha.comp_root = SGP_INVALID_ID; ha.comp_child = 0;
+		HostBody& ha = w->hb[id + k]; set_body_flags(w, ha, a.flags); ha.userdata = d->userdata; ha.ghost = false; ha.bound_radius = 0.0f; ha.volume = 0.0f; ha.comp_root = SGP_INVALID_ID; ha.comp_child = 0;
 		w->cmds.push_back(a);
 	}
 	if (d->activate && d->motion_type != SGP_MOTION_STATIC) { BodyCmd a; memset(&a, 0, sizeof(a)); a.id = id; a.ops = CMD_ACTIVATE; w->cmds.push_back(a); }
@@ -151,7 +151,7 @@ int book_record_body(sgp_world* w, uint32_t* flags_io, uint64_t userdata, float 
 	if (!w->free_list.empty()) { id = w->free_list.back(); w->free_list.pop_back(); }
 	else { if (w->high >= w->dv.cap_bodies) return fail(SGP_ERR_CAPACITY, "sgp_body_add: max_bodies exceeded"); id = w->high++; }
 	HostBody& hb = w->hb[id];
-	hb.flags = *flags_io; hb.userdata = userdata; hb.ghost = ghost; hb.comp_root = SGP_INVALID_ID; hb.comp_child = 0; hb.shape_ref = 0u;
+	set_body_flags(w, hb, *flags_io); hb.userdata = userdata; hb.ghost = ghost; hb.comp_root = SGP_INVALID_ID; hb.comp_child = 0; hb.shape_ref = 0u;
 	if (hb.lg_tomb) w->large_dirty = true;
 	note_radius(w, id, radius);
 	hb.volume = volume;
@@ -284,7 +284,7 @@ SGP_API int sgp_body_remove(sgp_world* w, uint32_t id)
 	const bool was_mesh = ((w->hb[id].flags & BF_SHAPE_MASK) >> BF_SHAPE_SHIFT) == SGP_SHAPE_MESH;
 	if (w->hb[id].shape_ref) { if (was_mesh) w->mesh_refs[w->hb[id].shape_ref]--; else w->hull_refs[w->hb[id].shape_ref]--; w->hb[id].shape_ref = 0; }
 	const uint32_t nslots = was_mesh ? 3u : 1u;
-	for (uint32_t k = 0; k < nslots; ++k) { w->hb[id + k].flags = 0; w->cmds.push_back(blank_cmd(id + k, CMD_REMOVE)); }
+	for (uint32_t k = 0; k < nslots; ++k) { set_body_flags(w, w->hb[id + k], 0u); w->cmds.push_back(blank_cmd(id + k, CMD_REMOVE)); }
 	if (was_mesh) w->free_triples.push_back(id); else w->free_list.push_back(id);       // a triple stays a triple: the next mesh body reuses it
 	w->n_alive--;
 	return SGP_OK;
@@ -319,7 +319,7 @@ SGP_API int sgp_body_set_layer(sgp_world* w, uint32_t id, int32_t layer)
 	for (size_t k = 0; k < n; ++k) {
 		const uint32_t b = rec ? rec->ids[k] : id;
 		BodyCmd c = blank_cmd(b, CMD_SET_LAYER); c.flags = (uint32_t)layer & 0x3u;
-		w->hb[b].flags = (w->hb[b].flags & ~BF_LAYER_MASK) | (((uint32_t)layer & 0x3u) << BF_LAYER_SHIFT);
+		set_body_flags(w, w->hb[b], (w->hb[b].flags & ~BF_LAYER_MASK) | (((uint32_t)layer & 0x3u) << BF_LAYER_SHIFT));
 		w->cmds.push_back(c);
 	}
 	return SGP_OK;

@@ -235,7 +235,8 @@ static void apply_host(sgp_world* w, const CkptHost& h)
 	for (const CkptCompound& c : h.compounds) { CompoundRec r; r.ids = c.ids; r.children = c.children; memcpy(r.pos, c.pos, sizeof(r.pos)); memcpy(r.rot, c.rot, sizeof(r.rot)); w->compounds.emplace(c.id, std::move(r)); }
 	w->ev_act = h.ev_act; w->ev_deact = h.ev_deact; w->ev_water = h.ev_water; w->ev_added = h.ev_added; w->ev_pers = h.ev_pers;
 	w->cmds.clear(); w->ghost_refresh.clear();      // edits queued after the capture belong to the history that is being abandoned
-	w->events_on_device = false;                    // (a capture leaves the device's event lists empty)
+	w->events_on_device = false; w->ev_reset_pending = false;      // (a capture leaves the device's event lists empty)
+	recount_layers(w);
 	w->grid_valid = false;
 }
 
@@ -276,6 +277,7 @@ SGP_API int sgp_world_checkpoint(sgp_world* w, sgp_checkpoint** io)
 	hipSetDevice(w->device);
 	{ int r = flush_cmds(w); if (r != SGP_OK) return r; }      // (stops a resident ray server too)
 	{ int r = collect_events(w); if (r != SGP_OK) return r; }   // raised but not drained: into the host's lists, in order -- what a drain would do first
+	{ int r = flush_event_reset(w); if (r != SGP_OK) return r; }   // ... and the device's counters say so before they are copied
 	CkptCounts c;
 	{ int r = read_device_counts(w, c); if (r != SGP_OK) return r; }
 	std::vector<CkptArray> arrays;

@@ -112,7 +112,11 @@ struct sgp_world {
 	void* stage_dev = nullptr; size_t stage_dev_bytes = 0;
 	void* stage_host = nullptr; size_t stage_host_bytes = 0;
 	void* view_host = nullptr; size_t view_host_bytes = 0;       // pinned buffer of sgp_world_read_active[_poses]_view only
-	StepCounters* h_ctr = nullptr; StepCounters* h_ctr_dev = nullptr; EventCounters* h_evc = nullptr; EventCounters* h_evc_dev = nullptr;
+	StepCounters* h_ctr = nullptr; StepCounters* h_ctr_dev = nullptr;
+	EventWindow* h_evw = nullptr; EventWindow* h_evw_dev = nullptr; EventCounters* h_evc = nullptr;      // host-mapped: what the step's last launch reports (h_evc = &h_evw->c)
+	bool ev_reset_pending = false;                             // the host has pulled the device's event lists; their counters are emptied by the next step's first launch (or by
+	                                                           //   flush_event_reset before anything else that can raise an event)
+	uint32_t layer_counts[SGP_NUM_LAYERS] = { 0 };             // live, non-alias slots per layer: kept as HostBody::flags change (set_body_flags), reported by every step
 	bool dirty_since_step = true;                              // an edit was flushed since the last step (or no step yet)
 	bool events_on_device = true;                              // the device event lists may hold something the host vectors do not (a step without read-back, applied edits)
 	StepParams sp_uploaded; bool sp_uploaded_valid = false;    // what d_sp holds (upload_sp skips the launch when nothing changed)
@@ -220,6 +224,20 @@ static inline bool finite4(const float* v) { return finite3(v) && std::isfinite(
 // The reference only asserts finite inputs in debug builds (PhysicsWorld.cpp:548-556,625,710); a NaN that gets into one body spreads through
 // every contact it touches, so the setters refuse it outright.
 #define REQUIRE_FINITE(cond, what) do { if (!(cond)) return fail(SGP_ERR_INVALID, what ": non-finite argument"); } while (0)
+// every write of HostBody::flags goes through here: sgp_step_stats::layer_counts counts the slots that are alive and no alias slot of a mesh body, under their layer
+static inline bool counts_in_layer(uint32_t f) { return (f & (BF_ALIVE | BF_ALIAS)) == BF_ALIVE; }
+static inline void set_body_flags(sgp_world* w, HostBody& b, uint32_t f)
+{
+	if (counts_in_layer(b.flags)) w->layer_counts[(b.flags & BF_LAYER_MASK) >> BF_LAYER_SHIFT]--;
+	if (counts_in_layer(f)) w->layer_counts[(f & BF_LAYER_MASK) >> BF_LAYER_SHIFT]++;
+	b.flags = f;
+}
+// ... and after the mirror was replaced wholesale (a rollback)
+static inline void recount_layers(sgp_world* w)
+{
+	memset(w->layer_counts, 0, sizeof(w->layer_counts));
+	for (uint32_t i = 0; i < w->high; ++i) if (counts_in_layer(w->hb[i].flags)) w->layer_counts[(w->hb[i].flags & BF_LAYER_MASK) >> BF_LAYER_SHIFT]++;
+}
 static inline bool live(const sgp_world* w, uint32_t id) { return w && id < w->high && (w->hb[id].flags & BF_ALIVE); }
 
 static BodyCmd blank_cmd(uint32_t id, uint32_t ops) { BodyCmd c; memset(&c, 0, sizeof(c)); c.id = id; c.ops = ops; return c; }
@@ -237,6 +255,7 @@ void ray_server_stop(sgp_world* w);      // tells a resident ray server to leave
 void invalidate_graphs(sgp_world* w);
 int flush_cmds(sgp_world* w);
 int collect_events(sgp_world* w, bool counters_fresh = false);
+int flush_event_reset(sgp_world* w);      // empties the device's event counters now if the host has pulled the lists (before edits are applied, before a checkpoint)
 int read_counters(sgp_world* w);
 // defined in sgp_world.hip: the worlds of this process that exist, by serial
 uint64_t world_register(); void world_unregister(uint64_t serial); bool world_alive(uint64_t serial);

@@ -67,7 +67,7 @@ SGP_API int sgp_raycast(sgp_world* w, const sgp_ray* rays, uint32_t n, sgp_hit* 
 	if (!w->grid_valid && w->high) {
 		// poses changed since the grid was built (a step integrates after its broad phase; edits move bodies): re-bin
 		const DV& d = w->dv; hipStream_t s = w->stream; const uint32_t nb = w->high;
-		launch_step_begin(d, *w->h_sp, nb, false, s); w->sp_uploaded = *w->h_sp; w->sp_uploaded_valid = true;
+		launch_step_begin(d, *w->h_sp, nb, false, false, s); w->sp_uploaded = *w->h_sp; w->sp_uploaded_valid = true;
 		launch_bp_bounds(d, nb, s); launch_bp_cell(d, nb, s); launch_bp_scan(d, s); launch_bp_scatter(d, nb, s);
 		w->grid_valid = true;
 	}
@@ -102,7 +102,7 @@ static int ensure_query_grid(sgp_world* w)
 	if (!w->grid_valid && w->high) {
 		// poses changed since the grid was built (a step integrates after its broad phase; edits move bodies): re-bin
 		const DV& d = w->dv; hipStream_t s = w->stream; const uint32_t nb = w->high;
-		launch_step_begin(d, *w->h_sp, nb, false, s); w->sp_uploaded = *w->h_sp; w->sp_uploaded_valid = true;
+		launch_step_begin(d, *w->h_sp, nb, false, false, s); w->sp_uploaded = *w->h_sp; w->sp_uploaded_valid = true;
 		launch_bp_bounds(d, nb, s); launch_bp_cell(d, nb, s); launch_bp_scan(d, s); launch_bp_scatter(d, nb, s);
 		w->grid_valid = true;
 	}

@@ -131,6 +131,7 @@ static int import_ghosts_view(sgp_world* w, const GhostView& in, uint32_t n, con
 			if (dev) {
 				{ int r = flush_cmds(w); if (r != SGP_OK) return r; }
 				if (skip || *dev->ids_version != w->ghost_seq_version) { int r = upload_ghost_ids(w, dev, skip, n_all); if (r != SGP_OK) return r; }      // (the set was last changed by an import that did not come through here; or the records hold immigrants between the ghosts)
+				{ int r = flush_event_reset(w); if (r != SGP_OK) return r; }      // (the launch below raises activation events)
 				launch_ghost_refresh_records(w->dv, dev->d_recs, *dev->d_ids, n_all, w->stream);
 				w->grid_valid = false; w->dirty_since_step = true;
 				return SGP_OK;
@@ -219,6 +220,7 @@ static int import_ghosts_view(sgp_world* w, const GhostView& in, uint32_t n, con
 		// record -- non-finite pose ... -- has "no body" in the id array, like an immigrant's: the kernel passes over it)
 		{ int r = flush_cmds(w); if (r != SGP_OK) return r; }
 		{ int r = upload_ghost_ids(w, dev, skip, n_all); if (r != SGP_OK) return r; }
+		{ int r = flush_event_reset(w); if (r != SGP_OK) return r; }      // (the launch below raises activation events)
 		launch_ghost_refresh_records(w->dv, dev->d_recs, *dev->d_ids, n_all, w->stream);
 		w->grid_valid = false; w->dirty_since_step = true;
 	}
@@ -608,6 +610,7 @@ static int tiles_launch_creates(sgp_tiles* t)
 	memcpy(t->h_create, w->rec_creates.data(), sizeof(uint4) * n);
 	HIP_TRY(hipMemcpyAsync(t->d_create, t->h_create, sizeof(uint4) * n, hipMemcpyHostToDevice, w->stream));
 	sgp_body_desc def; sgp_default_body_desc(&def);
+	{ int r = flush_event_reset(w); if (r != SGP_OK) return r; }      // (the launch below raises activation events)
 	launch_create_from_records(w->dv, t->d_recv, t->d_create, n, def.gravity_factor, def.linear_damping, def.angular_damping, w->stream);
 	t->stats.device_creates += n;
 	w->rec_creates.clear();
@@ -644,6 +647,7 @@ static int tiles_import(sgp_tiles* t, uint32_t n)
 			{ int r = flush_cmds(w); if (r != SGP_OK) return r; }
 			GhostDeviceSource dev = { t->d_recv, &t->d_seq_ids, &t->cap_seq, &t->ids_version };
 			if (t->ids_version != w->ghost_seq_version) { int r = upload_ghost_ids(w, &dev); if (r != SGP_OK) return r; }
+			{ int r = flush_event_reset(w); if (r != SGP_OK) return r; }      // (the launch below raises activation events)
 			launch_ghost_refresh_records(w->dv, t->d_recv, t->d_seq_ids, n, w->stream);
 			w->grid_valid = false; w->dirty_since_step = true;
 			t->stats.ghosts = n; t->stats.immigrated = 0; t->stats.fast_imports++;
