@@ -364,7 +364,7 @@ int  sgp_world_launch_counts(sgp_world* w, uint32_t* graph_replays_out, uint32_t
 const char* sgp_kernel_class_name(int k);
 /* sizeof() of ABI struct number `which` (order: settings, world_desc, body_desc, body_state, body_event, contact_event,
  * ray, hit, step_stats, step_profile, ghost_record, vehicle_desc, vehicle_input, vehicle_state, hull_info, capsule_query,
- * query_contact, mesh_info, heightfield_desc) so bindings can verify their layout. */
+ * query_contact, mesh_info, heightfield_desc, checkpoint_info, shape_query) so bindings can verify their layout. */
 int  sgp_abi_sizeof(int which);
 /* activated_obs / newly_activated_obs maintenance + listener callbacks (PhysicsWorld.h:194-200). */
 int  sgp_world_drain_events(sgp_world* w, int kind, void* out, uint32_t cap, uint32_t* n_out);
@@ -606,6 +606,32 @@ typedef struct sgp_query_contact {
 int  sgp_collide_capsules(sgp_world* w, const sgp_capsule_query* queries, uint32_t n, sgp_query_contact* out, uint32_t cap, uint32_t* n_out);
 /* Sphere casts (rays with thickness): hit.t = distance travelled by the centre until first touch, hit.normal at the touch point. */
 int  sgp_spherecast(sgp_world* w, const sgp_ray* rays, const float* radii, uint32_t n, sgp_hit* hits_out);
+
+/* ---- overlap queries with any convex shape (JPH::NarrowPhaseQuery::CollideShape) --------------------
+ * "What is inside this volume?": a box for a parcel or a trigger volume, a sphere for an explosion or an audio radius, the hull of an
+ * object for a placement test before it is added -- thousands of them per call if need be.  Every query reports the contacts of its shape
+ * with every body whose surface lies within max_separation of it, as sgp_query_contact records: `normal` points from the body towards
+ * the query shape, `point` lies on the body, sensors are reported.  A compound child reports the compound's id and its child index in
+ * `sub_shape`. */
+#define SGP_QUERY_DEEPEST_ONLY 1u   /* sgp_shape_query::flags */
+typedef struct sgp_shape_query {
+	float    pos[3], rot[4];
+	int32_t  shape_type;        /* SGP_SHAPE_SPHERE | BOX | CAPSULE | HULL; shape[] as in sgp_body_desc (hull: shape[0] = hull id of this world) */
+	float    shape[4];
+	float    max_separation;    /* report surfaces closer than this; 0 = touching or overlapping only */
+	uint32_t ignore_id;
+	uint32_t layer_mask;        /* bit l set: bodies of layer l answer; 0 = all four (collidable_only of the capsule query = 0x3) */
+	uint32_t flags;             /* SGP_QUERY_DEEPEST_ONLY: one contact per (query, body), the deepest point of its first manifold
+	                               (a compound answers once per touched child) */
+	float    movement[3];
+	uint32_t active_edges;      /* as in sgp_capsule_query */
+} sgp_shape_query;
+/* Contacts come back sorted by (query, body, point).  n_out is the exact size of the whole answer and may exceed cap: what is written is then
+ * the first cap records of the sorted answer.  SGP_ERR_INVALID, with nothing launched and nothing written, when any query names a hull that
+ * does not exist, asks with SGP_SHAPE_MESH (or an unknown type), or holds a non-finite pose or a non-positive size.  n == 0 is SGP_OK.
+ * Many small volumes are answered from a list of candidate (query, body) pairs, a thread per pair; a few large ones by a wave per query:
+ * the same records either way (SGP_QUERY_PATH=wave|pairs, read at world creation, forces one). */
+int  sgp_collide_shapes(sgp_world* w, const sgp_shape_query* queries, uint32_t n, sgp_query_contact* out, uint32_t cap, uint32_t* n_out);
 
 /* ---- multi-GPU tiles: ghost bodies are ordinary kinematic-like bodies owned elsewhere ---- */
 /* Pack the ghost record of every owned body whose AABB, inflated by `margin`, crosses outside [lo,hi). */

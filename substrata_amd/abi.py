@@ -205,6 +205,15 @@ class CapsuleQuery(C.Structure):
                 ("ignore_id", u32), ("collidable_only", u32), ("movement", f32 * 3), ("active_edges", u32)]
 
 
+QUERY_DEEPEST_ONLY = 1
+
+
+class ShapeQuery(C.Structure):
+    """sgp_shape_query: one overlap query of sgp_collide_shapes (a sphere, box, capsule or convex hull at a pose)."""
+    _fields_ = [("pos", f32 * 3), ("rot", f32 * 4), ("shape_type", i32), ("shape", f32 * 4), ("max_separation", f32),
+                ("ignore_id", u32), ("layer_mask", u32), ("flags", u32), ("movement", f32 * 3), ("active_edges", u32)]
+
+
 class CompoundChild(C.Structure):
     _fields_ = [("shape_type", i32), ("shape", f32 * 4), ("pos", f32 * 3), ("rot", f32 * 4)]
 
@@ -230,13 +239,17 @@ ABI_SIZEOF_ORDER = ["sgp_settings", "sgp_world_desc", "sgp_body_desc", "sgp_body
                     "sgp_vehicle_desc", "sgp_vehicle_input", "sgp_vehicle_state", "sgp_hull_info",
                     "sgp_capsule_query", "sgp_query_contact", "sgp_mesh_info", "sgp_heightfield_desc", "sgp_checkpoint_info"]
 
+# structs appended to sgp_abi_sizeof after ABI_SIZEOF_ORDER was fixed (their indices follow its last one; nothing before them moves)
+ABI_SIZEOF_APPENDED = ["sgp_shape_query"]
+ABI_SIZEOF_ALL = ABI_SIZEOF_ORDER + ABI_SIZEOF_APPENDED
+
 STRUCTS = {"sgp_settings": Settings, "sgp_world_desc": WorldDesc, "sgp_body_desc": BodyDesc,
            "sgp_body_state": BodyState, "sgp_body_event": BodyEvent, "sgp_contact_event": ContactEvent,
            "sgp_ray": Ray, "sgp_hit": Hit, "sgp_step_stats": StepStats, "sgp_step_profile": StepProfile,
            "sgp_ghost_record": GhostRecord, "sgp_vehicle_desc": VehicleDesc, "sgp_vehicle_input": VehicleInput,
            "sgp_vehicle_state": VehicleState, "sgp_hull_info": HullInfo, "sgp_capsule_query": CapsuleQuery,
            "sgp_query_contact": QueryContact, "sgp_mesh_info": MeshInfo, "sgp_heightfield_desc": HeightfieldDesc,
-           "sgp_checkpoint_info": CheckpointInfo}
+           "sgp_checkpoint_info": CheckpointInfo, "sgp_shape_query": ShapeQuery}
 
 body_desc_dtype = np.dtype(BodyDesc)
 body_state_dtype = np.dtype(BodyState)
@@ -252,6 +265,7 @@ vehicle_input_dtype = np.dtype(VehicleInput)
 vehicle_state_dtype = np.dtype(VehicleState)
 capsule_query_dtype = np.dtype(CapsuleQuery)
 query_contact_dtype = np.dtype(QueryContact)
+shape_query_dtype = np.dtype(ShapeQuery)
 compound_child_dtype = np.dtype(CompoundChild)
 migration_dtype = np.dtype(Migration)
 
@@ -317,6 +331,7 @@ PROTOTYPES = {
     "raycast": (C.c_int, [vp, vp, u32, vp]),
     "collide_capsules": (C.c_int, [vp, vp, u32, vp, u32, P(u32)]),
     "spherecast": (C.c_int, [vp, vp, vp, u32, vp]),
+    "collide_shapes": (C.c_int, [vp, vp, u32, vp, u32, P(u32)]),
     "world_export_boundary": (C.c_int, [vp, P(f32), P(f32), f32, vp, u32, P(u32)]),
     "world_import_ghosts": (C.c_int, [vp, vp, u32]),
     "tiles_route": (C.c_int, [vp, u32, u32, vp, u32, f32, vp, u32, vp, vp, u32, P(u32)]),

@@ -1,0 +1,278 @@
+// sgp_k_shapequery.hip -- A7 -- overlap queries with a sphere, box, capsule or convex hull (sgp_collide_shapes; JPH::NarrowPhaseQuery::CollideShape).
+// One of the stage files of the step kernels (stage map: sgp_kernels.h).  Kernels first, their launch wrappers at the end.
+//
+// Two organisations, one answer.  A WAVE PER QUERY (k_sq_wave: k_collide_capsules with the query shape built from sgp_shape_query) for the one or few
+// volumes somebody waits for, and for a volume with hundreds of candidates: the candidates are dealt to the 64 lanes.  CANDIDATE PAIRS for thousands of
+// small volumes that touch a handful of bodies each (60 of a wave's 64 lanes would idle): k_sq_candidates, a thread per query, walks the broad-phase
+// structures under the query's bounds and appends (query, body) to one of three lists; then a thread per pair (k_sq_pairs_prim: sphere / box / capsule on
+// both sides, nothing of the hull search in it; k_sq_pairs_hull: a convex hull on either side) and a wave per pair whose body is a mesh (k_sq_mesh, which
+// the wave-per-query organisation uses too).  Every record is a function of its (query, body) pair alone -- the same device functions collide it in either
+// organisation -- and the host sorts the records by (query, body, point): the answer depends neither on the organisation nor on the order of the atomics.
+// Nothing here drops silently: a list or the output that is too small is counted past its capacity, and the host runs the call again with more room.
+#include "sgp_dev_all.h"
+
+// the query's shape record and, BOUNDS: its world bounds grown by max_separation (a capsule: the expressions of k_collide_capsules, bit for bit)
+template <bool BOUNDS> SGP_DEV void sq_shape(const DV& d, const sgp_shape_query& q, sgd_shape& X, v3& lo, v3& hi)
+{
+	X.pos = V3(q.pos[0], q.pos[1], q.pos[2]);
+	quat qq; qq.x = q.rot[0]; qq.y = q.rot[1]; qq.z = q.rot[2]; qq.w = q.rot[3];
+	X.R = quat_to_m33(qq); X.type = (int)q.shape_type; X.hull = nullptr;
+	if (q.shape_type == SGP_SHAPE_CAPSULE) {
+		X.p0 = q.shape[0]; X.p1 = q.shape[1]; X.p2 = 0.0f;
+		if (BOUNDS) {
+			const v3 ax = v3_scale(X.R.c2, q.shape[1]);
+			const float e = q.shape[0] + q.max_separation;
+			const v3 ext = V3(fabsf(ax.x) + e, fabsf(ax.y) + e, fabsf(ax.z) + e);
+			lo = v3_sub(X.pos, ext); hi = v3_add(X.pos, ext);
+		}
+		return;
+	}
+	X.p0 = q.shape[0]; X.p1 = q.shape[1]; X.p2 = q.shape[2];
+	if (q.shape_type == SGP_SHAPE_SPHERE) { X.p1 = 0.0f; X.p2 = 0.0f; }
+	else if (q.shape_type == SGP_SHAPE_BOX) X.hull = &d.hulls[0];
+	else X.hull = &d.hulls[(uint32_t)q.shape[0]];      // (the host has checked the id)
+	if (BOUNDS) {
+		v3 mn, mx;
+		compute_aabb(d, (uint32_t)q.shape_type, make_float4(q.shape[0], q.shape[1], q.shape[2], q.shape[3]), X.pos, qq, mn, mx);
+		const v3 e = V3(q.max_separation, q.max_separation, q.max_separation);
+		lo = v3_sub(mn, e); hi = v3_add(mx, e);
+	}
+}
+
+// the filters every candidate passes before anything is computed for it: ignore_id, alive and no alias slot, the layer mask, the bounds
+SGP_DEV bool sq_passes(const DV& d, const sgp_shape_query& q, v3 lo, v3 hi, uint32_t j, uint32_t* f_out)
+{
+	if (j == q.ignore_id) return false;
+	const uint32_t f = d.flags[j];
+	if (!(f & BF_ALIVE) || (f & BF_ALIAS)) return false;
+	const uint32_t mask = q.layer_mask ? q.layer_mask : 0xFu;
+	if (!((mask >> f_layer(f)) & 1u)) return false;
+	const float4 mn = d.aabb_min[j], mx = d.aabb_max[j];
+	if (mx.x < lo.x || mn.x > hi.x || mx.y < lo.y || mn.y > hi.y || mx.z < lo.z || mn.z > hi.z) return false;
+	*f_out = f;
+	return true;
+}
+
+// fn(body) for the candidates of the bounds [lo, hi] -- the large bodies, those of the static large bodies' grid, those of the cell rows under the bounds --
+// dealt to W lanes (W = 64: the lanes of a wave walk together, as k_collide_capsules does; W = 1: one lane takes them all)
+template <int W, class F> SGP_DEV void sq_walk(const DV& d, v3 lo, v3 hi, uint32_t lane, F fn)
+{
+	for (uint32_t l = lane; l < d.sp->n_large; l += W) fn(d.large_ids[l]);
+	{
+		uint32_t seen = 0;
+		large_grid_query(d, lo, hi, [&](uint32_t i) { if (W == 1 || (seen++ & (uint32_t)(W - 1)) == lane) fn(i); });
+	}
+	const BpGrid g = *d.grid;
+	if (g.n_cells > 0 && g.min_x <= g.max_x) {
+		const int x0 = max((int)floorf((lo.x - g.ox) * g.inv_cell) - 1, 0), x1 = min((int)floorf((hi.x - g.ox) * g.inv_cell) + 1, g.nx - 1);
+		const int y0 = max((int)floorf((lo.y - g.oy) * g.inv_cell) - 1, 0), y1 = min((int)floorf((hi.y - g.oy) * g.inv_cell) + 1, g.ny - 1);
+		const int z0 = max((int)floorf((lo.z - g.oz) * g.inv_cell) - 1, 0), z1 = min((int)floorf((hi.z - g.oz) * g.inv_cell) + 1, g.nz - 1);
+		if (x0 <= x1) for (int z = z0; z <= z1; ++z) for (int y = y0; y <= y1; ++y) {
+			grid_row_runs(d, g, x0, x1, y, z, [&](uint32_t c0, uint32_t c1) { for (uint32_t c = c0 + lane; c < c1; c += W) fn(__float_as_uint(d.sorted_max[c].w)); });
+		}
+	}
+}
+
+// one (body j, query shape X) pair of convex shapes: the manifold with its normal from the body to the query shape
+// (clip: the lane's two polygon columns of the box - box clip, sgd_box_box<true>)
+SGP_DEV bool sq_collide_prim(const DV& d, const sgd_shape& X, float max_sep, uint32_t j, uint32_t f, float* clip, sgd_manifold* m)
+{
+	const sgd_shape sb = load_shape(d, j, f);
+	return sgd_collide<true>(&sb, &X, max_sep, m, clip) != 0;
+}
+SGP_DEV bool sq_collide_hull(const DV& d, const sgd_shape& X, float max_sep, uint32_t j, uint32_t f, sgd_manifold* m)
+{
+	const sgd_shape sb = load_shape(d, j, f);
+	return sgd_collide_hull(&sb, &X, max_sep, m) != 0;
+}
+
+// how many records manifold g of a (query, body) pair gives, and the records (capsule_emit's, field by field) from slot `base` on
+SGP_DEV int sq_num_records(const sgp_shape_query& q, int g, const sgd_manifold& m)
+{
+	if (q.flags & SGP_QUERY_DEEPEST_ONLY) return (g == 0 && m.np > 0) ? 1 : 0;
+	return m.np;
+}
+SGP_DEV void sq_record(const DV& d, uint32_t k, uint32_t j, uint32_t f, int g, const sgd_manifold& m, int i, sgp_query_contact* dst)
+{
+	sgp_query_contact c;
+	c.query = k; c.body = j; c.sub_shape = (uint32_t)(4 * g + i);      // point index for the host's sort; the host then stores the compound child index here
+	c.point[0] = m.p1[i].x; c.point[1] = m.p1[i].y; c.point[2] = m.p1[i].z;
+	c.normal[0] = m.n.x; c.normal[1] = m.n.y; c.normal[2] = m.n.z;
+	c.distance = v3_dot(v3_sub(m.p2[i], m.p1[i]), m.n);
+	v3 pv = V3(0.0f, 0.0f, 0.0f);
+	if (f_motion(f) != SGP_MOTION_STATIC) pv = v3_add(V3(d.vel[VEL_F4 * (size_t)j]), v3_cross(V3(d.vel[VEL_F4 * (size_t)j + 1]), v3_sub(m.p1[i], V3(d.pose[POSE_F4 * (size_t)j]))));
+	c.point_velocity[0] = pv.x; c.point_velocity[1] = pv.y; c.point_velocity[2] = pv.z;
+	c.motion_type = f_motion(f); c.is_sensor = (f & BF_SENSOR) ? 1u : 0u; c.inv_mass = d.pose[POSE_F4 * (size_t)j].w; c.userdata = 0;
+	*dst = c;
+}
+SGP_DEV void sq_emit_at(const DV& d, const SqBufs& b, const sgp_shape_query& q, uint32_t k, uint32_t j, uint32_t f, int g, const sgd_manifold& m, uint32_t base)
+{
+	if (q.flags & SGP_QUERY_DEEPEST_ONLY) {
+		if (g != 0 || m.np <= 0) return;
+		int best = 0; float bd = v3_dot(v3_sub(m.p2[0], m.p1[0]), m.n);
+#pragma unroll
+		for (int i = 1; i < 4; ++i) if (i < m.np) { const float di = v3_dot(v3_sub(m.p2[i], m.p1[i]), m.n); if (di < bd) { bd = di; best = i; } }      // (ties: the lower point index)
+		if (base < b.cap) {
+#pragma unroll
+			for (int i = 0; i < 4; ++i) if (i == best) sq_record(d, k, j, f, g, m, i, &b.out[base]);      // (static slots: the manifold stays in registers)
+		}
+		return;
+	}
+#pragma unroll
+	for (int i = 0; i < 4; ++i) if (i < m.np && base + (uint32_t)i < b.cap) sq_record(d, k, j, f, g, m, i, &b.out[base + (uint32_t)i]);
+}
+// ... with the slots taken by this lane alone (divergent callers)
+SGP_DEV void sq_emit(const DV& d, const SqBufs& b, const sgp_shape_query& q, uint32_t k, uint32_t j, uint32_t f, int g, const sgd_manifold& m)
+{
+	const int nr = sq_num_records(q, g, m);
+	if (nr > 0) sq_emit_at(d, b, q, k, j, f, g, m, atomicAdd(&b.ctr[SQ_N_OUT], (uint32_t)nr));
+}
+// Slots for every lane of a wave with ONE atomic (whole wave: every lane calls this, nr = 0 for a lane with nothing to write)
+SGP_DEV uint32_t sq_wave_slots(uint32_t* counter, int nr)
+{
+	const int lane = (int)(threadIdx.x & 63u);
+	int incl = nr;
+#pragma unroll
+	for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(incl, off, 64); if (lane >= off) incl += o; }
+	const int total = __shfl(incl, 63, 64);
+	uint32_t base = 0;
+	if (lane == 0 && total > 0) base = atomicAdd(counter, (uint32_t)total);
+	base = (uint32_t)__shfl((int)base, 0, 64);
+	return base + (uint32_t)(incl - nr);
+}
+// a candidate on its list (the lanes of the wave that append to the same list at the same time share one atomic)
+SGP_DEV void sq_append(const SqBufs& b, int which, uint2* list, uint32_t k, uint32_t j)
+{
+	const uint32_t at = wave_alloc(&b.ctr[which]);
+	if (at < b.pcap) list[at] = make_uint2(k, j);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// a wave per query
+
+__global__ void __launch_bounds__(64) k_sq_wave(DV d, SqBufs b)
+{
+	__shared__ float s_clip[2 * SGD_LPOLY_FLOATS];
+	const uint32_t lane = threadIdx.x;
+	for (uint32_t k = blockIdx.x; k < b.n; k += gridDim.x) {
+		const sgp_shape_query q = b.qs[k];
+		sgd_shape X; v3 lo, hi;
+		sq_shape<true>(d, q, X, lo, hi);
+		sq_walk<64>(d, lo, hi, lane, [&](uint32_t j) {
+			uint32_t f;
+			if (!sq_passes(d, q, lo, hi, j, &f)) return;
+			const uint32_t st = f_shape(f);
+			if (st == SGP_SHAPE_MESH) { sq_append(b, SQ_N_MESH, b.mesh, k, j); return; }      // (its triangles are a whole wave's work: k_sq_mesh)
+			sgd_manifold m;
+			const bool hit = (st == SGP_SHAPE_HULL || q.shape_type == SGP_SHAPE_HULL) ? sq_collide_hull(d, X, q.max_separation, j, f, &m) : sq_collide_prim(d, X, q.max_separation, j, f, &s_clip[lane], &m);
+			if (hit) sq_emit(d, b, q, k, j, f, 0, m);
+		});
+	}
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// candidate pairs: a thread per query finds them ...
+
+__global__ void __launch_bounds__(64) k_sq_candidates(DV d, SqBufs b)
+{
+	const uint32_t k = blockIdx.x * 64 + threadIdx.x;
+	if (k >= b.n) return;
+	const sgp_shape_query q = b.qs[k];
+	sgd_shape X; v3 lo, hi;
+	sq_shape<true>(d, q, X, lo, hi);
+	sq_walk<1>(d, lo, hi, 0u, [&](uint32_t j) {
+		uint32_t f;
+		if (!sq_passes(d, q, lo, hi, j, &f)) return;
+		const uint32_t st = f_shape(f);
+		if (st == SGP_SHAPE_MESH) sq_append(b, SQ_N_MESH, b.mesh, k, j);
+		else if (st == SGP_SHAPE_HULL || q.shape_type == SGP_SHAPE_HULL) sq_append(b, SQ_N_HULL, b.hull, k, j);
+		else sq_append(b, SQ_N_PRIM, b.prim, k, j);
+	});
+}
+
+// ... a thread per pair collides them: spheres, boxes and capsules on both sides (the box - box clip polygons in LDS: no scratch) ...
+__global__ void __launch_bounds__(64) k_sq_pairs_prim(DV d, SqBufs b)
+{
+	__shared__ float s_clip[2 * SGD_LPOLY_FLOATS];
+	const uint32_t n = min(b.ctr[SQ_N_PRIM], b.pcap);
+	const uint32_t lane = threadIdx.x;
+	for (uint32_t p0 = blockIdx.x * 64u; p0 < n; p0 += gridDim.x * 64u) {
+		const uint32_t p = p0 + lane;
+		sgd_manifold m; m.np = 0;
+		uint2 kj = make_uint2(0u, 0u); uint32_t f = 0; int nr = 0;
+		sgp_shape_query q;
+		if (p < n) {
+			kj = b.prim[p];
+			q = b.qs[kj.x];
+			sgd_shape X; v3 lo, hi;
+			sq_shape<false>(d, q, X, lo, hi);
+			f = d.flags[kj.y];
+			if (sq_collide_prim(d, X, q.max_separation, kj.y, f, &s_clip[lane], &m)) nr = sq_num_records(q, 0, m);
+		}
+		const uint32_t base = sq_wave_slots(&b.ctr[SQ_N_OUT], nr);
+		if (nr > 0) sq_emit_at(d, b, q, kj.x, kj.y, f, 0, m, base);
+	}
+}
+// ... and the pairs with a convex hull on either side (the sequential separating-axis search: its clip buffers and long loops stay out of the kernel above)
+__global__ void __launch_bounds__(64) k_sq_pairs_hull(DV d, SqBufs b)
+{
+	const uint32_t n = min(b.ctr[SQ_N_HULL], b.pcap);
+	for (uint32_t p = blockIdx.x * 64u + threadIdx.x; p < n; p += gridDim.x * 64u) {
+		const uint2 kj = b.hull[p];
+		const sgp_shape_query q = b.qs[kj.x];
+		sgd_shape X; v3 lo, hi;
+		sq_shape<false>(d, q, X, lo, hi);
+		const uint32_t f = d.flags[kj.y];
+		sgd_manifold m;
+		if (sq_collide_hull(d, X, q.max_separation, kj.y, f, &m)) sq_emit(d, b, q, kj.x, kj.y, f, 0, m);
+	}
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// (query, mesh body) pairs of either organisation: a wave per pair, 64 candidate triangles per round (mesh_pair_groups, as k_collide_capsules takes them)
+
+__global__ void __launch_bounds__(64) k_sq_mesh(DV d, SqBufs b)
+{
+	__shared__ MeshPairLds<64> L;
+	const uint32_t n = min(b.ctr[SQ_N_MESH], b.pcap);
+	const uint32_t lane = threadIdx.x;
+	for (uint32_t p = blockIdx.x; p < n; p += gridDim.x) {
+		const uint2 kj = b.mesh[p];
+		const sgp_shape_query q = b.qs[kj.x];
+		const uint32_t mid = kj.y;
+		sgd_shape X; v3 lo, hi;
+		sq_shape<true>(d, q, X, lo, hi);
+		const v3 es = V3(q.max_separation, q.max_separation, q.max_separation);
+		const v3 mv = V3(q.movement[0], q.movement[1], q.movement[2]);
+		bool valid = true, dropped = false;
+		// (a capsule: the instance k_collide_capsules uses, nothing of the polytope search in it)
+		if (q.shape_type == SGP_SHAPE_CAPSULE) mesh_pair_groups<64, 4>(d, L, valid, X, mid, v3_sub(lo, es), v3_add(hi, es), q.max_separation, 0, (int)lane, 0u, dropped, mv, q.active_edges != 0u);
+		else mesh_pair_groups<64, SGD_KINDS_ALL>(d, L, valid, X, mid, v3_sub(lo, es), v3_add(hi, es), q.max_separation, 0, (int)lane, 0u, dropped, mv, q.active_edges != 0u);
+		if ((int)lane < L.mc.ng) {
+			const sgd_mesh_group& grp = L.mc.g[lane];
+			sgd_manifold mm;
+			sgd_hull_reduce(grp.n, grp.p_mesh, grp.p_body, grp.np, &mm);
+			sq_emit(d, b, q, kj.x, mid, d.flags[mid], (int)lane, mm);
+		}
+		__syncthreads();          // (the tables are reused by the next pair)
+	}
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// launch wrappers (the list kernels stride over what the lists hold when they start: their grids follow the capacities, which the host sized from the last call)
+
+static inline uint32_t sq_list_blocks(uint32_t items, uint32_t per_block, uint32_t most) { return std::min(std::max((items + per_block - 1u) / per_block, 1u), most); }
+void launch_shape_queries_wave(const DV& d, const SqBufs& b, hipStream_t s)
+{
+	if (!b.n) return;
+	hipLaunchKernelGGL(k_sq_wave, dim3(std::min(b.n, 65536u)), dim3(64), 0, s, d, b);
+	hipLaunchKernelGGL(k_sq_mesh, dim3(sq_list_blocks(std::min(b.pcap, 4u * b.n), 1u, 4096u)), dim3(64), 0, s, d, b);
+}
+void launch_shape_queries_pairs(const DV& d, const SqBufs& b, hipStream_t s)
+{
+	if (!b.n) return;
+	hipLaunchKernelGGL(k_sq_candidates, dim3((b.n + 63u) / 64u), dim3(64), 0, s, d, b);
+	hipLaunchKernelGGL(k_sq_pairs_prim, dim3(sq_list_blocks(b.pcap, 64u, 4096u)), dim3(64), 0, s, d, b);
+	hipLaunchKernelGGL(k_sq_pairs_hull, dim3(sq_list_blocks(b.pcap, 64u, 4096u)), dim3(64), 0, s, d, b);
+	hipLaunchKernelGGL(k_sq_mesh, dim3(sq_list_blocks(std::min(b.pcap, 4u * b.n), 1u, 4096u)), dim3(64), 0, s, d, b);
+}

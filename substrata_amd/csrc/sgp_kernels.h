@@ -12,6 +12,7 @@
 //   sgp_k_sweep.hip        K8/K1/K9/A3  the body-array sweep k_pre_solve + k_integrate_pose + k_finalize, k_island_*, k_sleep_apply, k_buoyancy (PhysicsWorld.cpp:1367-1442)
 //   sgp_k_vehicle.hip      (f)1   k_vehicle_cast / controller, the vehicle rows inside the solver passes (k_solve_colour_veh)
 //   sgp_k_queries.hip      A7     k_raycast, k_collide_capsules, k_spherecast
+//   sgp_k_shapequery.hip   A7     k_sq_wave, k_sq_candidates + k_sq_pairs_prim / k_sq_pairs_hull / k_sq_mesh (sgp_collide_shapes)
 //   sgp_k_edits.hip        A5/A6  k_apply_cmds, k_ghost_refresh, read-back
 //   sgp_k_tiles.hip        (e)    tile export / routing, re-tiling histograms
 //   sgp_k_checkpoint.hip          k_ckpt_copy: the segmented copy of sgp_world_checkpoint / sgp_world_rollback
@@ -455,6 +456,18 @@ void launch_ray_server(const DV& d, RayMailbox* mb, uint32_t first_seq, uint32_t
 void launch_raycast(const DV& d, const sgp_ray* rays, uint32_t n, sgp_hit* hits, hipStream_t s);
 void launch_collide_capsules(const DV& d, const sgp_capsule_query* q, uint32_t n, sgp_query_contact* out, uint32_t cap, uint32_t* count, hipStream_t s);
 void launch_spherecast(const DV& d, const sgp_ray* rays, const float* radii, uint32_t n, sgp_hit* hits, hipStream_t s);
+// sgp_collide_shapes (sgp_k_shapequery.hip): the buffers of one call, all of them in the world's stage buffer.  ctr: SQ_N_OUT contacts found (all of them: what
+// does not fit in `out` is counted, not written), then the candidate (query, body) pairs found per list (likewise) -- the host compares them with the capacities
+// and runs the call again with larger ones when something did not fit.
+enum { SQ_N_OUT = 0, SQ_N_PRIM = 1, SQ_N_HULL = 2, SQ_N_MESH = 3 };
+struct SqBufs {
+	const sgp_shape_query* qs; uint32_t n;
+	sgp_query_contact* out; uint32_t cap;
+	uint32_t* ctr;
+	uint2* prim; uint2* hull; uint2* mesh; uint32_t pcap;      // pairs of sphere / box / capsule shapes, pairs with a convex hull on either side, pairs whose body is a mesh; pcap entries each
+};
+void launch_shape_queries_wave(const DV& d, const SqBufs& b, hipStream_t s);       // a wave per query (mesh bodies: through the mesh list, a wave per pair)
+void launch_shape_queries_pairs(const DV& d, const SqBufs& b, hipStream_t s);      // candidate pairs by a thread per query, then a thread per pair (mesh bodies: a wave per pair)
 void launch_export_boundary(const DV& d, uint32_t nb, float3 lo, float3 hi, float margin, sgp_ghost_record* out, uint32_t cap, uint32_t* count, hipStream_t s);
 
 // ---- tile exchange with the routing on the device (sgp_tiles_*) ----------------------------------------------------

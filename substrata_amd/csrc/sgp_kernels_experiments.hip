@@ -12,6 +12,7 @@
 #include "sgp_k_sweep.hip"
 #include "sgp_k_edits.hip"
 #include "sgp_k_queries.hip"
+#include "sgp_k_shapequery.hip"
 #include "sgp_k_vehicle.hip"
 #include "sgp_k_tiles.hip"
 #include "sgp_k_checkpoint.hip"

@@ -78,7 +78,7 @@ SGP_API int sgp_abi_sizeof(int which)
 	case 9: return (int)sizeof(sgp_step_profile); case 10: return (int)sizeof(sgp_ghost_record);
 	case 11: return (int)sizeof(sgp_vehicle_desc); case 12: return (int)sizeof(sgp_vehicle_input); case 13: return (int)sizeof(sgp_vehicle_state);
 	case 14: return (int)sizeof(sgp_hull_info); case 15: return (int)sizeof(sgp_capsule_query); case 16: return (int)sizeof(sgp_query_contact); case 17: return (int)sizeof(sgp_mesh_info);
-	case 18: return (int)sizeof(sgp_heightfield_desc); case 19: return (int)sizeof(sgp_checkpoint_info);
+	case 18: return (int)sizeof(sgp_heightfield_desc); case 19: return (int)sizeof(sgp_checkpoint_info); case 20: return (int)sizeof(sgp_shape_query);
 	default: return -1;
 	}
 }
@@ -235,6 +235,7 @@ SGP_API int sgp_world_create(const sgp_world_desc* desc, sgp_world** out)
 	{ const char* e = getenv("SGP_NO_GRAPH"); if (e && e[0] == '1') w->use_graphs = false; }
 	{ const char* e = getenv("SGP_NO_SMALL_WORLD"); if (e && e[0] == '1') w->use_small_world = false; }
 	{ const char* e = getenv("SGP_NO_RAY_SERVER"); if (e && e[0] == '1') w->ray_server_enabled = false; }      // (single rays then cost a launch + a sync each)
+	{ const char* e = getenv("SGP_QUERY_PATH"); if (e && !strcmp(e, "wave")) w->query_path = 1; else if (e && !strcmp(e, "pairs")) w->query_path = 2; }      // (sgp_collide_shapes: one organisation for every call; the same records)
 	{ const char* e = getenv("SGP_NO_WAKE_ROUND"); if (e && e[0] == '1') w->use_wake_round = false; }      // (measurements only: the CPU statement has its own switch)
 	{ const char* e = getenv("SGP_CHECKPOINT_FULL"); if (e && e[0] == '1') w->checkpoint_full = true; }      // (checkpoints copy every device allocation whole: the A side of profiles/r08_checkpoint.md)
 	w->serial = world_register();

@@ -143,6 +143,9 @@ struct sgp_world {
 	// single-query mailbox (sgp_raycast with n = 1): host-mapped block + whether a server wave is (believed to be) resident on the stream
 	RayMailbox* ray_mb = nullptr; bool ray_server_on = false; bool ray_server_enabled = true; uint32_t ray_seq = 0, ray_gen = 0;
 	uint32_t ray_server_launches = 0, ray_server_rays = 0;
+	// sgp_collide_shapes: which organisation answers (SGP_QUERY_PATH: 0 by the number of queries, 1 a wave per query, 2 candidate pairs), and what the last call
+	// needed per query -- the first guess of the next call's list and output capacities (a guess only: a call that overflows them grows them and runs again)
+	int query_path = 0; uint32_t sq_wave_max_n = 32; float sq_pairs_per_query = 2.0f, sq_out_per_query = 4.0f; uint32_t sq_reruns = 0, sq_last_n = 0, sq_last_out = 0, sq_last_pairs = 0;
 	bool last_step_idle = false;       // the last step was skipped (every body asleep, nothing edited): no vehicle took part in it, whatever its record says
 	bool grid_valid = false;                                   // the broad-phase grid matches the current poses (ray queries reuse it)
 	// static triangle meshes: host-side headers + pools mirrored on the device (grown on demand)

@@ -142,6 +142,94 @@ SGP_API int sgp_collide_capsules(sgp_world* w, const sgp_capsule_query* qs, uint
 	return SGP_OK;
 }
 
+// NarrowPhaseQuery::CollideShape with a sphere, box, capsule or convex hull, batched (kernels and their two organisations: sgp_k_shapequery.hip)
+static const char* shape_query_fault(const sgp_world* w, const sgp_shape_query& q)
+{
+	if (!finite3(q.pos) || !finite4(q.rot) || !finite3(q.movement) || !std::isfinite(q.max_separation)) return "non-finite pose, movement or max_separation";
+	if (!(q.rot[0] * q.rot[0] + q.rot[1] * q.rot[1] + q.rot[2] * q.rot[2] + q.rot[3] * q.rot[3] > 0.0f)) return "zero rotation quaternion";
+	if (q.max_separation < 0.0f) return "negative max_separation";
+	if (!finite4(q.shape)) return "non-finite shape";
+	switch (q.shape_type) {
+	case SGP_SHAPE_SPHERE: return q.shape[0] > 0.0f ? nullptr : "non-positive sphere radius";
+	case SGP_SHAPE_BOX: return (q.shape[0] > 0.0f && q.shape[1] > 0.0f && q.shape[2] > 0.0f) ? nullptr : "non-positive box half extent";
+	case SGP_SHAPE_CAPSULE: return (q.shape[0] > 0.0f && q.shape[1] >= 0.0f) ? nullptr : "non-positive capsule size";
+	case SGP_SHAPE_HULL: {
+		const float h = q.shape[0];
+		if (!(h >= 1.0f) || h != floorf(h) || h >= (float)w->hulls.size() || w->hulls[(size_t)h].nv == 0) return "no such hull";
+		return nullptr; }
+	case SGP_SHAPE_MESH: return "a mesh cannot be a query shape";
+	default: return "unknown shape type";
+	}
+}
+
+SGP_API int sgp_collide_shapes(sgp_world* w, const sgp_shape_query* qs, uint32_t n, sgp_query_contact* out, uint32_t cap, uint32_t* n_out)
+{
+	if (!w || (!qs && n) || (!out && cap) || !n_out) return fail(SGP_ERR_INVALID, "sgp_collide_shapes: NULL");
+	for (uint32_t k = 0; k < n; ++k) if (const char* what = shape_query_fault(w, qs[k])) {      // (before anything is launched: a call is answered whole or not at all)
+		char msg[160]; snprintf(msg, sizeof(msg), "sgp_collide_shapes: query %u: %s", k, what);
+		return fail(SGP_ERR_INVALID, msg);
+	}
+	hipSetDevice(w->device);
+	{ int r = flush_cmds(w); if (r != SGP_OK) return r; }
+	*n_out = 0;
+	if (!n) return SGP_OK;
+	ensure_query_grid(w);
+	const bool by_wave = w->query_path == 1 || (w->query_path == 0 && n <= w->sq_wave_max_n);
+	// Capacities: a first guess from what the last call needed per query.  The kernels count everything they find, also what did not fit; a call that overflowed
+	// a list or the output runs again with room for what was counted (a list that overflowed hid some of the output: that run may be followed by one more).
+	const size_t qb = (sizeof(sgp_shape_query) * n + 15) & ~size_t(15);
+	uint64_t ocap = std::max<uint64_t>(64, (uint64_t)((double)w->sq_out_per_query * n) + 1), pcap = std::max<uint64_t>(64, (uint64_t)((double)w->sq_pairs_per_query * n) + 1);
+	if (n == w->sq_last_n) { ocap = std::max<uint64_t>(ocap, w->sq_last_out + w->sq_last_out / 4); pcap = std::max<uint64_t>(pcap, w->sq_last_pairs + w->sq_last_pairs / 4); }      // (the same batch again, as every frame: what it needed last time)
+	uint32_t ctr[4] = { 0, 0, 0, 0 };
+	size_t out_off = 0;
+	for (int attempt = 0;; ++attempt) {
+		if (attempt == 6) return fail(SGP_ERR_CAPACITY, "sgp_collide_shapes: the answer kept outgrowing its buffers");      // (cannot happen while the world stands still: the counts are exact)
+		if (ocap > 0x7FFFFFFFull || pcap > 0x7FFFFFFFull) return fail(SGP_ERR_CAPACITY, "sgp_collide_shapes: more than 2^31 contacts or candidate pairs");
+		out_off = qb + 16;
+		const size_t lists_off = out_off + sizeof(sgp_query_contact) * (size_t)ocap;
+		{ int r = ensure_stage(w, lists_off + 3 * sizeof(uint2) * (size_t)pcap); if (r != SGP_OK) return r; }
+		memcpy(w->stage_host, qs, sizeof(sgp_shape_query) * n);
+		HIP_TRY(hipMemcpyAsync(w->stage_dev, w->stage_host, sizeof(sgp_shape_query) * n, hipMemcpyHostToDevice, w->stream));
+		char* dev = (char*)w->stage_dev;
+		SqBufs b;
+		b.qs = (const sgp_shape_query*)dev; b.n = n;
+		b.ctr = (uint32_t*)(dev + qb);
+		b.out = (sgp_query_contact*)(dev + out_off); b.cap = (uint32_t)ocap;
+		b.prim = (uint2*)(dev + lists_off); b.hull = b.prim + pcap; b.mesh = b.hull + pcap; b.pcap = (uint32_t)pcap;
+		HIP_TRY(hipMemsetAsync(b.ctr, 0, 16, w->stream));
+		if (by_wave) launch_shape_queries_wave(w->dv, b, w->stream); else launch_shape_queries_pairs(w->dv, b, w->stream);
+		HIP_TRY(hipMemcpyAsync((char*)w->stage_host + qb, b.ctr, 16, hipMemcpyDeviceToHost, w->stream));
+		HIP_TRY(hipStreamSynchronize(w->stream));
+		memcpy(ctr, (char*)w->stage_host + qb, 16);
+		const uint32_t most = std::max(ctr[SQ_N_PRIM], std::max(ctr[SQ_N_HULL], ctr[SQ_N_MESH]));
+		if (ctr[SQ_N_OUT] <= ocap && most <= pcap) break;
+		w->sq_reruns++;
+		if (most > pcap) { ocap = std::max<uint64_t>(ocap, (uint64_t)ctr[SQ_N_OUT] * 2u); pcap = most; }
+		else ocap = ctr[SQ_N_OUT];
+	}
+	const uint32_t cnt = ctr[SQ_N_OUT];
+	{
+		const uint32_t most = std::max(ctr[SQ_N_PRIM], std::max(ctr[SQ_N_HULL], ctr[SQ_N_MESH]));
+		// (per query at most 8: one huge volume must not size the buffers of the next call's thousands of small ones)
+		w->sq_out_per_query = std::min(8.0f, 1.25f * (float)cnt / (float)n + 1.0f); w->sq_pairs_per_query = std::min(8.0f, 1.25f * (float)most / (float)n + 1.0f);
+		w->sq_last_n = n; w->sq_last_out = cnt; w->sq_last_pairs = most;
+	}
+	sgp_query_contact* h = (sgp_query_contact*)((char*)w->stage_host + out_off);
+	if (cnt) {
+		HIP_TRY(hipMemcpyAsync(h, (char*)w->stage_dev + out_off, sizeof(sgp_query_contact) * (size_t)cnt, hipMemcpyDeviceToHost, w->stream));
+		HIP_TRY(hipStreamSynchronize(w->stream));
+	}
+	std::sort(h, h + cnt, [](const sgp_query_contact& a, const sgp_query_contact& b) {
+		if (a.query != b.query) return a.query < b.query;
+		if (a.body != b.body) return a.body < b.body;
+		return a.sub_shape < b.sub_shape; });         // (the kernels leave the contact's point index in this field)
+	const uint32_t m = std::min(cnt, cap);      // the FIRST cap records of the whole sorted answer
+	for (uint32_t i = 0; i < m; ++i) { h[i].userdata = w->hb[h[i].body].userdata; h[i].body = compound_id_of(w, h[i].body, &h[i].sub_shape); }
+	if (m) memcpy(out, h, sizeof(sgp_query_contact) * m);
+	*n_out = cnt;
+	return SGP_OK;
+}
+
 SGP_API int sgp_spherecast(sgp_world* w, const sgp_ray* rays, const float* radii, uint32_t n, sgp_hit* hits)
 {
 	if (!w || (n && (!rays || !radii || !hits))) return fail(SGP_ERR_INVALID, "sgp_spherecast: NULL");

@@ -850,6 +850,53 @@ void PhysicsWorld::traceRays(const std::vector<RayQuery>& rays, std::vector<RayT
 		r.hit_mat_index = hs[k].material;
 	}
 }
+void PhysicsWorld::collideShapes(const std::vector<ShapeQuery>& queries, std::vector<ShapeContact>& contacts_out) const
+{
+	contacts_out.clear();
+	if (queries.empty()) return;
+	std::vector<sgp_shape_query> qs(queries.size());
+	memset(qs.data(), 0, sizeof(sgp_shape_query) * qs.size());
+	for (size_t k = 0; k < queries.size(); ++k) {
+		const ShapeQuery& q = queries[k]; sgp_shape_query& s = qs[k];
+		for (int i = 0; i < 3; ++i) s.pos[i] = q.pos[i];
+		for (int i = 0; i < 4; ++i) s.rot[i] = q.rot.v[i];
+		switch (q.kind) {
+		case ShapeQuery::Kind_Sphere: s.shape_type = SGP_SHAPE_SPHERE; s.shape[0] = q.size.x; break;
+		case ShapeQuery::Kind_Box: s.shape_type = SGP_SHAPE_BOX; s.shape[0] = q.size.x; s.shape[1] = q.size.y; s.shape[2] = q.size.z; break;
+		case ShapeQuery::Kind_Capsule: s.shape_type = SGP_SHAPE_CAPSULE; s.shape[0] = q.size.x; s.shape[1] = q.size.y; break;
+		default: s.shape_type = SGP_SHAPE_HULL; s.shape[0] = (float)q.hull_id; break;
+		}
+		s.max_separation = q.max_separation; s.ignore_id = q.ignore_body_id.GetIndex(); s.layer_mask = q.layer_mask;
+		s.flags = q.deepest_only ? SGP_QUERY_DEEPEST_ONLY : 0u;
+	}
+	// (the whole answer: a first call sized by a guess, a second one when it held more)
+	std::vector<sgp_query_contact> recs(std::max<size_t>(256, 8 * queries.size()));
+	uint32_t n = 0;
+	checkSGP(sgp_collide_shapes(world, qs.data(), (uint32_t)qs.size(), recs.data(), (uint32_t)recs.size(), &n), "collideShapes");
+	if (n > recs.size()) { recs.resize(n); checkSGP(sgp_collide_shapes(world, qs.data(), (uint32_t)qs.size(), recs.data(), (uint32_t)recs.size(), &n), "collideShapes"); }
+	contacts_out.reserve(n);
+	for (uint32_t i = 0; i < n && i < recs.size(); ++i) {
+		const sgp_query_contact& c = recs[i];
+		ShapeContact o;
+		o.query = c.query; o.hit_object = (PhysicsObject*)c.userdata;
+		o.point_ws = Vec4f(c.point[0], c.point[1], c.point[2], 1.f); o.normal_ws = Vec4f(c.normal[0], c.normal[1], c.normal[2], 0.f);
+		o.distance = c.distance; o.sub_shape = c.sub_shape; o.is_sensor = c.is_sensor != 0;
+		contacts_out.push_back(o);
+	}
+}
+void PhysicsWorld::getObjectsInBox(const Vec4f& min, const Vec4f& max, uint32 layer_mask, std::vector<PhysicsObject*>& obs_out) const
+{
+	obs_out.clear();
+	std::vector<ShapeQuery> q(1);
+	q[0].kind = ShapeQuery::Kind_Box;
+	q[0].pos = (min + max) * 0.5f; q[0].pos[3] = 1.f;
+	q[0].size = Vec3f(0.5f * (max[0] - min[0]), 0.5f * (max[1] - min[1]), 0.5f * (max[2] - min[2]));
+	q[0].layer_mask = layer_mask; q[0].deepest_only = true;
+	std::vector<ShapeContact> cs;
+	collideShapes(q, cs);
+	// (sorted by object id: the children of a compound follow each other)
+	for (const ShapeContact& c : cs) if (c.hit_object && std::find(obs_out.begin(), obs_out.end(), c.hit_object) == obs_out.end()) obs_out.push_back(c.hit_object);
+}
 bool PhysicsWorld::doesRayHitAnything(const Vec4f& origin, const Vec4f& dir, float max_t) const
 {
 	sgp_ray r; memset(&r, 0, sizeof(r));

@@ -300,6 +300,24 @@ public:
 	struct RayQuery { Vec4f origin, dir; float max_t; JPH::BodyID ignore_body_id; bool collidable_only; };
 	void traceRays(const std::vector<RayQuery>& rays, std::vector<RayTraceResult>& results_out) const;
 
+	// Extension (not in the reference, which never needed NarrowPhaseQuery::CollideShape outside CharacterVirtual): what is inside these volumes?  Any number
+	// of spheres, boxes, capsules and convex hulls in ONE call (sgp_collide_shapes); the contacts come back sorted by (query, object, point).
+	struct ShapeQuery {
+		enum Kind { Kind_Sphere, Kind_Box, Kind_Capsule, Kind_Hull };
+		Kind kind = Kind_Box;
+		Vec4f pos = Vec4f(0, 0, 0, 1); Quatf rot = Quatf::identity();
+		Vec3f size = Vec3f(0.5f);          // sphere: x = radius; box: half extents; capsule: x = radius, y = half height (axis: local z); hull: unused
+		uint32 hull_id = 0;                // Kind_Hull: the id of a hull of this world
+		float max_separation = 0.f;        // report surfaces closer than this; 0 = touching or overlapping only
+		JPH::BodyID ignore_body_id;
+		uint32 layer_mask = 0;             // bit l: objects of Layers:: l answer; 0 = all
+		bool deepest_only = false;         // one contact per (query, object): its deepest point
+	};
+	struct ShapeContact { uint32 query; PhysicsObject* hit_object; Vec4f point_ws, normal_ws; float distance; uint32 sub_shape; bool is_sensor; };      // normal: from the object towards the query shape
+	void collideShapes(const std::vector<ShapeQuery>& queries, std::vector<ShapeContact>& contacts_out) const;
+	// The objects that touch or overlap the axis-aligned box [min, max], each once (a parcel's or a trigger volume's contents).
+	void getObjectsInBox(const Vec4f& min, const Vec4f& max, uint32 layer_mask, std::vector<PhysicsObject*>& obs_out) const;
+
 	// What GUIClient.cpp:6581-6690 does through physics_system->GetBodyInterface(): copy the poses of the activated
 	// objects back into PhysicsObject::pos / rot (one batched device read instead of one Jolt call per object).
 	void readBackActivatedObjectTransforms();

@@ -427,6 +427,15 @@ class CWorld:
         self._check(self._fn("collide_capsules")(self._h, queries.ctypes.data, len(queries), out.ctypes.data, int(cap), C.byref(n)), "collide_capsules")
         return out[:min(n.value, cap)]
 
+    def collide_shapes(self, queries, cap=4096):
+        """sgp_collide_shapes: overlap queries with spheres, boxes, capsules and hulls (array of abi.shape_query_dtype).  Returns (records, n_total):
+        the first min(n_total, cap) records of the whole answer sorted by (query, body, point), and the size of that whole answer."""
+        queries = np.ascontiguousarray(queries, dtype=abi.shape_query_dtype)
+        out = np.zeros(cap, dtype=abi.query_contact_dtype)
+        n = C.c_uint32(0)
+        self._check(self._fn("collide_shapes")(self._h, queries.ctypes.data, len(queries), out.ctypes.data, int(cap), C.byref(n)), "collide_shapes")
+        return out[:min(n.value, cap)], n.value
+
     def spherecast(self, rays, radii):
         rays = np.ascontiguousarray(rays, dtype=abi.ray_dtype)
         radii = np.ascontiguousarray(np.broadcast_to(np.asarray(radii, dtype=np.float32), (len(rays),)), dtype=np.float32)
