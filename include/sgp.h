@@ -364,7 +364,8 @@ int  sgp_world_launch_counts(sgp_world* w, uint32_t* graph_replays_out, uint32_t
 const char* sgp_kernel_class_name(int k);
 /* sizeof() of ABI struct number `which` (order: settings, world_desc, body_desc, body_state, body_event, contact_event,
  * ray, hit, step_stats, step_profile, ghost_record, vehicle_desc, vehicle_input, vehicle_state, hull_info, capsule_query,
- * query_contact, mesh_info, heightfield_desc, checkpoint_info, shape_query) so bindings can verify their layout. */
+ * query_contact, mesh_info, heightfield_desc, checkpoint_info, shape_query, -- 21 is not used and stays -1 --, shape_cast, cast_hit) so
+ * bindings can verify their layout. */
 int  sgp_abi_sizeof(int which);
 /* activated_obs / newly_activated_obs maintenance + listener callbacks (PhysicsWorld.h:194-200). */
 int  sgp_world_drain_events(sgp_world* w, int kind, void* out, uint32_t cap, uint32_t* n_out);
@@ -632,6 +633,51 @@ typedef struct sgp_shape_query {
  * Many small volumes are answered from a list of candidate (query, body) pairs, a thread per pair; a few large ones by a wave per query:
  * the same records either way (SGP_QUERY_PATH=wave|pairs, read at world creation, forces one). */
 int  sgp_collide_shapes(sgp_world* w, const sgp_shape_query* queries, uint32_t n, sgp_query_contact* out, uint32_t cap, uint32_t* n_out);
+
+/* ---- shape casts with any convex shape (JPH::NarrowPhaseQuery::CastShape) ----------------------------
+ * "How far can this volume travel before it touches something?": the hull of an object lowered onto the scene, a kinematic platform moved up
+ * to the first obstacle, the box of a projectile, the character's capsule as a whole.  The shape keeps its rotation and translates from `pos`
+ * along `dir`; every cast reports its closest hit.  On equal t the lower body id wins, then the lower triangle index (the rule of
+ * sgp_spherecast).  Sensors, dead slots, `ignore_id` and masked layers never answer (as for rays and sphere casts).  Bodies of every shape
+ * answer; a compound child reports the compound's id and its child index; mesh and height-field triangles answer on their front side only and
+ * every edge with its own normal (no active-edge treatment).
+ *
+ * The contract of t, with SGP_CAST_TOLERANCE (Jolt's default collision tolerance for casts):
+ *   - at the reported t the shape and the body are separated by at most SGP_CAST_TOLERANCE along `normal`;
+ *   - at no t' < t does the shape overlap a body that passes the filters by more than fp32 rounding;
+ *   - a reported miss means no such overlap anywhere in [0, max_t];
+ *   - the record is a function of the cast and the world alone: not of the batch it came in, its place in the batch, or the order of any atomics.
+ * The sweep is conservative advancement over the library's pairwise separation functions (sgp_k_shapecast.hip); pairs with a rounded shape at
+ * an edge or corner converge geometrically, and a cast that runs into the iteration cap reports the t it got to (never past the true hit) and is
+ * counted (sgp_cast_shapes_counters). */
+#define SGP_CAST_TOLERANCE 1.0e-4f
+typedef struct sgp_shape_cast {
+	float    pos[3], rot[4];    /* pose at t = 0 */
+	int32_t  shape_type;        /* SGP_SHAPE_SPHERE | BOX | CAPSULE | HULL; shape[] as in sgp_shape_query */
+	float    shape[4];
+	float    dir[3];            /* unit, as in sgp_ray */
+	float    max_t;             /* >= 0 */
+	uint32_t ignore_id;
+	uint32_t layer_mask;        /* as in sgp_shape_query; 0 = all four */
+	uint32_t flags;             /* 0; reserved */
+} sgp_shape_cast;
+typedef struct sgp_cast_hit {
+	uint32_t id;                /* SGP_INVALID_ID: nothing within max_t */
+	float    t;                 /* distance travelled until first touch; 0 when the shape starts in touch or overlapping */
+	float    normal[3];         /* from the body towards the shape, at the touch */
+	float    point[3];          /* on the body */
+	float    penetration;       /* > 0 only for t == 0 hits that start overlapping */
+	uint32_t sub_shape;         /* compound child index, as in sgp_query_contact */
+	uint32_t triangle, material;/* mesh / height-field hits, as in sgp_hit; SGP_INVALID_ID / 0 otherwise */
+	uint64_t userdata;
+} sgp_cast_hit;
+/* SGP_ERR_INVALID, with nothing launched and nothing written and the message naming the cast, for what sgp_collide_shapes rejects (unknown
+ * hull, SGP_SHAPE_MESH or an unknown type, a non-finite pose, a non-positive size), a `dir` that is not finite or not unit within 1e-3, and a
+ * negative or non-finite max_t.  n == 0 is SGP_OK. */
+int  sgp_cast_shapes(sgp_world* w, const sgp_shape_cast* casts, uint32_t n, sgp_cast_hit* hits_out);
+/* counters_out[0]: (cast, body or triangle) pairs of every call so far that ran into the iteration cap; [1]: runs that were repeated because a
+ * candidate list was too small for what the kernels found. */
+int  sgp_cast_shapes_counters(sgp_world* w, uint32_t counters_out[2]);
 
 /* ---- multi-GPU tiles: ghost bodies are ordinary kinematic-like bodies owned elsewhere ---- */
 /* Pack the ghost record of every owned body whose AABB, inflated by `margin`, crosses outside [lo,hi). */

@@ -214,6 +214,21 @@ class ShapeQuery(C.Structure):
                 ("ignore_id", u32), ("layer_mask", u32), ("flags", u32), ("movement", f32 * 3), ("active_edges", u32)]
 
 
+CAST_TOLERANCE = 1.0e-4      # SGP_CAST_TOLERANCE
+
+
+class ShapeCast(C.Structure):
+    """sgp_shape_cast: one cast of sgp_cast_shapes (a sphere, box, capsule or convex hull translated from a pose along dir)."""
+    _fields_ = [("pos", f32 * 3), ("rot", f32 * 4), ("shape_type", i32), ("shape", f32 * 4), ("dir", f32 * 3), ("max_t", f32),
+                ("ignore_id", u32), ("layer_mask", u32), ("flags", u32)]
+
+
+class CastHit(C.Structure):
+    """sgp_cast_hit: the closest hit of one cast (id == INVALID_ID: none within max_t)."""
+    _fields_ = [("id", u32), ("t", f32), ("normal", f32 * 3), ("point", f32 * 3), ("penetration", f32), ("sub_shape", u32),
+                ("triangle", u32), ("material", u32), ("userdata", u64)]
+
+
 class CompoundChild(C.Structure):
     _fields_ = [("shape_type", i32), ("shape", f32 * 4), ("pos", f32 * 3), ("rot", f32 * 4)]
 
@@ -240,7 +255,8 @@ ABI_SIZEOF_ORDER = ["sgp_settings", "sgp_world_desc", "sgp_body_desc", "sgp_body
                     "sgp_capsule_query", "sgp_query_contact", "sgp_mesh_info", "sgp_heightfield_desc", "sgp_checkpoint_info"]
 
 # structs appended to sgp_abi_sizeof after ABI_SIZEOF_ORDER was fixed (their indices follow its last one; nothing before them moves)
-ABI_SIZEOF_APPENDED = ["sgp_shape_query"]
+# (index 21 is not used and answers -1 for good: bindings that know 21 structs probe it for the end of the list)
+ABI_SIZEOF_APPENDED = ["sgp_shape_query", None, "sgp_shape_cast", "sgp_cast_hit"]
 ABI_SIZEOF_ALL = ABI_SIZEOF_ORDER + ABI_SIZEOF_APPENDED
 
 STRUCTS = {"sgp_settings": Settings, "sgp_world_desc": WorldDesc, "sgp_body_desc": BodyDesc,
@@ -249,7 +265,8 @@ STRUCTS = {"sgp_settings": Settings, "sgp_world_desc": WorldDesc, "sgp_body_desc
            "sgp_ghost_record": GhostRecord, "sgp_vehicle_desc": VehicleDesc, "sgp_vehicle_input": VehicleInput,
            "sgp_vehicle_state": VehicleState, "sgp_hull_info": HullInfo, "sgp_capsule_query": CapsuleQuery,
            "sgp_query_contact": QueryContact, "sgp_mesh_info": MeshInfo, "sgp_heightfield_desc": HeightfieldDesc,
-           "sgp_checkpoint_info": CheckpointInfo, "sgp_shape_query": ShapeQuery}
+           "sgp_checkpoint_info": CheckpointInfo, "sgp_shape_query": ShapeQuery, "sgp_shape_cast": ShapeCast,
+           "sgp_cast_hit": CastHit}
 
 body_desc_dtype = np.dtype(BodyDesc)
 body_state_dtype = np.dtype(BodyState)
@@ -266,6 +283,8 @@ vehicle_state_dtype = np.dtype(VehicleState)
 capsule_query_dtype = np.dtype(CapsuleQuery)
 query_contact_dtype = np.dtype(QueryContact)
 shape_query_dtype = np.dtype(ShapeQuery)
+shape_cast_dtype = np.dtype(ShapeCast)
+cast_hit_dtype = np.dtype(CastHit)
 compound_child_dtype = np.dtype(CompoundChild)
 migration_dtype = np.dtype(Migration)
 
@@ -332,6 +351,8 @@ PROTOTYPES = {
     "collide_capsules": (C.c_int, [vp, vp, u32, vp, u32, P(u32)]),
     "spherecast": (C.c_int, [vp, vp, vp, u32, vp]),
     "collide_shapes": (C.c_int, [vp, vp, u32, vp, u32, P(u32)]),
+    "cast_shapes": (C.c_int, [vp, vp, u32, vp]),
+    "cast_shapes_counters": (C.c_int, [vp, P(u32)]),
     "world_export_boundary": (C.c_int, [vp, P(f32), P(f32), f32, vp, u32, P(u32)]),
     "world_import_ghosts": (C.c_int, [vp, vp, u32]),
     "tiles_route": (C.c_int, [vp, u32, u32, vp, u32, f32, vp, u32, vp, vp, u32, P(u32)]),

@@ -13,6 +13,7 @@
 //   sgp_k_vehicle.hip      (f)1   k_vehicle_cast / controller, the vehicle rows inside the solver passes (k_solve_colour_veh)
 //   sgp_k_queries.hip      A7     k_raycast, k_collide_capsules, k_spherecast
 //   sgp_k_shapequery.hip   A7     k_sq_wave, k_sq_candidates + k_sq_pairs_prim / k_sq_pairs_hull / k_sq_mesh (sgp_collide_shapes)
+//   sgp_k_shapecast.hip    A7     k_sc_candidates + k_sc_pairs_prim / k_sc_pairs_hull / k_sc_mesh (sgp_cast_shapes)
 //   sgp_k_edits.hip        A5/A6  k_apply_cmds, k_ghost_refresh, read-back
 //   sgp_k_tiles.hip        (e)    tile export / routing, re-tiling histograms
 //   sgp_k_checkpoint.hip          k_ckpt_copy: the segmented copy of sgp_world_checkpoint / sgp_world_rollback
@@ -468,6 +469,19 @@ struct SqBufs {
 };
 void launch_shape_queries_wave(const DV& d, const SqBufs& b, hipStream_t s);       // a wave per query (mesh bodies: through the mesh list, a wave per pair)
 void launch_shape_queries_pairs(const DV& d, const SqBufs& b, hipStream_t s);      // candidate pairs by a thread per query, then a thread per pair (mesh bodies: a wave per pair)
+// sgp_cast_shapes (sgp_k_shapecast.hip): the buffers of one call, in the world's stage buffer.  A wave per cast deals the bodies under the swept bounds to three
+// lists of (cast, body) pairs; every pair that hits appends ONE record to `out` -- its own first touch, for a mesh the closest triangle's -- with the cast's index in
+// sgp_cast_hit::userdata, and the host keeps per cast the least by (t, id, triangle): a record is a function of its pair alone, the order of arrival never enters.
+// `out` has room for a record per pair (3 pcap); a list that is too small is counted past its capacity and the host runs the call again with room for the count.
+// ctr: SC_N_OUT records, SC_N_PRIM / HULL / MESH pairs found, SC_N_CAPPED pairs that ran into the iteration cap, SC_N_DROPPED mesh trees too deep for the walk's stack.
+enum { SC_N_OUT = 0, SC_N_PRIM = 1, SC_N_HULL = 2, SC_N_MESH = 3, SC_N_CAPPED = 4, SC_N_DROPPED = 5, SC_N_CTR = 8 };
+struct ScBufs {
+	const sgp_shape_cast* cs; uint32_t n;
+	sgp_cast_hit* out;
+	uint32_t* ctr;
+	uint2* prim; uint2* hull; uint2* mesh; uint32_t pcap;      // as SqBufs: sphere / box / capsule pairs, pairs with a convex hull on either side, pairs whose body is a mesh or a height field
+};
+void launch_shape_casts(const DV& d, const ScBufs& b, hipStream_t s);
 void launch_export_boundary(const DV& d, uint32_t nb, float3 lo, float3 hi, float margin, sgp_ghost_record* out, uint32_t cap, uint32_t* count, hipStream_t s);
 
 // ---- tile exchange with the routing on the device (sgp_tiles_*) ----------------------------------------------------

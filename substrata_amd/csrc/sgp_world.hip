@@ -79,6 +79,7 @@ SGP_API int sgp_abi_sizeof(int which)
 	case 11: return (int)sizeof(sgp_vehicle_desc); case 12: return (int)sizeof(sgp_vehicle_input); case 13: return (int)sizeof(sgp_vehicle_state);
 	case 14: return (int)sizeof(sgp_hull_info); case 15: return (int)sizeof(sgp_capsule_query); case 16: return (int)sizeof(sgp_query_contact); case 17: return (int)sizeof(sgp_mesh_info);
 	case 18: return (int)sizeof(sgp_heightfield_desc); case 19: return (int)sizeof(sgp_checkpoint_info); case 20: return (int)sizeof(sgp_shape_query);
+	case 22: return (int)sizeof(sgp_shape_cast); case 23: return (int)sizeof(sgp_cast_hit);      // (21 stays -1: bindings that know 21 structs probe it for the end of the list)
 	default: return -1;
 	}
 }

@@ -146,6 +146,8 @@ struct sgp_world {
 	// sgp_collide_shapes: which organisation answers (SGP_QUERY_PATH: 0 by the number of queries, 1 a wave per query, 2 candidate pairs), and what the last call
 	// needed per query -- the first guess of the next call's list and output capacities (a guess only: a call that overflows them grows them and runs again)
 	int query_path = 0; uint32_t sq_wave_max_n = 32; float sq_pairs_per_query = 2.0f, sq_out_per_query = 4.0f; uint32_t sq_reruns = 0, sq_last_n = 0, sq_last_out = 0, sq_last_pairs = 0;
+	// sgp_cast_shapes: what the last call needed per cast (the first guess of the next call's list capacity), runs repeated because a list was too small, pairs that ran into the iteration cap
+	float sc_pairs_per_cast = 2.0f; uint32_t sc_reruns = 0, sc_capped = 0;
 	bool last_step_idle = false;       // the last step was skipped (every body asleep, nothing edited): no vehicle took part in it, whatever its record says
 	bool grid_valid = false;                                   // the broad-phase grid matches the current poses (ray queries reuse it)
 	// static triangle meshes: host-side headers + pools mirrored on the device (grown on demand)

@@ -230,6 +230,93 @@ SGP_API int sgp_collide_shapes(sgp_world* w, const sgp_shape_query* qs, uint32_t
 	return SGP_OK;
 }
 
+// NarrowPhaseQuery::CastShape with a sphere, box, capsule or convex hull, batched (kernels: sgp_k_shapecast.hip)
+static const char* shape_cast_fault(const sgp_world* w, const sgp_shape_cast& c)
+{
+	sgp_shape_query q;
+	memset(&q, 0, sizeof(q));
+	memcpy(q.pos, c.pos, sizeof(q.pos)); memcpy(q.rot, c.rot, sizeof(q.rot)); memcpy(q.shape, c.shape, sizeof(q.shape)); q.shape_type = c.shape_type;
+	if (const char* what = shape_query_fault(w, q)) return what;
+	if (!finite3(c.dir)) return "non-finite dir";
+	if (fabsf(sqrtf(c.dir[0] * c.dir[0] + c.dir[1] * c.dir[1] + c.dir[2] * c.dir[2]) - 1.0f) > 1.0e-3f) return "dir is not a unit vector";
+	if (!std::isfinite(c.max_t) || c.max_t < 0.0f) return "negative or non-finite max_t";
+	return nullptr;
+}
+
+SGP_API int sgp_cast_shapes(sgp_world* w, const sgp_shape_cast* cs, uint32_t n, sgp_cast_hit* hits)
+{
+	if (!w || (n && (!cs || !hits))) return fail(SGP_ERR_INVALID, "sgp_cast_shapes: NULL");
+	for (uint32_t k = 0; k < n; ++k) if (const char* what = shape_cast_fault(w, cs[k])) {      // (before anything is launched: a call is answered whole or not at all)
+		char msg[160]; snprintf(msg, sizeof(msg), "sgp_cast_shapes: cast %u: %s", k, what);
+		return fail(SGP_ERR_INVALID, msg);
+	}
+	hipSetDevice(w->device);
+	{ int r = flush_cmds(w); if (r != SGP_OK) return r; }
+	if (!n) return SGP_OK;
+	ensure_query_grid(w);
+	// Capacity of the three candidate lists: a first guess from what the last call needed per cast.  The kernels count every candidate they find, also what did not
+	// fit; a call that overflowed a list runs again with room for what was counted (the counts are exact while the world stands still: one more run at most).
+	const size_t cb = (sizeof(sgp_shape_cast) * n + 15) & ~size_t(15);
+	uint64_t pcap = std::max<uint64_t>(64, (uint64_t)((double)w->sc_pairs_per_cast * n) + 1);
+	uint32_t ctr[SC_N_CTR];
+	size_t out_off = 0;
+	for (int attempt = 0;; ++attempt) {
+		if (attempt == 4) return fail(SGP_ERR_CAPACITY, "sgp_cast_shapes: the candidate lists kept outgrowing their buffers");
+		if (pcap > 0x3FFFFFFFull) return fail(SGP_ERR_CAPACITY, "sgp_cast_shapes: more than 2^30 candidate pairs");
+		out_off = cb + sizeof(uint32_t) * SC_N_CTR;
+		const size_t lists_off = out_off + sizeof(sgp_cast_hit) * 3 * (size_t)pcap;
+		{ int r = ensure_stage(w, lists_off + 3 * sizeof(uint2) * (size_t)pcap); if (r != SGP_OK) return r; }
+		memcpy(w->stage_host, cs, sizeof(sgp_shape_cast) * n);
+		HIP_TRY(hipMemcpyAsync(w->stage_dev, w->stage_host, sizeof(sgp_shape_cast) * n, hipMemcpyHostToDevice, w->stream));
+		char* dev = (char*)w->stage_dev;
+		ScBufs b;
+		b.cs = (const sgp_shape_cast*)dev; b.n = n;
+		b.ctr = (uint32_t*)(dev + cb);
+		b.out = (sgp_cast_hit*)(dev + out_off);
+		b.prim = (uint2*)(dev + lists_off); b.hull = b.prim + pcap; b.mesh = b.hull + pcap; b.pcap = (uint32_t)pcap;
+		HIP_TRY(hipMemsetAsync(b.ctr, 0, sizeof(uint32_t) * SC_N_CTR, w->stream));
+		launch_shape_casts(w->dv, b, w->stream);
+		HIP_TRY(hipMemcpyAsync((char*)w->stage_host + cb, b.ctr, sizeof(uint32_t) * SC_N_CTR, hipMemcpyDeviceToHost, w->stream));
+		HIP_TRY(hipStreamSynchronize(w->stream));
+		memcpy(ctr, (char*)w->stage_host + cb, sizeof(ctr));
+		const uint32_t most = std::max(ctr[SC_N_PRIM], std::max(ctr[SC_N_HULL], ctr[SC_N_MESH]));
+		if (most <= pcap) break;
+		w->sc_reruns++;
+		pcap = most;
+	}
+	if (ctr[SC_N_DROPPED]) return fail(SGP_ERR_CAPACITY, "sgp_cast_shapes: a mesh tree is deeper than the walk's stack");
+	w->sc_capped += ctr[SC_N_CAPPED];
+	w->sc_pairs_per_cast = std::min(16.0f, 1.25f * (float)std::max(ctr[SC_N_PRIM], std::max(ctr[SC_N_HULL], ctr[SC_N_MESH])) / (float)n + 1.0f);
+	const uint32_t cnt = ctr[SC_N_OUT];
+	const sgp_cast_hit* h = (const sgp_cast_hit*)((char*)w->stage_host + out_off);
+	if (cnt) {
+		HIP_TRY(hipMemcpyAsync((char*)w->stage_host + out_off, (char*)w->stage_dev + out_off, sizeof(sgp_cast_hit) * (size_t)cnt, hipMemcpyDeviceToHost, w->stream));
+		HIP_TRY(hipStreamSynchronize(w->stream));
+	}
+	// per cast the least record by (t, id, triangle): whatever order the records arrived in
+	for (uint32_t k = 0; k < n; ++k) { memset(&hits[k], 0, sizeof(sgp_cast_hit)); hits[k].id = SGP_INVALID_ID; hits[k].triangle = SGP_INVALID_ID; }
+	for (uint32_t i = 0; i < cnt; ++i) {
+		const sgp_cast_hit& r = h[i];
+		sgp_cast_hit& o = hits[(uint32_t)r.userdata];
+		if (o.id == SGP_INVALID_ID || r.t < o.t || (r.t == o.t && (r.id < o.id || (r.id == o.id && r.triangle < o.triangle)))) o = r;
+	}
+	for (uint32_t k = 0; k < n; ++k) {
+		sgp_cast_hit& o = hits[k];
+		o.userdata = 0;
+		if (o.id == SGP_INVALID_ID) continue;
+		o.userdata = w->hb[o.id].userdata;
+		o.id = compound_id_of(w, o.id, &o.sub_shape);
+	}
+	return SGP_OK;
+}
+
+SGP_API int sgp_cast_shapes_counters(sgp_world* w, uint32_t counters_out[2])
+{
+	if (!w || !counters_out) return fail(SGP_ERR_INVALID, "sgp_cast_shapes_counters: NULL");
+	counters_out[0] = w->sc_capped; counters_out[1] = w->sc_reruns;
+	return SGP_OK;
+}
+
 SGP_API int sgp_spherecast(sgp_world* w, const sgp_ray* rays, const float* radii, uint32_t n, sgp_hit* hits)
 {
 	if (!w || (n && (!rays || !radii || !hits))) return fail(SGP_ERR_INVALID, "sgp_spherecast: NULL");

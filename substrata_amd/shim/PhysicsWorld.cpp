@@ -897,6 +897,36 @@ void PhysicsWorld::getObjectsInBox(const Vec4f& min, const Vec4f& max, uint32 la
 	// (sorted by object id: the children of a compound follow each other)
 	for (const ShapeContact& c : cs) if (c.hit_object && std::find(obs_out.begin(), obs_out.end(), c.hit_object) == obs_out.end()) obs_out.push_back(c.hit_object);
 }
+void PhysicsWorld::castShapes(const std::vector<ShapeCast>& casts, std::vector<ShapeCastResult>& results_out) const
+{
+	results_out.clear();
+	if (casts.empty()) return;
+	std::vector<sgp_shape_cast> cs(casts.size());
+	memset(cs.data(), 0, sizeof(sgp_shape_cast) * cs.size());
+	for (size_t k = 0; k < casts.size(); ++k) {
+		const ShapeCast& q = casts[k]; sgp_shape_cast& s = cs[k];
+		for (int i = 0; i < 3; ++i) { s.pos[i] = q.pos[i]; s.dir[i] = q.dir[i]; }
+		for (int i = 0; i < 4; ++i) s.rot[i] = q.rot.v[i];
+		switch (q.kind) {
+		case ShapeQuery::Kind_Sphere: s.shape_type = SGP_SHAPE_SPHERE; s.shape[0] = q.size.x; break;
+		case ShapeQuery::Kind_Box: s.shape_type = SGP_SHAPE_BOX; s.shape[0] = q.size.x; s.shape[1] = q.size.y; s.shape[2] = q.size.z; break;
+		case ShapeQuery::Kind_Capsule: s.shape_type = SGP_SHAPE_CAPSULE; s.shape[0] = q.size.x; s.shape[1] = q.size.y; break;
+		default: s.shape_type = SGP_SHAPE_HULL; s.shape[0] = (float)q.hull_id; break;
+		}
+		s.max_t = q.max_t; s.ignore_id = q.ignore_body_id.GetIndex(); s.layer_mask = q.collidable_only ? 0x3u : 0u;
+	}
+	std::vector<sgp_cast_hit> hs(casts.size());
+	checkSGP(sgp_cast_shapes(world, cs.data(), (uint32_t)cs.size(), hs.data()), "castShapes");
+	results_out.resize(casts.size());
+	for (size_t k = 0; k < casts.size(); ++k) {
+		const sgp_cast_hit& h = hs[k];
+		ShapeCastResult& r = results_out[k];
+		r.hit_object = (h.id != SGP_INVALID_ID) ? (PhysicsObject*)h.userdata : nullptr;
+		r.hit_t = h.t;
+		r.hit_normal_ws = Vec4f(h.normal[0], h.normal[1], h.normal[2], 0.f); r.hit_pos_ws = Vec4f(h.point[0], h.point[1], h.point[2], 1.f);
+		r.penetration = h.penetration; r.sub_shape = h.sub_shape; r.hit_mat_index = h.material;
+	}
+}
 bool PhysicsWorld::doesRayHitAnything(const Vec4f& origin, const Vec4f& dir, float max_t) const
 {
 	sgp_ray r; memset(&r, 0, sizeof(r));

@@ -318,6 +318,22 @@ public:
 	// The objects that touch or overlap the axis-aligned box [min, max], each once (a parcel's or a trigger volume's contents).
 	void getObjectsInBox(const Vec4f& min, const Vec4f& max, uint32 layer_mask, std::vector<PhysicsObject*>& obs_out) const;
 
+	// Extension (NarrowPhaseQuery::CastShape, which the reference reaches only through CharacterVirtual): how far can these volumes travel before they touch
+	// something?  Any number of spheres, boxes, capsules and convex hulls in ONE call (sgp_cast_shapes): the hull of an object lowered onto the scene, a platform
+	// moved up to the first obstacle, a projectile's box.  One result per cast: its first touch (hit_object = nullptr: nothing within max_t).
+	struct ShapeCast {
+		ShapeQuery::Kind kind = ShapeQuery::Kind_Box;
+		Vec4f pos = Vec4f(0, 0, 0, 1); Quatf rot = Quatf::identity();      // the pose at t = 0; the rotation is kept
+		Vec3f size = Vec3f(0.5f);          // as ShapeQuery::size
+		uint32 hull_id = 0;                // Kind_Hull: the id of a hull of this world
+		Vec4f dir = Vec4f(0, 0, -1, 0);    // unit
+		float max_t = 0.f;
+		JPH::BodyID ignore_body_id;
+		bool collidable_only = false;      // as RayQuery::collidable_only
+	};
+	struct ShapeCastResult { PhysicsObject* hit_object; float hit_t; Vec4f hit_normal_ws, hit_pos_ws; float penetration; uint32 sub_shape, hit_mat_index; };      // normal: from the object towards the shape; pos: on the object
+	void castShapes(const std::vector<ShapeCast>& casts, std::vector<ShapeCastResult>& results_out) const;
+
 	// What GUIClient.cpp:6581-6690 does through physics_system->GetBodyInterface(): copy the poses of the activated
 	// objects back into PhysicsObject::pos / rot (one batched device read instead of one Jolt call per object).
 	void readBackActivatedObjectTransforms();

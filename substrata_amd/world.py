@@ -436,6 +436,19 @@ class CWorld:
         self._check(self._fn("collide_shapes")(self._h, queries.ctypes.data, len(queries), out.ctypes.data, int(cap), C.byref(n)), "collide_shapes")
         return out[:min(n.value, cap)], n.value
 
+    def cast_shapes(self, casts):
+        """sgp_cast_shapes: the closest hit of every cast (array of abi.shape_cast_dtype) as an array of abi.cast_hit_dtype; id == abi.INVALID_ID: a miss."""
+        casts = np.ascontiguousarray(casts, dtype=abi.shape_cast_dtype)
+        hits = np.zeros(len(casts), dtype=abi.cast_hit_dtype)
+        self._check(self._fn("cast_shapes")(self._h, casts.ctypes.data, len(casts), hits.ctypes.data), "cast_shapes")
+        return hits
+
+    def cast_shapes_counters(self):
+        """(pairs of all sgp_cast_shapes calls so far that ran into the iteration cap, runs repeated because a candidate list was too small)"""
+        out = (C.c_uint32 * 2)()
+        self._check(self._fn("cast_shapes_counters")(self._h, out), "cast_shapes_counters")
+        return int(out[0]), int(out[1])
+
     def spherecast(self, rays, radii):
         rays = np.ascontiguousarray(rays, dtype=abi.ray_dtype)
         radii = np.ascontiguousarray(np.broadcast_to(np.asarray(radii, dtype=np.float32), (len(rays),)), dtype=np.float32)
