@@ -364,8 +364,8 @@ int  sgp_world_launch_counts(sgp_world* w, uint32_t* graph_replays_out, uint32_t
 const char* sgp_kernel_class_name(int k);
 /* sizeof() of ABI struct number `which` (order: settings, world_desc, body_desc, body_state, body_event, contact_event,
  * ray, hit, step_stats, step_profile, ghost_record, vehicle_desc, vehicle_input, vehicle_state, hull_info, capsule_query,
- * query_contact, mesh_info, heightfield_desc, checkpoint_info, shape_query, -- 21 is not used and stays -1 --, shape_cast, cast_hit) so
- * bindings can verify their layout. */
+ * query_contact, mesh_info, heightfield_desc, checkpoint_info, shape_query, -- 21 is not used and stays -1 --, shape_cast, cast_hit,
+ * -- 24 is not used and stays -1 --, character_desc, character_input, character_state, character_contact) so bindings can verify their layout. */
 int  sgp_abi_sizeof(int which);
 /* activated_obs / newly_activated_obs maintenance + listener callbacks (PhysicsWorld.h:194-200). */
 int  sgp_world_drain_events(sgp_world* w, int kind, void* out, uint32_t cap, uint32_t* n_out);
@@ -607,6 +607,88 @@ typedef struct sgp_query_contact {
 int  sgp_collide_capsules(sgp_world* w, const sgp_capsule_query* queries, uint32_t n, sgp_query_contact* out, uint32_t cap, uint32_t* n_out);
 /* Sphere casts (rays with thickness): hit.t = distance travelled by the centre until first touch, hit.normal at the touch point. */
 int  sgp_spherecast(sgp_world* w, const sgp_ray* rays, const float* radii, uint32_t n, sgp_hit* hits_out);
+
+/* ---- batched virtual characters (JPH::CharacterVirtual for many avatars at once) ---------------------
+ * A batch of kinematic characters that belongs to one world.  sgp_characters_update runs CharacterVirtual::Update / ExtendedUpdate for
+ * every character of the batch in ONE launch on the world's stream -- contacts, plane constraints, sliding, the swept tests, ground
+ * state, stick-to-floor and stairs, all on the device, with the character state living there -- and returns without waiting for it.
+ * The algorithm, its constants and its fp32 expressions are those of shim/Jolt/JoltCharacterLite.h (the host class that walks one
+ * character at a time through sgp_collide_capsules / sgp_spherecast): a character of a batch moves as that class moves it.
+ * The capsule's axis is the world z axis (identity rotation, as PlayerPhysics uses it).  Characters do not collide with each other.
+ * A batch holds no state that a world checkpoint captures (docs/GAPS.md). */
+typedef struct sgp_characters sgp_characters;
+#define SGP_CHAR_EXTENDED  1u   /* ExtendedUpdate (stick to floor, stairs); without it the plain Update of PlayerPhysics::updateForInVehicle */
+#define SGP_CHAR_NO_SLIDE  2u   /* PlayerPhysics::OnContactSolve (PlayerPhysics.cpp:536-545): a contact whose velocity is near zero (squared length <= 1e-12)
+                                   and whose normal is not too steep leaves the character with zero velocity                                  */
+#define SGP_CHAR_DISABLED  4u   /* skipped by sgp_characters_update                                                                          */
+/* CharacterBase::EGroundState */
+#define SGP_GROUND_ON_GROUND        0
+#define SGP_GROUND_ON_STEEP_GROUND  1
+#define SGP_GROUND_NOT_SUPPORTED    2
+#define SGP_GROUND_IN_AIR           3
+#define SGP_CHAR_MAX_CONTACTS 64    /* contacts one query of a character keeps (the buffer of JoltCharacterLite.h); more: the overflow bit */
+/* What CharacterVirtualSettings and CharacterVirtual::ExtendedUpdateSettings carry; sgp_default_character_desc fills Jolt's defaults. */
+typedef struct sgp_character_desc {
+	float    radius, half_height;     /* capsule: 0.3, 0.65 (half height of the cylinder part)                        */
+	float    shape_offset[3];         /* from the character position to the capsule centre: (0,0,0)                   */
+	float    up[3];                   /* mUp (0,1,0)                                                                  */
+	float    supporting_plane[4];     /* mSupportingVolume: normal (0,0,1), constant 1e10                             */
+	float    max_slope_angle;         /* 50 degrees, in radians (the library keeps its cosine)                        */
+	float    mass, max_strength;      /* 70, 100                                                                      */
+	float    predictive_contact_distance, character_padding, penetration_recovery_speed, collision_tolerance;   /* 0.1, 0.02, 1, 1e-3 */
+	uint32_t max_collision_iterations, max_constraint_iterations;     /* 5, 15 (at most 16 and 64)                     */
+	float    min_time_remaining;      /* 1e-4                                                                         */
+	float    stick_to_floor_step_down[3];      /* (0,-0.5,0)                                                          */
+	float    walk_stairs_step_up[3];           /* (0,0.4,0)                                                           */
+	float    walk_stairs_min_step_forward, walk_stairs_step_forward_test, walk_stairs_cos_angle_forward_contact;   /* 0.02, 0.15, 0.2588 */
+	float    walk_stairs_step_down_extra[3];   /* (0,0,0)                                                             */
+} sgp_character_desc;
+typedef struct sgp_character_input {
+	float    velocity[3];             /* CharacterVirtual::SetLinearVelocity                                          */
+	uint32_t ignore_id;               /* JPH::IgnoreSingleBodyFilter (PlayerPhysics.cpp:477); SGP_INVALID_ID: none    */
+	uint32_t flags;                   /* SGP_CHAR_*                                                                   */
+} sgp_character_input;
+typedef struct sgp_character_state {
+	float    pos[3];
+	float    lin_vel[3];              /* GetLinearVelocity: as set, less what ExtendedUpdate cancelled towards steep slopes */
+	uint32_t ground_state;            /* SGP_GROUND_*                                                                 */
+	float    ground_normal[3], ground_velocity[3], ground_position[3];
+	uint32_t ground_body;             /* SGP_INVALID_ID: none; a compound's id for its children                       */
+	uint32_t ground_sub_shape;
+	uint32_t overflow;                /* bit 0: a query of the last update met more than SGP_CHAR_MAX_CONTACTS contacts; bit 1: more bodies seen, contact
+	                                     records or pushes than the character's slots hold (the rest was dropped)                                          */
+	uint64_t ground_userdata;
+} sgp_character_state;
+/* CharacterContactListener::OnContactAdded: one record per (body, sub shape) a character newly touches */
+typedef struct sgp_character_contact {
+	uint32_t character, body, sub_shape, reserved_;
+	uint64_t userdata;
+	float    point[3], normal[3];
+} sgp_character_contact;
+void sgp_default_character_desc(sgp_character_desc* out);
+int  sgp_characters_create(sgp_world* w, uint32_t capacity, sgp_characters** out);
+/* After sgp_world_destroy of its world this still frees the batch and returns SGP_OK; every other call on such a batch is SGP_ERR_INVALID. */
+int  sgp_characters_destroy(sgp_characters* cs);
+/* Ids are slots of the batch; a removed slot is reused and carries nothing over.  SGP_ERR_INVALID for a degenerate description (a
+ * non-positive or non-finite size, a zero up vector, iteration limits of 0 or beyond 16 / 64), SGP_ERR_CAPACITY for a full batch. */
+int  sgp_character_add(sgp_characters* cs, const sgp_character_desc* desc, const float pos[3], uint32_t* id_out);
+int  sgp_character_remove(sgp_characters* cs, uint32_t id);
+int  sgp_characters_set_pose(sgp_characters* cs, const uint32_t* ids, const float* pos_xyz, uint32_t n);      /* teleport */
+/* CharacterVirtual::SetShape with another capsule: the standing / sitting switch of PlayerPhysics.cpp:71-79 */
+int  sgp_characters_set_shape(sgp_characters* cs, uint32_t id, float radius, float half_height, const float offset[3]);
+/* Inputs of characters [first, first + n); they stay in force until set again.  A non-finite velocity is SGP_ERR_INVALID. */
+int  sgp_characters_set_inputs(sgp_characters* cs, uint32_t first, uint32_t n, const sgp_character_input* inputs);
+/* Advances every live character that is not disabled by dt: flushes pending body edits, makes the query grid valid (as
+ * sgp_collide_capsules does), uploads changed inputs and enqueues the update on the world's stream.  No wait, no copy to the host.
+ * Dynamic bodies in a character's way are pushed as CharacterVirtual pushes them: a second launch of the same call applies the push
+ * records, waking the bodies on the device, with the effect of sgp_body_activate + sgp_body_add_force_at called in ascending character
+ * order, then in order of occurrence -- the same bits on every run.  The world's next step is never skipped as idle after an update. */
+int  sgp_characters_update(sgp_characters* cs, float dt);
+/* Waits for the updates in flight.  Slots that are not live read as zeros with ground_state = SGP_GROUND_IN_AIR. */
+int  sgp_characters_get_states(sgp_characters* cs, uint32_t first, uint32_t n, sgp_character_state* out);
+/* The contact-added records since the last drain, ascending character, then order of discovery; *n_out = how many were pending
+ * (<= cap are written; all are consumed).  A character holds at most 32 between drains. */
+int  sgp_characters_drain_contacts(sgp_characters* cs, sgp_character_contact* out, uint32_t cap, uint32_t* n_out);
 
 /* ---- overlap queries with any convex shape (JPH::NarrowPhaseQuery::CollideShape) --------------------
  * "What is inside this volume?": a box for a parcel or a trigger volume, a sphere for an explosion or an audio radius, the hull of an

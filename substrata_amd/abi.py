@@ -229,6 +229,38 @@ class CastHit(C.Structure):
                 ("triangle", u32), ("material", u32), ("userdata", u64)]
 
 
+CHAR_EXTENDED, CHAR_NO_SLIDE, CHAR_DISABLED = 1, 2, 4                                   # SGP_CHAR_*
+GROUND_ON_GROUND, GROUND_ON_STEEP_GROUND, GROUND_NOT_SUPPORTED, GROUND_IN_AIR = 0, 1, 2, 3    # SGP_GROUND_* (CharacterBase::EGroundState)
+CHAR_MAX_CONTACTS = 64
+
+
+class CharacterDesc(C.Structure):
+    """sgp_character_desc: CharacterVirtualSettings + ExtendedUpdateSettings of one character of a batch."""
+    _fields_ = [("radius", f32), ("half_height", f32), ("shape_offset", f32 * 3), ("up", f32 * 3), ("supporting_plane", f32 * 4),
+                ("max_slope_angle", f32), ("mass", f32), ("max_strength", f32), ("predictive_contact_distance", f32),
+                ("character_padding", f32), ("penetration_recovery_speed", f32), ("collision_tolerance", f32),
+                ("max_collision_iterations", u32), ("max_constraint_iterations", u32), ("min_time_remaining", f32),
+                ("stick_to_floor_step_down", f32 * 3), ("walk_stairs_step_up", f32 * 3), ("walk_stairs_min_step_forward", f32),
+                ("walk_stairs_step_forward_test", f32), ("walk_stairs_cos_angle_forward_contact", f32),
+                ("walk_stairs_step_down_extra", f32 * 3)]
+
+
+class CharacterInput(C.Structure):
+    _fields_ = [("velocity", f32 * 3), ("ignore_id", u32), ("flags", u32)]
+
+
+class CharacterState(C.Structure):
+    _fields_ = [("pos", f32 * 3), ("lin_vel", f32 * 3), ("ground_state", u32), ("ground_normal", f32 * 3),
+                ("ground_velocity", f32 * 3), ("ground_position", f32 * 3), ("ground_body", u32), ("ground_sub_shape", u32),
+                ("overflow", u32), ("ground_userdata", u64)]
+
+
+class CharacterContact(C.Structure):
+    """sgp_character_contact: CharacterContactListener::OnContactAdded of one character of a batch."""
+    _fields_ = [("character", u32), ("body", u32), ("sub_shape", u32), ("reserved_", u32), ("userdata", u64),
+                ("point", f32 * 3), ("normal", f32 * 3)]
+
+
 class CompoundChild(C.Structure):
     _fields_ = [("shape_type", i32), ("shape", f32 * 4), ("pos", f32 * 3), ("rot", f32 * 4)]
 
@@ -256,7 +288,9 @@ ABI_SIZEOF_ORDER = ["sgp_settings", "sgp_world_desc", "sgp_body_desc", "sgp_body
 
 # structs appended to sgp_abi_sizeof after ABI_SIZEOF_ORDER was fixed (their indices follow its last one; nothing before them moves)
 # (index 21 is not used and answers -1 for good: bindings that know 21 structs probe it for the end of the list)
-ABI_SIZEOF_APPENDED = ["sgp_shape_query", None, "sgp_shape_cast", "sgp_cast_hit"]
+# (likewise 24, which the bindings that know 24 structs probe)
+ABI_SIZEOF_APPENDED = ["sgp_shape_query", None, "sgp_shape_cast", "sgp_cast_hit",
+                       None, "sgp_character_desc", "sgp_character_input", "sgp_character_state", "sgp_character_contact"]
 ABI_SIZEOF_ALL = ABI_SIZEOF_ORDER + ABI_SIZEOF_APPENDED
 
 STRUCTS = {"sgp_settings": Settings, "sgp_world_desc": WorldDesc, "sgp_body_desc": BodyDesc,
@@ -266,7 +300,8 @@ STRUCTS = {"sgp_settings": Settings, "sgp_world_desc": WorldDesc, "sgp_body_desc
            "sgp_vehicle_state": VehicleState, "sgp_hull_info": HullInfo, "sgp_capsule_query": CapsuleQuery,
            "sgp_query_contact": QueryContact, "sgp_mesh_info": MeshInfo, "sgp_heightfield_desc": HeightfieldDesc,
            "sgp_checkpoint_info": CheckpointInfo, "sgp_shape_query": ShapeQuery, "sgp_shape_cast": ShapeCast,
-           "sgp_cast_hit": CastHit}
+           "sgp_cast_hit": CastHit, "sgp_character_desc": CharacterDesc, "sgp_character_input": CharacterInput,
+           "sgp_character_state": CharacterState, "sgp_character_contact": CharacterContact}
 
 body_desc_dtype = np.dtype(BodyDesc)
 body_state_dtype = np.dtype(BodyState)
@@ -285,6 +320,9 @@ query_contact_dtype = np.dtype(QueryContact)
 shape_query_dtype = np.dtype(ShapeQuery)
 shape_cast_dtype = np.dtype(ShapeCast)
 cast_hit_dtype = np.dtype(CastHit)
+character_input_dtype = np.dtype(CharacterInput)
+character_state_dtype = np.dtype(CharacterState)
+character_contact_dtype = np.dtype(CharacterContact)
 compound_child_dtype = np.dtype(CompoundChild)
 migration_dtype = np.dtype(Migration)
 
@@ -353,6 +391,18 @@ PROTOTYPES = {
     "collide_shapes": (C.c_int, [vp, vp, u32, vp, u32, P(u32)]),
     "cast_shapes": (C.c_int, [vp, vp, u32, vp]),
     "cast_shapes_counters": (C.c_int, [vp, P(u32)]),
+    # batched virtual characters (handle: void*)
+    "default_character_desc": (None, [P(CharacterDesc)]),
+    "characters_create": (C.c_int, [vp, u32, P(vp)]),
+    "characters_destroy": (C.c_int, [vp]),
+    "character_add": (C.c_int, [vp, P(CharacterDesc), P(f32), P(u32)]),
+    "character_remove": (C.c_int, [vp, u32]),
+    "characters_set_pose": (C.c_int, [vp, vp, vp, u32]),
+    "characters_set_shape": (C.c_int, [vp, u32, f32, f32, P(f32)]),
+    "characters_set_inputs": (C.c_int, [vp, u32, u32, vp]),
+    "characters_update": (C.c_int, [vp, f32]),
+    "characters_get_states": (C.c_int, [vp, u32, u32, vp]),
+    "characters_drain_contacts": (C.c_int, [vp, vp, u32, P(u32)]),
     "world_export_boundary": (C.c_int, [vp, P(f32), P(f32), f32, vp, u32, P(u32)]),
     "world_import_ghosts": (C.c_int, [vp, vp, u32]),
     "tiles_route": (C.c_int, [vp, u32, u32, vp, u32, f32, vp, u32, vp, vp, u32, P(u32)]),

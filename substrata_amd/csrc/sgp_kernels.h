@@ -14,6 +14,7 @@
 //   sgp_k_queries.hip      A7     k_raycast, k_collide_capsules, k_spherecast
 //   sgp_k_shapequery.hip   A7     k_sq_wave, k_sq_candidates + k_sq_pairs_prim / k_sq_pairs_hull / k_sq_mesh (sgp_collide_shapes)
 //   sgp_k_shapecast.hip    A7     k_sc_candidates + k_sc_pairs_prim / k_sc_pairs_hull / k_sc_mesh (sgp_cast_shapes)
+//   sgp_k_characters.hip   A7     k_characters_update (a wave per character: the whole Update / ExtendedUpdate), k_characters_push, k_characters_sync (sgp_characters_*)
 //   sgp_k_edits.hip        A5/A6  k_apply_cmds, k_ghost_refresh, read-back
 //   sgp_k_tiles.hip        (e)    tile export / routing, re-tiling histograms
 //   sgp_k_checkpoint.hip          k_ckpt_copy: the segmented copy of sgp_world_checkpoint / sgp_world_rollback
@@ -482,6 +483,41 @@ struct ScBufs {
 	uint2* prim; uint2* hull; uint2* mesh; uint32_t pcap;      // as SqBufs: sphere / box / capsule pairs, pairs with a convex hull on either side, pairs whose body is a mesh or a height field
 };
 void launch_shape_casts(const DV& d, const ScBufs& b, hipStream_t s);
+// ---- batched virtual characters (sgp_k_characters.hip, sgp_dev_character.h) -----------------------------------------------------------------------------
+// The host owns the descriptions and the inputs (CharRec, CharIn: uploaded when they change); the device owns the state (CharState, the active contacts and
+// the bodies already reported of every character).  The host reaches into the state only through serial numbers: a record whose reset / pose / input serial
+// differs from the one the state has seen makes the next launch clear the state / move the character / take the new velocity.
+#define SGP_CHAR_MAX_PUSHES 32       // push records of one character and update
+#define SGP_CHAR_MAX_ADDED 32        // contact-added records a character holds between drains
+#define SGP_CHAR_MAX_SEEN 128        // (body, sub shape) pairs a character remembers as reported within one update (between updates: those of its last contacts, <= 64)
+#define SGP_CHAR_MESH_LIST 32        // mesh bodies around one character the wave takes together (as QUERY_MESH_LIST)
+struct CharRec {
+	uint32_t alive, reset_serial, pose_serial, pad_;
+	float pose[3];
+	float radius, half_height, offset[3], up[3], sv_n[3], sv_c, cos_max_slope, mass, max_strength, predictive, padding, recovery, tolerance;
+	uint32_t max_coll_it, max_cons_it; float min_time;
+	float stick[3], stairs_up[3], min_step_fwd, step_fwd_test, cos_fwd, down_extra[3];
+};
+struct CharIn { float vel[3]; uint32_t ignore, flags, serial; };
+struct CharContact { uint32_t body, idx; float p[3], n[3], v[3], dist; uint32_t bits; float inv_mass; };      // bits: 1 sensor, 2 dynamic; body: raw slot; idx: point index (4 group + point)
+struct CharState {
+	float pos[3], vel[3]; uint32_t ground_state; float gn[3], gv[3], gp[3]; uint32_t ground_body, overflow;
+	uint32_t n_active, n_seen, reset_serial, pose_serial, in_serial, pad_[3];
+};
+struct CharPush { uint32_t body; float f[3], p[3]; uint32_t pad_; };
+struct CharAdded { uint32_t body, pad_; float p[3], n[3]; };
+struct CharBufs {
+	const CharRec* rec; const CharIn* in; CharState* st;
+	CharContact* active;      // [character][SGP_CHAR_MAX_CONTACTS]: CharacterVirtual::GetActiveContacts
+	uint32_t* seen;           // [character][SGP_CHAR_MAX_CONTACTS]
+	CharPush* push; uint32_t* n_push;        // [character][SGP_CHAR_MAX_PUSHES]; emptied by k_characters_push
+	uint32_t* push_any;       // one word: some character of the running update wrote a push record (plain store of 1; k_characters_push clears it, and has nothing to scan while it is 0)
+	CharAdded* added; uint32_t* n_added;     // [character][SGP_CHAR_MAX_ADDED]; emptied by the host's drain
+	uint32_t n;               // slots in use (high-water mark)
+};
+void launch_characters_update(const DV* d_dev, const CharBufs& b, float dt, hipStream_t s);      // d_dev: a copy of the world's DV in device memory (the phases are functions of their own: they read it through a pointer)
+void launch_characters_push(const DV& d, const CharBufs& b, hipStream_t s);
+void launch_characters_sync(const CharBufs& b, hipStream_t s);
 void launch_export_boundary(const DV& d, uint32_t nb, float3 lo, float3 hi, float margin, sgp_ghost_record* out, uint32_t cap, uint32_t* count, hipStream_t s);
 
 // ---- tile exchange with the routing on the device (sgp_tiles_*) ----------------------------------------------------

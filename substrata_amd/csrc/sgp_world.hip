@@ -80,6 +80,8 @@ SGP_API int sgp_abi_sizeof(int which)
 	case 14: return (int)sizeof(sgp_hull_info); case 15: return (int)sizeof(sgp_capsule_query); case 16: return (int)sizeof(sgp_query_contact); case 17: return (int)sizeof(sgp_mesh_info);
 	case 18: return (int)sizeof(sgp_heightfield_desc); case 19: return (int)sizeof(sgp_checkpoint_info); case 20: return (int)sizeof(sgp_shape_query);
 	case 22: return (int)sizeof(sgp_shape_cast); case 23: return (int)sizeof(sgp_cast_hit);      // (21 stays -1: bindings that know 21 structs probe it for the end of the list)
+	case 25: return (int)sizeof(sgp_character_desc); case 26: return (int)sizeof(sgp_character_input); case 27: return (int)sizeof(sgp_character_state);
+	case 28: return (int)sizeof(sgp_character_contact);      // (24 stays -1, as 21 does: bindings that know 24 structs probe it for the end of the list)
 	default: return -1;
 	}
 }

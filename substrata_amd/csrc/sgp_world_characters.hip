@@ -1,0 +1,303 @@
+// sgp_world_characters.hip -- the batched character controller (JPH::CharacterVirtual for many avatars): the host side of sgp_characters_*.
+// The host keeps the descriptions and inputs (uploaded when they change) and the slot bookkeeping; positions, ground states, active contacts and the bodies
+// already reported live on the device and are touched by the kernels of sgp_k_characters.hip alone.  An update enqueues and returns.
+#include "sgp_world_internal.h"
+
+struct sgp_characters {
+	sgp_world* w = nullptr; uint64_t world_serial = 0; int device = 0;
+	uint32_t cap = 0, high = 0, n_alive = 0;
+	std::vector<CharRec> rec; std::vector<CharIn> in; std::vector<uint32_t> free_list;
+	bool rec_dirty = false, in_dirty = false;
+	// device
+	DV* d_dv = nullptr; DV dv_uploaded; bool dv_valid = false;
+	CharRec* d_rec = nullptr; CharIn* d_in = nullptr; CharState* d_st = nullptr; CharContact* d_active = nullptr; uint32_t* d_seen = nullptr;
+	CharPush* d_push = nullptr; uint32_t* d_n_push = nullptr; CharAdded* d_added = nullptr; uint32_t* d_n_added = nullptr;
+	// pinned staging of the uploads ([DV][records][inputs]); `uploaded` is recorded behind the copies that read it, and waited for before it is written again
+	char* h_up = nullptr; hipEvent_t uploaded = nullptr; bool upload_in_flight = false;
+};
+
+// a tile's world: ghosts imported, or queued for import
+static bool world_holds_ghosts(const sgp_world* w) { return !w->ghost_map.empty() || !w->ghost_seq.empty() || !w->ghost_refresh.empty() || !w->rec_creates.empty(); }
+static bool chars_usable(const sgp_characters* cs) { return cs && cs->w && world_alive(cs->world_serial); }
+static size_t up_rec_off() { return (sizeof(DV) + 15) & ~size_t(15); }
+static size_t up_in_off(const sgp_characters* cs) { return up_rec_off() + ((sizeof(CharRec) * cs->cap + 15) & ~size_t(15)); }
+
+static CharBufs chars_bufs(const sgp_characters* cs)
+{
+	CharBufs b;
+	b.rec = cs->d_rec; b.in = cs->d_in; b.st = cs->d_st; b.active = cs->d_active; b.seen = cs->d_seen;
+	b.push = cs->d_push; b.n_push = cs->d_n_push; b.push_any = cs->d_n_push + cs->cap; b.added = cs->d_added; b.n_added = cs->d_n_added; b.n = cs->high;
+	return b;
+}
+
+SGP_API void sgp_default_character_desc(sgp_character_desc* d)
+{
+	if (!d) return;
+	memset(d, 0, sizeof(*d));
+	// CharacterShape, CharacterVirtualSettings and ExtendedUpdateSettings of shim/Jolt/JoltCharacterLite.h (Jolt's defaults)
+	d->radius = 0.3f; d->half_height = 0.65f;
+	d->up[1] = 1.0f;
+	d->supporting_plane[2] = 1.0f; d->supporting_plane[3] = 1.0e10f;
+	d->max_slope_angle = 50.0f * 3.14159265f / 180.0f;
+	d->mass = 70.0f; d->max_strength = 100.0f;
+	d->predictive_contact_distance = 0.1f; d->character_padding = 0.02f; d->penetration_recovery_speed = 1.0f; d->collision_tolerance = 1.0e-3f;
+	d->max_collision_iterations = 5; d->max_constraint_iterations = 15;
+	d->min_time_remaining = 1.0e-4f;
+	d->stick_to_floor_step_down[1] = -0.5f;
+	d->walk_stairs_step_up[1] = 0.4f;
+	d->walk_stairs_min_step_forward = 0.02f; d->walk_stairs_step_forward_test = 0.15f; d->walk_stairs_cos_angle_forward_contact = 0.2588f;
+}
+
+SGP_API int sgp_characters_destroy(sgp_characters* cs)
+{
+	if (!cs) return fail(SGP_ERR_INVALID, "sgp_characters_destroy: NULL");
+	hipSetDevice(cs->device);
+	if (chars_usable(cs)) hipStreamSynchronize(cs->w->stream);      // (a destroyed world has waited for its stream already)
+	void* dev[] = { cs->d_dv, cs->d_rec, cs->d_in, cs->d_st, cs->d_active, cs->d_seen, cs->d_push, cs->d_n_push, cs->d_added, cs->d_n_added };
+	for (void* p : dev) if (p) hipFree(p);
+	if (cs->h_up) hipHostFree(cs->h_up);
+	if (cs->uploaded) hipEventDestroy(cs->uploaded);
+	delete cs;
+	return SGP_OK;
+}
+
+template <typename T> static bool chars_alloc(T*& p, size_t n, hipStream_t s)
+{
+	const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
+	if (hipMalloc((void**)&p, bytes) != hipSuccess) { p = nullptr; return false; }
+	return hipMemsetAsync(p, 0, bytes, s) == hipSuccess;
+}
+
+SGP_API int sgp_characters_create(sgp_world* w, uint32_t capacity, sgp_characters** out)
+{
+	if (!w || !out || capacity == 0 || capacity > (1u << 20)) return fail(SGP_ERR_INVALID, "sgp_characters_create: NULL world or out, or a capacity of 0 or beyond 2^20");
+	if (world_holds_ghosts(w)) return fail(SGP_ERR_INVALID, "sgp_characters_create: the world holds ghost bodies (characters of tiled worlds are not supported)");
+	hipSetDevice(w->device);
+	sgp_characters* cs = new sgp_characters();
+	cs->w = w; cs->world_serial = w->serial; cs->device = w->device; cs->cap = capacity;
+	cs->rec.resize(capacity); cs->in.resize(capacity);
+	memset(cs->rec.data(), 0, sizeof(CharRec) * capacity); memset(cs->in.data(), 0, sizeof(CharIn) * capacity);
+	for (uint32_t i = 0; i < capacity; ++i) cs->in[i].ignore = SGP_INVALID_ID;
+	hipStream_t s = w->stream;
+	const size_t n = capacity;
+	bool ok = chars_alloc(cs->d_dv, 1, s) && chars_alloc(cs->d_rec, n, s) && chars_alloc(cs->d_in, n, s) && chars_alloc(cs->d_st, n, s)
+	       && chars_alloc(cs->d_active, n * SGP_CHAR_MAX_CONTACTS, s) && chars_alloc(cs->d_seen, n * SGP_CHAR_MAX_CONTACTS, s)
+	       && chars_alloc(cs->d_push, n * SGP_CHAR_MAX_PUSHES, s) && chars_alloc(cs->d_n_push, n + 1, s) && chars_alloc(cs->d_added, n * SGP_CHAR_MAX_ADDED, s) && chars_alloc(cs->d_n_added, n, s);
+	ok = ok && hipHostMalloc((void**)&cs->h_up, up_in_off(cs) + sizeof(CharIn) * n, hipHostMallocDefault) == hipSuccess;
+	ok = ok && hipEventCreateWithFlags(&cs->uploaded, hipEventDisableTiming) == hipSuccess;
+	if (!ok) { (void)hipGetLastError(); sgp_characters_destroy(cs); return fail(SGP_ERR_HIP, "sgp_characters_create: allocation"); }
+	*out = cs;
+	return SGP_OK;
+}
+
+static const char* character_desc_fault(const sgp_character_desc& d)
+{
+	if (!std::isfinite(d.radius) || !std::isfinite(d.half_height) || !finite3(d.shape_offset) || !finite3(d.up) || !finite4(d.supporting_plane) || !std::isfinite(d.max_slope_angle)
+	    || !std::isfinite(d.mass) || !std::isfinite(d.max_strength) || !std::isfinite(d.predictive_contact_distance) || !std::isfinite(d.character_padding)
+	    || !std::isfinite(d.penetration_recovery_speed) || !std::isfinite(d.collision_tolerance)) return "a non-finite value";
+	if (!std::isfinite(d.min_time_remaining) || !finite3(d.stick_to_floor_step_down) || !finite3(d.walk_stairs_step_up) || !finite3(d.walk_stairs_step_down_extra)
+	    || !std::isfinite(d.walk_stairs_min_step_forward) || !std::isfinite(d.walk_stairs_step_forward_test) || !std::isfinite(d.walk_stairs_cos_angle_forward_contact)) return "a non-finite value";
+	if (!(d.radius > 0.0f) || !(d.half_height >= 0.0f)) return "a non-positive capsule size";
+	if (!(d.up[0] * d.up[0] + d.up[1] * d.up[1] + d.up[2] * d.up[2] > 0.0f)) return "a zero up vector";
+	if (!(d.mass > 0.0f) || d.max_strength < 0.0f) return "a non-positive mass or a negative strength";
+	if (d.predictive_contact_distance < 0.0f || d.character_padding < 0.0f || d.collision_tolerance < 0.0f || d.penetration_recovery_speed < 0.0f) return "a negative distance";
+	if (d.max_collision_iterations == 0 || d.max_collision_iterations > 16 || d.max_constraint_iterations == 0 || d.max_constraint_iterations > 64) return "iteration limits outside 1..16 / 1..64";
+	if (!(d.min_time_remaining > 0.0f)) return "a non-positive minimum time remaining";      // (bounds the collision iterations' time)
+	return nullptr;
+}
+
+SGP_API int sgp_character_add(sgp_characters* cs, const sgp_character_desc* desc, const float pos[3], uint32_t* id_out)
+{
+	if (!chars_usable(cs) || !desc || !pos || !id_out) return fail(SGP_ERR_INVALID, "sgp_character_add: NULL, or the batch's world is gone");
+	if (!finite3(pos)) return fail(SGP_ERR_INVALID, "sgp_character_add: non-finite position");
+	if (const char* what = character_desc_fault(*desc)) { char msg[160]; snprintf(msg, sizeof(msg), "sgp_character_add: %s", what); return fail(SGP_ERR_INVALID, msg); }
+	uint32_t id;
+	if (!cs->free_list.empty()) { id = cs->free_list.back(); cs->free_list.pop_back(); }
+	else if (cs->high < cs->cap) id = cs->high++;
+	else return fail(SGP_ERR_CAPACITY, "sgp_character_add: the batch is full");
+	CharRec& r = cs->rec[id];
+	const uint32_t reset = r.reset_serial + 1u, pose = r.pose_serial + 1u;
+	memset(&r, 0, sizeof(r));
+	r.alive = 1; r.reset_serial = reset; r.pose_serial = pose;
+	memcpy(r.pose, pos, 12);
+	r.radius = desc->radius; r.half_height = desc->half_height; memcpy(r.offset, desc->shape_offset, 12); memcpy(r.up, desc->up, 12);
+	memcpy(r.sv_n, desc->supporting_plane, 12); r.sv_c = desc->supporting_plane[3];
+	r.cos_max_slope = std::cos(desc->max_slope_angle);      // (once, here: as CharacterVirtual's constructor)
+	r.mass = desc->mass; r.max_strength = desc->max_strength; r.predictive = desc->predictive_contact_distance; r.padding = desc->character_padding;
+	r.recovery = desc->penetration_recovery_speed; r.tolerance = desc->collision_tolerance;
+	r.max_coll_it = desc->max_collision_iterations; r.max_cons_it = desc->max_constraint_iterations; r.min_time = desc->min_time_remaining;
+	memcpy(r.stick, desc->stick_to_floor_step_down, 12); memcpy(r.stairs_up, desc->walk_stairs_step_up, 12);
+	r.min_step_fwd = desc->walk_stairs_min_step_forward; r.step_fwd_test = desc->walk_stairs_step_forward_test; r.cos_fwd = desc->walk_stairs_cos_angle_forward_contact;
+	memcpy(r.down_extra, desc->walk_stairs_step_down_extra, 12);
+	CharIn& in = cs->in[id];
+	const uint32_t in_serial = in.serial + 1u;
+	memset(&in, 0, sizeof(in)); in.ignore = SGP_INVALID_ID; in.serial = in_serial;
+	cs->rec_dirty = cs->in_dirty = true;
+	cs->n_alive++;
+	*id_out = id;
+	return SGP_OK;
+}
+
+static bool char_live(const sgp_characters* cs, uint32_t id) { return id < cs->high && cs->rec[id].alive; }
+
+SGP_API int sgp_character_remove(sgp_characters* cs, uint32_t id)
+{
+	if (!chars_usable(cs) || !char_live(cs, id)) return fail(SGP_ERR_INVALID, "sgp_character_remove: no such character");
+	hipSetDevice(cs->w->device);
+	HIP_TRY(hipMemsetAsync(cs->d_n_added + id, 0, sizeof(uint32_t), cs->w->stream));      // (its pending contact records go with it: the slot's next character starts with none)
+	cs->rec[id].alive = 0; cs->rec_dirty = true;
+	cs->free_list.push_back(id); cs->n_alive--;
+	return SGP_OK;
+}
+
+SGP_API int sgp_characters_set_pose(sgp_characters* cs, const uint32_t* ids, const float* pos, uint32_t n)
+{
+	if (!chars_usable(cs) || (n && (!ids || !pos))) return fail(SGP_ERR_INVALID, "sgp_characters_set_pose: NULL");
+	for (uint32_t i = 0; i < n; ++i) if (!char_live(cs, ids[i]) || !finite3(pos + 3 * i)) return fail(SGP_ERR_INVALID, "sgp_characters_set_pose: no such character, or a non-finite position");      // (all or nothing)
+	for (uint32_t i = 0; i < n; ++i) { CharRec& r = cs->rec[ids[i]]; memcpy(r.pose, pos + 3 * i, 12); r.pose_serial++; }
+	if (n) cs->rec_dirty = true;
+	return SGP_OK;
+}
+
+SGP_API int sgp_characters_set_shape(sgp_characters* cs, uint32_t id, float radius, float half_height, const float offset[3])
+{
+	if (!chars_usable(cs) || !char_live(cs, id) || !offset) return fail(SGP_ERR_INVALID, "sgp_characters_set_shape: no such character");
+	if (!std::isfinite(radius) || !std::isfinite(half_height) || !finite3(offset) || !(radius > 0.0f) || !(half_height >= 0.0f)) return fail(SGP_ERR_INVALID, "sgp_characters_set_shape: a non-finite or non-positive capsule size");
+	CharRec& r = cs->rec[id];
+	r.radius = radius; r.half_height = half_height; memcpy(r.offset, offset, 12);
+	cs->rec_dirty = true;
+	return SGP_OK;
+}
+
+SGP_API int sgp_characters_set_inputs(sgp_characters* cs, uint32_t first, uint32_t n, const sgp_character_input* inputs)
+{
+	if (!chars_usable(cs) || (n && !inputs)) return fail(SGP_ERR_INVALID, "sgp_characters_set_inputs: NULL");
+	if ((uint64_t)first + n > cs->high) return fail(SGP_ERR_INVALID, "sgp_characters_set_inputs: range beyond the last character");
+	for (uint32_t i = 0; i < n; ++i) {
+		if (!finite3(inputs[i].velocity)) return fail(SGP_ERR_INVALID, "sgp_characters_set_inputs: non-finite velocity");
+		if (inputs[i].flags & ~(SGP_CHAR_EXTENDED | SGP_CHAR_NO_SLIDE | SGP_CHAR_DISABLED)) return fail(SGP_ERR_INVALID, "sgp_characters_set_inputs: unknown flag");
+	}
+	for (uint32_t i = 0; i < n; ++i) {
+		CharIn& in = cs->in[first + i];
+		memcpy(in.vel, inputs[i].velocity, 12); in.ignore = inputs[i].ignore_id; in.flags = inputs[i].flags; in.serial++;
+	}
+	if (n) cs->in_dirty = true;
+	return SGP_OK;
+}
+
+// what changed on the host -> the device, behind whatever the stream holds (no wait for the stream; only for the previous upload to have left the staging buffer)
+static int chars_upload(sgp_characters* cs, bool with_dv)
+{
+	sgp_world* w = cs->w;
+	const bool dv_dirty = with_dv && (!cs->dv_valid || memcmp(&cs->dv_uploaded, &w->dv, sizeof(DV)) != 0);
+	if (!dv_dirty && !cs->rec_dirty && !cs->in_dirty) return SGP_OK;
+	if (cs->upload_in_flight) { HIP_TRY(hipEventSynchronize(cs->uploaded)); cs->upload_in_flight = false; }
+	if (dv_dirty) {
+		memcpy(cs->h_up, &w->dv, sizeof(DV));
+		HIP_TRY(hipMemcpyAsync(cs->d_dv, cs->h_up, sizeof(DV), hipMemcpyHostToDevice, w->stream));
+		memcpy(&cs->dv_uploaded, &w->dv, sizeof(DV)); cs->dv_valid = true;
+	}
+	if (cs->rec_dirty && cs->high) {
+		memcpy(cs->h_up + up_rec_off(), cs->rec.data(), sizeof(CharRec) * cs->high);
+		HIP_TRY(hipMemcpyAsync(cs->d_rec, cs->h_up + up_rec_off(), sizeof(CharRec) * cs->high, hipMemcpyHostToDevice, w->stream));
+	}
+	if (cs->in_dirty && cs->high) {
+		memcpy(cs->h_up + up_in_off(cs), cs->in.data(), sizeof(CharIn) * cs->high);
+		HIP_TRY(hipMemcpyAsync(cs->d_in, cs->h_up + up_in_off(cs), sizeof(CharIn) * cs->high, hipMemcpyHostToDevice, w->stream));
+	}
+	cs->rec_dirty = cs->in_dirty = false;
+	HIP_TRY(hipEventRecord(cs->uploaded, w->stream));
+	cs->upload_in_flight = true;
+	return SGP_OK;
+}
+
+SGP_API int sgp_characters_update(sgp_characters* cs, float dt)
+{
+	if (!chars_usable(cs)) return fail(SGP_ERR_INVALID, "sgp_characters_update: NULL, or the batch's world is gone");
+	if (!std::isfinite(dt) || !(dt > 0.0f)) return fail(SGP_ERR_INVALID, "sgp_characters_update: dt must be finite and positive");
+	sgp_world* w = cs->w;
+	hipSetDevice(w->device);
+	if (world_holds_ghosts(w)) return fail(SGP_ERR_INVALID, "sgp_characters_update: the world holds ghost bodies (characters of tiled worlds are not supported)");
+	{ int r = flush_cmds(w); if (r != SGP_OK) return r; }
+	if (!cs->high || !cs->n_alive) return SGP_OK;
+	ensure_query_grid(w);
+	{ int r = chars_upload(cs, true); if (r != SGP_OK) return r; }
+	{ int r = flush_event_reset(w); if (r != SGP_OK) return r; }      // (a push may wake a body: an activation event)
+	const CharBufs b = chars_bufs(cs);
+	launch_characters_update(cs->d_dv, b, dt, w->stream);
+	launch_characters_push(w->dv, b, w->stream);
+	// a push leaves a force on a body, and may have woken it, without the host hearing of it: the next step is not skipped as idle, and the event lists may hold something
+	w->dirty_since_step = true; w->events_on_device = true;
+	HIP_TRY(hipGetLastError());
+	return SGP_OK;
+}
+
+SGP_API int sgp_characters_get_states(sgp_characters* cs, uint32_t first, uint32_t n, sgp_character_state* out)
+{
+	if (!chars_usable(cs) || (n && !out)) return fail(SGP_ERR_INVALID, "sgp_characters_get_states: NULL, or the batch's world is gone");
+	if ((uint64_t)first + n > cs->cap) return fail(SGP_ERR_INVALID, "sgp_characters_get_states: range beyond the batch's capacity");
+	if (!n) return SGP_OK;
+	sgp_world* w = cs->w;
+	hipSetDevice(w->device);
+	ray_server_stop(w);
+	if (cs->rec_dirty || cs->in_dirty) {
+		{ int r = chars_upload(cs, false); if (r != SGP_OK) return r; }
+		launch_characters_sync(chars_bufs(cs), w->stream);
+	}
+	{ int r = ensure_stage(w, sizeof(CharState) * n); if (r != SGP_OK) return r; }
+	HIP_TRY(hipMemcpyAsync(w->stage_host, cs->d_st + first, sizeof(CharState) * n, hipMemcpyDeviceToHost, w->stream));
+	HIP_TRY(hipStreamSynchronize(w->stream));
+	const CharState* hs = (const CharState*)w->stage_host;
+	for (uint32_t i = 0; i < n; ++i) {
+		sgp_character_state& o = out[i];
+		memset(&o, 0, sizeof(o));
+		o.ground_state = SGP_GROUND_IN_AIR; o.ground_body = SGP_INVALID_ID;
+		if (!char_live(cs, first + i)) continue;
+		const CharState& s = hs[i];
+		memcpy(o.pos, s.pos, 12); memcpy(o.lin_vel, s.vel, 12);
+		o.ground_state = s.ground_state;
+		memcpy(o.ground_normal, s.gn, 12); memcpy(o.ground_velocity, s.gv, 12); memcpy(o.ground_position, s.gp, 12);
+		o.overflow = s.overflow;
+		if (s.ground_body != SGP_INVALID_ID && s.ground_body < w->hb.size()) {
+			o.ground_userdata = w->hb[s.ground_body].userdata;
+			o.ground_body = compound_id_of(w, s.ground_body, &o.ground_sub_shape);
+		}
+	}
+	return SGP_OK;
+}
+
+SGP_API int sgp_characters_drain_contacts(sgp_characters* cs, sgp_character_contact* out, uint32_t cap, uint32_t* n_out)
+{
+	if (!chars_usable(cs) || (cap && !out) || !n_out) return fail(SGP_ERR_INVALID, "sgp_characters_drain_contacts: NULL, or the batch's world is gone");
+	*n_out = 0;
+	if (!cs->high) return SGP_OK;
+	sgp_world* w = cs->w;
+	hipSetDevice(w->device);
+	ray_server_stop(w);
+	const size_t cb = (sizeof(uint32_t) * cs->high + 15) & ~size_t(15);
+	{ int r = ensure_stage(w, cb + sizeof(CharAdded) * SGP_CHAR_MAX_ADDED * (size_t)cs->high); if (r != SGP_OK) return r; }
+	HIP_TRY(hipMemcpyAsync(w->stage_host, cs->d_n_added, sizeof(uint32_t) * cs->high, hipMemcpyDeviceToHost, w->stream));
+	HIP_TRY(hipStreamSynchronize(w->stream));
+	const uint32_t* counts = (const uint32_t*)w->stage_host;
+	uint32_t last = 0, total = 0;
+	for (uint32_t k = 0; k < cs->high; ++k) if (counts[k]) { last = k + 1; total += std::min(counts[k], (uint32_t)SGP_CHAR_MAX_ADDED); }
+	if (!total) return SGP_OK;
+	HIP_TRY(hipMemcpyAsync((char*)w->stage_host + cb, cs->d_added, sizeof(CharAdded) * SGP_CHAR_MAX_ADDED * (size_t)last, hipMemcpyDeviceToHost, w->stream));
+	HIP_TRY(hipMemsetAsync(cs->d_n_added, 0, sizeof(uint32_t) * cs->high, w->stream));
+	HIP_TRY(hipStreamSynchronize(w->stream));
+	const CharAdded* recs = (const CharAdded*)((char*)w->stage_host + cb);
+	uint32_t m = 0;
+	for (uint32_t k = 0; k < last; ++k) for (uint32_t r = 0; r < std::min(counts[k], (uint32_t)SGP_CHAR_MAX_ADDED); ++r) {
+		const CharAdded& a = recs[(size_t)k * SGP_CHAR_MAX_ADDED + r];
+		if (a.body >= w->hb.size()) continue;      // (cannot happen: the device reports slots it found alive)
+		if (m < cap) {
+			sgp_character_contact& o = out[m];
+			memset(&o, 0, sizeof(o));
+			o.character = k; o.userdata = w->hb[a.body].userdata; o.body = compound_id_of(w, a.body, &o.sub_shape);
+			memcpy(o.point, a.p, 12); memcpy(o.normal, a.n, 12);
+		}
+		++m;
+	}
+	*n_out = m;
+	return SGP_OK;
+}

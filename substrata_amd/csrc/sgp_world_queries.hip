@@ -97,7 +97,7 @@ SGP_API int sgp_raycast(sgp_world* w, const sgp_ray* rays, uint32_t n, sgp_hit* 
 	return SGP_OK;
 }
 
-static int ensure_query_grid(sgp_world* w)
+int ensure_query_grid(sgp_world* w)
 {
 	if (!w->grid_valid && w->high) {
 		// poses changed since the grid was built (a step integrates after its broad phase; edits move bodies): re-bin

@@ -56,6 +56,67 @@ class Checkpoint:
             pass
 
 
+class Characters:
+    """A batch of virtual characters of one world (sgp_characters): numpy in, numpy out.  update() enqueues and returns; states() waits."""
+
+    def __init__(self, world, capacity):
+        self._w, self._h = world, C.c_void_p()
+        world._check(world._fn("characters_create")(world._h, int(capacity), C.byref(self._h)), "characters_create")
+        self.capacity = int(capacity)
+
+    def default_desc(self):
+        d = abi.CharacterDesc()
+        self._w._fn("default_character_desc")(C.byref(d))
+        return d
+
+    def add(self, desc, pos):
+        i = C.c_uint32(0)
+        self._w._check(self._w._fn("character_add")(self._h, C.byref(desc), _fp(_f3(pos)), C.byref(i)), "character_add")
+        return int(i.value)
+
+    def remove(self, i):
+        self._w._check(self._w._fn("character_remove")(self._h, int(i)), "character_remove")
+
+    def set_pose(self, ids, pos):
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        pos = np.ascontiguousarray(pos, dtype=np.float32).reshape(len(ids), 3)
+        self._w._check(self._w._fn("characters_set_pose")(self._h, ids.ctypes.data, pos.ctypes.data, len(ids)), "characters_set_pose")
+
+    def set_shape(self, i, radius, half_height, offset=(0.0, 0.0, 0.0)):
+        self._w._check(self._w._fn("characters_set_shape")(self._h, int(i), float(radius), float(half_height), _fp(_f3(offset))), "characters_set_shape")
+
+    def set_inputs(self, first, inputs):
+        """inputs: array of abi.character_input_dtype (velocity, ignore_id, flags) for characters first, first + 1, ..."""
+        inputs = np.ascontiguousarray(inputs, dtype=abi.character_input_dtype).reshape(-1)
+        self._w._check(self._w._fn("characters_set_inputs")(self._h, int(first), len(inputs), inputs.ctypes.data), "characters_set_inputs")
+
+    def update(self, dt=1.0 / 60.0):
+        self._w._check(self._w._fn("characters_update")(self._h, float(dt)), "characters_update")
+
+    def states(self, first=0, n=None):
+        n = self.capacity - first if n is None else int(n)
+        out = np.zeros(n, dtype=abi.character_state_dtype)
+        self._w._check(self._w._fn("characters_get_states")(self._h, int(first), n, out.ctypes.data), "characters_get_states")
+        return out
+
+    def drain_contacts(self, cap=4096):
+        out = np.zeros(cap, dtype=abi.character_contact_dtype)
+        n = C.c_uint32(0)
+        self._w._check(self._w._fn("characters_drain_contacts")(self._h, out.ctypes.data, cap, C.byref(n)), "characters_drain_contacts")
+        return out[:min(n.value, cap)].copy()
+
+    def close(self):
+        if self._h:
+            self._w._fn("characters_destroy")(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class CWorld:
     def __init__(self, lib, prefix, max_bodies=65536, gravity=(0.0, 0.0, -9.81), device=0, settings=None,
                  max_body_pairs=0, max_manifolds=0, large_body_radius=0.0):
@@ -419,6 +480,10 @@ class CWorld:
     def vehicle_reset_drivetrain(self, vid, engine_rpm=0.0, wheel_angular_velocity=0.0):
         self._check(self._fn("vehicle_reset_drivetrain")(self._h, int(vid), float(engine_rpm), float(wheel_angular_velocity)),
                     "vehicle_reset_drivetrain")
+
+    def characters(self, capacity):
+        """A batch of up to `capacity` virtual characters that belongs to this world (close it before the world)."""
+        return Characters(self, capacity)
 
     def collide_capsules(self, queries, cap=4096):
         queries = np.ascontiguousarray(queries, dtype=abi.capsule_query_dtype)
