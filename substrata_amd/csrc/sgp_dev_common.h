@@ -14,6 +14,49 @@
 
 SGP_DEV const ConstraintArrays& CUR(const DV& d) { return d.ca[d.sp->parity & 1]; }
 SGP_DEV const ConstraintArrays& PRV(const DV& d) { return d.ca[(d.sp->parity & 1) ^ 1]; }
+// The same buffers resolved ONCE, by value: a kernel calls this at entry, before any store, with the parity it read through its preloaded StepParams pointer
+// (one scalar load), and hands the result to the device functions of the solver.  The pointers then live in scalar registers for the whole kernel; CUR(d)
+// at every use re-read the parity (after a store the compiler can neither hoist nor scalarise that load) and fetched each pointer from the argument segment
+// at an address computed from it -- dependent memory round trips on the chain of every solver launch.  The parity stays a device-side value.
+SGP_DEV ConstraintArrays cur_arrays(const DV& d, uint32_t parity)
+{
+	// member by member, a select between two VALUES: both buffers' pointers are fetched from the argument segment at fixed addresses, beside the parity
+	// and everything else the kernel's head asks for, and picked with scalar selects when they are in -- one wait.  (`parity ? d.ca[1] : d.ca[0]` as a struct
+	// copy compiles to a select between the two ADDRESSES: the pointer fetch then waits for the parity, a dependent level more.)  Members a kernel
+	// does not use cost nothing.
+	const bool odd = (parity & 1u) != 0u;
+	const ConstraintArrays &a = d.ca[0], &b = d.ca[1];
+	const auto pick = [odd](auto pa, auto pb) { return odd ? pb : pa; };      // (by value: `odd ? b.hdr : a.hdr` on the members themselves is a select between two addresses again)
+	ConstraintArrays c;
+	c.hdr = pick(a.hdr, b.hdr); c.n_fric = pick(a.n_fric, b.n_fric); c.prec = pick(a.prec, b.prec);
+#pragma unroll
+	for (int i = 0; i < 4; ++i) {
+		c.r1b[i] = pick(a.r1b[i], b.r1b[i]); c.r2e[i] = pick(a.r2e[i], b.r2e[i]); c.lam[i] = pick(a.lam[i], b.lam[i]);
+		c.efft[i] = pick(a.efft[i], b.efft[i]); c.loc1[i] = pick(a.loc1[i], b.loc1[i]); c.loc2[i] = pick(a.loc2[i], b.loc2[i]);
+	}
+	return c;
+}
+// The head of a solver kernel: names, as operands of ONE empty instruction, every scalar the first data loads need -- the resolved pointers the kernel reads, the
+// colour's slot range, the base of the body records, the grid size.  The loads and selects that produce them cannot be moved below it; left alone, the compiler moves
+// each argument fetch behind the range check, next to its first use, and the head becomes a chain of scalar fetches with a wait each.  Here nothing of it depends on
+// anything else of it, so all is requested together, under one wait.
+// WHAT: the lever arms, effective masses and impulses (velocity iterations on the layout without rows, the warm start); the impulses alone (velocity iterations on
+// rows); the contact points in the bodies' frames (position iterations) -- always with the header and the normal.
+enum { CA_ARMS = 1, CA_LAM = 2, CA_LOC = 4 };
+#define SGP_KEEP4(a) "s"((a)[0]), "s"((a)[1]), "s"((a)[2]), "s"((a)[3])
+template <int WHAT> SGP_DEV void keep_buffer(const ConstraintArrays& c)
+{
+	if constexpr (WHAT == CA_ARMS) asm volatile("" :: "s"(c.hdr), "s"(c.n_fric), SGP_KEEP4(c.r1b), SGP_KEEP4(c.r2e), SGP_KEEP4(c.efft), SGP_KEEP4(c.lam));
+	else if constexpr (WHAT == CA_LAM) asm volatile("" :: "s"(c.hdr), "s"(c.n_fric), SGP_KEEP4(c.lam));
+	else asm volatile("" :: "s"(c.hdr), "s"(c.n_fric), SGP_KEEP4(c.loc1), SGP_KEEP4(c.loc2));
+}
+template <int WHAT> SGP_DEV void keep_head(const DV& d, uint32_t parity, uint32_t first, uint32_t end, const void* records, uint32_t grid)
+{
+	asm volatile("" :: "s"(parity), "s"(first), "s"(end), "s"(records), "s"(grid));
+	if constexpr (WHAT == CA_LAM) asm volatile("" :: "s"(d.rows), "s"(d.cap_manifolds));      // (the rows' base and stride)
+	keep_buffer<WHAT>(d.ca[0]);
+	keep_buffer<WHAT>(d.ca[1]);
+}
 // a constraint's header: the two body ids (8 bytes), np_col, or all of it in one 16-byte load
 SGP_DEV uint2 con_ab(const ConstraintArrays& c, size_t k) { return *(const uint2*)(c.hdr + k); }
 SGP_DEV int& con_npc(const ConstraintArrays& c, size_t k) { return ((int*)(c.hdr + k))[2]; }

@@ -37,6 +37,13 @@ SGP_DEV float lane_swap1(float x)
 //
 // A constraint half in registers: loaded once (half_load), iterated any number of times (half_solve: only this lane's body's velocities
 // are gathered and scattered), lambdas written back at the end by lane 0 (half_store).
+// The loads of a manifold's points as ONE dependent level: point 0 without waiting for the point count, the others NESTED -- if (np > 1) { point 1; if (np > 2)
+// { point 2; if (np > 3) point 3; } }.  With a branch per point side by side, each branch ended in register copies of what it had just loaded (the values merge with
+// "nothing" for a manifold without that point), a copy waits for its load, and the points of a four-point manifold arrived one round trip after the other; nested,
+// the copies come behind the innermost branch, after every load has been issued.  f(i) is called with a constant after inlining.
+template <class F> SGP_DEV void more_points(int np, F f) { if (np > 1) { f(1); if (np > 2) { f(2); if (np > 3) f(3); } } }
+template <class F> SGP_DEV void for_points(int np, F f) { f(0); more_points(np, f); }
+
 struct ConHalf {
 	uint32_t body;          // this lane's body
 	float4 nf; int np_col;
@@ -50,7 +57,7 @@ struct ConHalf {
 
 // ROWS: the row layout as a compile-time fact (0 full, 1 compact) where the launch knows it -- the colour launches: with both layouts behind a run-time
 // branch the velocity kernel spilled ten registers --, -1 = read StepParams::compact_rows
-template <int ROWS = -1> SGP_DEV void half_load_rows(const DV& d, uint32_t slot, int side, ConHalf& h)
+template <int ROWS = -1> SGP_DEV void half_load_rows(const DV& d, const ConstraintArrays& ca, uint32_t slot, int side, ConHalf& h)
 {
 	const int np = h.np_col & 0xFF;
 	const size_t st = d.cap_manifolds;
@@ -62,19 +69,18 @@ template <int ROWS = -1> SGP_DEV void half_load_rows(const DV& d, uint32_t slot,
 		const v3 n = V3(h.nf);
 		h.t1 = v3_normalized_perpendicular(n);
 		const v3 t2 = v3_cross(n, h.t1);
+		float4 r4[4]; float2 et[4];
+		for_points(np, [&](int i) { r4[i] = (side ? ca.r2e[i] : ca.r1b[i])[slot]; et[i] = ca.efft[i][slot]; h.lam[i] = V3(ca.lam[i][slot]); });      // (a select between two pointers in registers, one load)
 #pragma unroll
 		for (int i = 0; i < 4; ++i) {
 			if (i == 0 || i < np) {
-				const float4 r4 = side ? CUR(d).r2e[i][slot] : CUR(d).r1b[i][slot];
-				const float2 et = CUR(d).efft[i][slot];
-				const v3 r = V3(r4);
+				const v3 r = V3(r4[i]);
 				h.c[i][0] = v3_cross(r, n); h.c[i][1] = v3_cross(r, h.t1); h.c[i][2] = v3_cross(r, t2);
 #pragma unroll
 				for (int a = 0; a < 3; ++a) h.iv[i][a] = sym33_mul(I, h.c[i][a]);
-				const float ow = lane_swap1(r4.w);
-				h.eff[i][0] = side ? r4.w : ow; h.bias[i] = side ? ow : r4.w;
-				h.eff[i][1] = et.x; h.eff[i][2] = et.y;
-				h.lam[i] = V3(CUR(d).lam[i][slot]);
+				const float ow = lane_swap1(r4[i].w);
+				h.eff[i][0] = side ? r4[i].w : ow; h.bias[i] = side ? ow : r4[i].w;
+				h.eff[i][1] = et[i].x; h.eff[i][2] = et[i].y;
 			}
 		}
 		return;
@@ -94,7 +100,7 @@ template <int ROWS = -1> SGP_DEV void half_load_rows(const DV& d, uint32_t slot,
 					h.eff[i][a] = side ? c4.w : ow;
 					if (a == 0) h.bias[i] = side ? ow : c4.w;
 				}
-				h.lam[i] = V3(CUR(d).lam[i][slot]);
+				h.lam[i] = V3(ca.lam[i][slot]);
 			}
 		}
 		h.t1 = v3_normalized_perpendicular(V3(h.nf));
@@ -120,32 +126,36 @@ template <int ROWS = -1> SGP_DEV void half_load_rows(const DV& d, uint32_t slot,
 					if (a == 0) { h.t1.x = side ? oi : i4.w; h.t1.y = side ? i4.w : oi; } else h.t1.z = side ? oi : i4.w;
 				}
 			}
-			const float4 l4 = CUR(d).lam[i][slot];
+			const float4 l4 = ca.lam[i][slot];
 			h.lam[i] = V3(l4);
 		}
 	}
 }
 
-template <int ROWS = -1> SGP_DEV void half_load_known(const DV& d, uint32_t slot, int side, int np_col, uint32_t body, ConHalf& h)      // (header already known: nothing here waits for it)
+template <int ROWS = -1> SGP_DEV void half_load_known(const DV& d, const ConstraintArrays& ca, uint32_t slot, int side, int np_col, uint32_t body, ConHalf& h)      // (header already known: nothing here waits for it)
 {
 	h.body = body;
-	h.nf = CUR(d).n_fric[slot];
+	h.nf = ca.n_fric[slot];
 	h.np_col = np_col;
-	half_load_rows<ROWS>(d, slot, side, h);
+	half_load_rows<ROWS>(d, ca, slot, side, h);
 }
-template <int ROWS = -1> SGP_DEV void half_load(const DV& d, uint32_t slot, int side, ConHalf& h)
+template <int ROWS = -1> SGP_DEV void half_load(const DV& d, const ConstraintArrays& ca, uint32_t slot, int side, ConHalf& h)
 {
-	const uint4 hd = con_hdr(CUR(d), slot);      // ids + np_col: one 16-byte load
-	half_load_known<ROWS>(d, slot, side, (int)hd.z, side ? hd.y : hd.x, h);
+	const uint4 hd = con_hdr(ca, slot);      // ids + np_col: one 16-byte load
+	half_load_known<ROWS>(d, ca, slot, side, (int)hd.z, side ? hd.y : hd.x, h);
 }
 
-SGP_DEV void half_store(const DV& d, uint32_t slot, int side, const ConHalf& h)
+SGP_DEV void half_store(const ConstraintArrays& ca, uint32_t slot, int side, const ConHalf& h)
 {
 	if (side) return;
 	const int np = h.np_col & 0xFF;
 #pragma unroll
-	for (int i = 0; i < 4; ++i) { if (i < np) CUR(d).lam[i][slot] = F4(h.lam[i], 0.0f); }
+	for (int i = 0; i < 4; ++i) { if (i < np) ca.lam[i][slot] = F4(h.lam[i], 0.0f); }
 }
+
+// (the forms that look the buffer up themselves: experiments)
+template <int ROWS = -1> SGP_DEV void half_load(const DV& d, uint32_t slot, int side, ConHalf& h) { half_load<ROWS>(d, CUR(d), slot, side, h); }
+SGP_DEV void half_store(const DV& d, uint32_t slot, int side, const ConHalf& h) { half_store(CUR(d), slot, side, h); }
 
 // this body's share of J v for one row, the neighbour's share, their difference (share of body 1 minus share of body 2: identical on both lanes)
 SGP_DEV float half_jv(v3 lv, v3 av, v3 axis, v3 c, int side)
@@ -209,41 +219,39 @@ template <int VS> SGP_DEV void half_solve(ConHalf& h, int side, float4* vel, uin
 }
 
 // load + one iteration + store: what a colour launch does per constraint (lanes 2k and 2k + 1 of a wave call it with the same slot)
-template <int VS, int ROWS = -1> SGP_DEV void solve_velocity_pair_t(const DV& d, uint32_t slot, int side, float4* vel)
+template <int VS, int ROWS = -1> SGP_DEV void solve_velocity_pair_t(const DV& d, const ConstraintArrays& ca, uint32_t slot, int side, float4* vel)
 {
 	ConHalf h;
-	half_load<ROWS>(d, slot, side, h);
+	half_load<ROWS>(d, ca, slot, side, h);
 	half_solve<VS>(h, side, vel, d.dbg_flags);
-	half_store(d, slot, side, h);
+	half_store(ca, slot, side, h);
 }
+
+template <int VS, int ROWS = -1> SGP_DEV void solve_velocity_pair_t(const DV& d, uint32_t slot, int side, float4* vel) { solve_velocity_pair_t<VS, ROWS>(d, CUR(d), slot, side, vel); }
 
 // The same for the layout without rows (ROWS = 2: worlds of a million constraints and more), written so that nothing is kept that is used once: a colour launch
 // loads a constraint, iterates it ONCE and stores it, so r x axis and I (r x axis) -- 72 registers of a ConHalf -- are built where the row is applied instead of
 // where the constraint is loaded.  The same expressions on the same operands in the same order as half_load_rows<2> + half_solve_core (each value is computed once
 // either way): the same bits.  What it buys is registers: the launch fits four waves per SIMD, and a colour of 300k constraints is nine waves per SIMD.
-template <int VS> SGP_DEV void solve_velocity_pair_norows(const DV& d, uint32_t slot, int side, float4* vel)
+template <int VS> SGP_DEV void solve_velocity_pair_norows(const DV& d, const ConstraintArrays& ca, uint32_t slot, int side, float4* vel)
 {
-	const uint4 hd = con_hdr(CUR(d), slot);      // ids + np_col: one 16-byte load
+	const uint4 hd = con_hdr(ca, slot);      // ids + np_col: one 16-byte load
 	const int np = (int)hd.z & 0xFF;
 	const uint32_t body = side ? hd.y : hd.x;
-	const float4 nf = CUR(d).n_fric[slot];
+	const float4 nf = ca.n_fric[slot];
 	float4 r4[4]; float2 et[4]; v3 lam[4];
-#pragma unroll
-	for (int i = 0; i < 4; ++i) {
-		if (i == 0 || i < np) { r4[i] = side ? CUR(d).r2e[i][slot] : CUR(d).r1b[i][slot]; et[i] = CUR(d).efft[i][slot]; lam[i] = V3(CUR(d).lam[i][slot]); }
-		else { r4[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); et[i] = make_float2(0.0f, 0.0f); lam[i] = V3(0.0f, 0.0f, 0.0f); }
-	}
-	if (np == 0) return;                                    // a sensor pair: kept in the contact list, nothing to solve
+	const auto load_point = [&](int i) { r4[i] = (side ? ca.r2e[i] : ca.r1b[i])[slot]; et[i] = ca.efft[i][slot]; lam[i] = V3(ca.lam[i][slot]); };      // (what is not loaded is not read below)
+	load_point(0);
+	// the gather by body id goes out BESIDE the further points: both wait for the header and for nothing else (a sensor pair gathers for nothing: its ids are bodies too)
 	const sym33 I = body_world_inv_inertia_rec(d, body);
 	float4 v4 = vel[VS * (size_t)body], w4 = vel[VS * (size_t)body + 1];
+	more_points(np, load_point);
+	if (np == 0) return;                                    // a sensor pair: kept in the contact list, nothing to solve
 	const float im = v4.w, friction = nf.w;
 	v3 lv = V3(v4), av = V3(w4);
 	const v3 n = V3(nf);
 	const v3 t1 = v3_normalized_perpendicular(n);
 	const v3 t2 = v3_cross(n, t1);
-	float eff0[4], bias[4];
-#pragma unroll
-	for (int i = 0; i < 4; ++i) { const float ow = lane_swap1(r4[i].w); eff0[i] = side ? r4[i].w : ow; bias[i] = side ? ow : r4[i].w; }
 	if (friction > 0.0f) {
 #pragma unroll
 		for (int i = 0; i < 4; ++i) {
@@ -262,10 +270,13 @@ template <int VS> SGP_DEV void solve_velocity_pair_norows(const DV& d, uint32_t 
 	}
 #pragma unroll
 	for (int i = 0; i < 4; ++i) {
-		if (i < np && eff0[i] > 0.0f) {
+		if (i >= np) continue;
+		const float ow = lane_swap1(r4[i].w);      // (both lanes of the pair are here: they share np)
+		const float eff0 = side ? r4[i].w : ow, bias = side ? ow : r4[i].w;
+		if (eff0 > 0.0f) {
 			const v3 c0 = v3_cross(V3(r4[i]), n);
 			const float jv = half_jv(lv, av, n, c0, side);
-			const float lambda = eff0[i] * (jv - bias[i]);
+			const float lambda = eff0 * (jv - bias);
 			const float nl = max0f(lam[i].x + lambda);
 			half_apply(lv, av, im, n, sym33_mul(I, c0), nl - lam[i].x, side);
 			lam[i].x = nl;
@@ -274,7 +285,7 @@ template <int VS> SGP_DEV void solve_velocity_pair_norows(const DV& d, uint32_t 
 	if (im > 0.0f) { vel[VS * (size_t)body] = F4(lv, im); vel[VS * (size_t)body + 1] = F4(av, 0.0f); }
 	if (!side) {
 #pragma unroll
-		for (int i = 0; i < 4; ++i) { if (i < np) CUR(d).lam[i][slot] = F4(lam[i], 0.0f); }
+		for (int i = 0; i < 4; ++i) { if (i < np) ca.lam[i][slot] = F4(lam[i], 0.0f); }
 	}
 }
 
@@ -284,21 +295,20 @@ template <int VS> SGP_DEV void solve_velocity_pair_norows(const DV& d, uint32_t 
 // hence the same bits -- at about half the instructions per lane, which is what a position launch is made of (4700 of them per manifold).
 // What a position iteration reads of the constraint itself (this lane's side): loaded once, iterated any number of times.
 struct PosHalf { float4 nf; int np; v3 loc[4]; };
-SGP_DEV void pos_half_load(const DV& d, uint32_t slot, int side, int np_col, PosHalf& ph)
+SGP_DEV void pos_half_load(const ConstraintArrays& ca, uint32_t slot, int side, int np_col, PosHalf& ph)
 {
-	ph.nf = CUR(d).n_fric[slot];
+	ph.nf = ca.n_fric[slot];
 	ph.np = np_col & 0xFF;
-#pragma unroll
-	for (int i = 0; i < 4; ++i) if (i == 0 || i < ph.np) ph.loc[i] = V3(side ? CUR(d).loc2[i][slot] : CUR(d).loc1[i][slot]);      // (point 0: without waiting for the count)
+	for_points(ph.np, [&](int i) { ph.loc[i] = V3((side ? ca.loc2[i] : ca.loc1[i])[slot]); });
 }
 // (rec: where this lane's body's pose record lives -- the global one, or a workgroup's copy in LDS; ii: its local inverse inertia diagonal)
-SGP_DEV void pos_half_solve(const DV& d, const PosHalf& ph, int side, float4* rec, v3 ii)
+// (p4, q4: the two float4 of the record, already read)
+SGP_DEV void pos_half_solve_rec(const DV& d, const PosHalf& ph, int side, float4* rec, float4 p4, float4 q4, v3 ii)
 {
 	const v3 nrm = V3(ph.nf);
 	const int np = ph.np;
-	const float4 p4 = rec[0];
 	const float im = p4.w;                                          // 0 unless dynamic (see solve_position_one)
-	quat q = Q4(rec[1]);
+	quat q = Q4(q4);
 	v3 pos = V3(p4);
 	bool moved = false;
 	m33 R = quat_to_m33(q);
@@ -334,18 +344,26 @@ SGP_DEV void pos_half_solve(const DV& d, const PosHalf& ph, int side, float4* re
 	}
 	if (moved && im > 0.0f) { rec[0] = F4(pos, im); rec[1] = make_float4(q.x, q.y, q.z, q.w); }
 }
-SGP_DEV void solve_position_pair(const DV& d, uint32_t slot, int side)
+SGP_DEV void pos_half_solve(const DV& d, const PosHalf& ph, int side, float4* rec, v3 ii) { pos_half_solve_rec(d, ph, side, rec, rec[0], rec[1], ii); }
+SGP_DEV void solve_position_pair(const DV& d, const ConstraintArrays& ca, uint32_t slot, int side)
 {
-	const uint4 hd = con_hdr(CUR(d), slot);      // ids + np_col: one 16-byte load
+	const uint4 hd = con_hdr(ca, slot);      // ids + np_col: one 16-byte load
 	const uint32_t body = side ? hd.y : hd.x;
 	PosHalf ph;
-	pos_half_load(d, slot, side, (int)hd.z, ph);
-	pos_half_solve(d, ph, side, d.pose + POSE_F4 * (size_t)body, V3(d.pose[POSE_F4 * (size_t)body + 2]));      // this lane's body's pose record + its local inverse inertia
+	ph.nf = ca.n_fric[slot];
+	ph.np = (int)hd.z & 0xFF;
+	const auto load_point = [&](int i) { ph.loc[i] = V3((side ? ca.loc2[i] : ca.loc1[i])[slot]); };
+	load_point(0);
+	// this lane's body's pose record + its local inverse inertia, requested BESIDE the further points: both wait for the header and for nothing else
+	float4* rec = d.pose + POSE_F4 * (size_t)body;
+	const float4 p4 = rec[0], q4 = rec[1], i4 = rec[2];
+	more_points(ph.np, load_point);
+	pos_half_solve_rec(d, ph, side, rec, p4, q4, V3(i4));
 }
-SGP_DEV void solve_position_pair_at(const DV& d, uint32_t slot, int side, float4* rec, v3 ii)
+SGP_DEV void solve_position_pair_at(const DV& d, const ConstraintArrays& ca, uint32_t slot, int side, float4* rec, v3 ii)
 {
 	PosHalf ph;
-	pos_half_load(d, slot, side, con_npc(CUR(d), slot), ph);
+	pos_half_load(ca, slot, side, con_npc(ca, slot), ph);
 	pos_half_solve(d, ph, side, rec, ii);
 }
 // (velocity and position iterations: two neighbouring lanes per constraint; workgroups of four waves = 128 constraints.  Measured on config 3:

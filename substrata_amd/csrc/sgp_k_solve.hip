@@ -25,11 +25,11 @@ SGP_DEV float axis_jv(const BodyVel& A, const BodyVel& B, v3 r1, v3 r2, v3 axis)
 }
 
 struct PairCtx { uint2 ab; float im1, im2; sym33 I1, I2; BodyVel A, B; v3 n, t1, t2; float friction; int np; };
-template <int VS> SGP_DEV void load_pair(const DV& d, uint32_t slot, PairCtx& c, const float4* vel)
+template <int VS> SGP_DEV void load_pair(const DV& d, const ConstraintArrays& ca, uint32_t slot, PairCtx& c, const float4* vel)
 {
-	const uint4 hd = con_hdr(CUR(d), slot);
+	const uint4 hd = con_hdr(ca, slot);
 	c.ab = make_uint2(hd.x, hd.y);
-	const float4 nf = CUR(d).n_fric[slot];
+	const float4 nf = ca.n_fric[slot];
 	c.n = V3(nf); c.friction = nf.w;
 	c.np = (int)hd.z & 0xFF;
 	const float4 va = vel[VS * (size_t)c.ab.x], wa = vel[VS * (size_t)c.ab.x + 1];
@@ -41,6 +41,8 @@ template <int VS> SGP_DEV void load_pair(const DV& d, uint32_t slot, PairCtx& c,
 	c.B.lv = V3(vb); c.B.av = V3(wb);
 }
 
+template <int VS> SGP_DEV void load_pair(const DV& d, uint32_t slot, PairCtx& c, const float4* vel) { load_pair<VS>(d, CUR(d), slot, c, vel); }
+
 template <int VS> SGP_DEV void store_pair_vel(const PairCtx& c, float4* vel)
 {
 	if (c.im1 > 0.0f) { vel[VS * (size_t)c.ab.x] = F4(c.A.lv, c.im1); vel[VS * (size_t)c.ab.x + 1] = F4(c.A.av, 0.0f); }
@@ -51,18 +53,18 @@ template <int VS> SGP_DEV void store_pair_vel(const PairCtx& c, float4* vel)
 // n lam_n (+ t1 lam_t1 + t2 lam_t2 with friction), over the points the linear impulse P and the angular impulses A1 = sum r1 x j, A2 = sum r2 x j -- and each
 // body receives one velocity change, v -+ P / m, w -+ I^-1 A.  k_setup evaluates the same expressions on the same operands for the (body, colour) records
 // k_warm_bodies adds up, so this form (small worlds, the tail, the overflow colour) and that one give the same bits.
-template <int VS> SGP_DEV void warm_start_one_t(const DV& d, uint32_t slot, float4* vel)
+template <int VS> SGP_DEV void warm_start_one_t(const DV& d, const ConstraintArrays& ca, uint32_t slot, float4* vel)
 {
 	PairCtx c;
-	load_pair<VS>(d, slot, c, vel);
+	load_pair<VS>(d, ca, slot, c, vel);
 	c.t1 = v3_normalized_perpendicular(c.n);
 	c.t2 = v3_cross(c.n, c.t1);
 	v3 P = V3(0.0f, 0.0f, 0.0f), A1 = V3(0.0f, 0.0f, 0.0f), A2 = V3(0.0f, 0.0f, 0.0f);
 #pragma unroll
 	for (int i = 0; i < 4; ++i) {
 		if (i < c.np) {
-			const v3 r1 = V3(CUR(d).r1b[i][slot]), r2 = V3(CUR(d).r2e[i][slot]);
-			const float4 l = CUR(d).lam[i][slot];
+			const v3 r1 = V3(ca.r1b[i][slot]), r2 = V3(ca.r2e[i][slot]);
+			const float4 l = ca.lam[i][slot];
 			v3 j = v3_scale(c.n, l.x);
 			if (c.friction > 0.0f) { j = v3_add(j, v3_scale(c.t1, l.y)); j = v3_add(j, v3_scale(c.t2, l.z)); }
 			P = v3_add(P, j);
@@ -74,7 +76,7 @@ template <int VS> SGP_DEV void warm_start_one_t(const DV& d, uint32_t slot, floa
 	if (c.im2 > 0.0f) { c.B.lv = v3_add(c.B.lv, v3_scale(P, c.im2)); c.B.av = v3_add(c.B.av, sym33_mul(c.I2, A2)); }
 	store_pair_vel<VS>(c, vel);
 }
-SGP_DEV void warm_start_one(const DV& d, uint32_t slot) { warm_start_one_t<VEL_F4>(d, slot, d.vel); }
+SGP_DEV void warm_start_one(const DV& d, const ConstraintArrays& ca, uint32_t slot) { warm_start_one_t<VEL_F4>(d, ca, slot, d.vel); }
 
 // Warm start, one thread per BODY instead of one launch per colour.  What a constraint's warm start does to one of its bodies depends only on the constraint
 // (cached impulses, axes, lever arms) and on that body's inverse mass / inertia -- not on any velocity --, so what the colour-by-colour order does to one body
@@ -108,8 +110,7 @@ SGP_DEV void warm_body_one(const DV& d, uint32_t i)
 	rec[0] = F4(lv, im);
 	rec[1] = F4(av, 0.0f);
 }
-SGP_DEV void warm_start_one(const DV& d, uint32_t k);
-SGP_DEV uint32_t overflow_next(const DV& d, uint32_t first, uint32_t count, uint64_t& last, bool& have_last);
+SGP_DEV uint32_t overflow_next(const ConstraintArrays& ca, uint32_t first, uint32_t count, uint64_t& last, bool& have_last);
 __global__ void __launch_bounds__(TPB) k_warm_bodies(DV d)
 {
 	warm_body_one(d, blockIdx.x * TPB + threadIdx.x);
@@ -118,8 +119,9 @@ __global__ void __launch_bounds__(TPB) k_warm_bodies(DV d)
 	const uint32_t first = d.cstarts[SGP_OVERFLOW_COLOUR], count = d.cstarts[SGP_OVERFLOW_COLOUR + 1] - first;
 	if (count == 0u) return;                                    // (uniform over the grid)
 	if (!last_block(&d.ctr->tickets[1]) || threadIdx.x != 0) return;
+	const ConstraintArrays ca = cur_arrays(d, d.sp->parity);
 	uint64_t last = 0; bool have_last = false;
-	for (uint32_t it = 0; it < count; ++it) warm_start_one(d, overflow_next(d, first, count, last, have_last));
+	for (uint32_t it = 0; it < count; ++it) warm_start_one(d, ca, overflow_next(ca, first, count, last, have_last));
 }
 struct AxisRows { float4 c1, c2, i1, i2; };      // r1 x axis (w: bias), r2 x axis (w: effective mass), I1 (r1 x axis), I2 (r2 x axis)
 
@@ -148,11 +150,11 @@ SGP_DEV void rows_apply(BodyVel& A, BodyVel& B, float im1, float im2, v3 axis, c
 	}
 }
 
-SGP_DEV void solve_position_one(const DV& d, uint32_t slot)
+SGP_DEV void solve_position_one(const DV& d, const ConstraintArrays& ca, uint32_t slot)
 {
-	const uint4 hd = con_hdr(CUR(d), slot);
+	const uint4 hd = con_hdr(ca, slot);
 	const uint2 ab = make_uint2(hd.x, hd.y);
-	const float4 nf = CUR(d).n_fric[slot];
+	const float4 nf = ca.n_fric[slot];
 	const v3 nrm = V3(nf);
 	const int np = (int)hd.z & 0xFF;
 	// the pose records themselves (k_integrate_pose advanced them; the corrections are made in place) + the local inverse inertia
@@ -168,8 +170,8 @@ SGP_DEV void solve_position_one(const DV& d, uint32_t slot)
 #pragma unroll
 	for (int i = 0; i < 4; ++i) {
 		if (i >= np) continue;
-		const v3 p1 = v3_add(posA, m33_mul(RA, V3(CUR(d).loc1[i][slot])));
-		const v3 p2 = v3_add(posB, m33_mul(RB, V3(CUR(d).loc2[i][slot])));
+		const v3 p1 = v3_add(posA, m33_mul(RA, V3(ca.loc1[i][slot])));
+		const v3 p2 = v3_add(posB, m33_mul(RB, V3(ca.loc2[i][slot])));
 		float sep = v3_dot(v3_sub(p2, p1), nrm) + d.st.penetration_slop;
 		if (sep < 0.0f) {
 			sep = fmaxf(sep, -d.st.max_penetration_distance);
@@ -208,11 +210,15 @@ SGP_DEV void solve_position_one(const DV& d, uint32_t slot)
 // (the two leading pointer arguments repeat d.cstarts and d.sp: leading scalar arguments are PRELOADED into registers when the wave starts (kernarg preload,
 // -amdgpu-kernarg-preload-count), so the colour table and the buffer parity are requested at once, beside the fetch of the rest of the arguments instead of after it --
 // one dependent scalar fetch less on the chain of each of the ~110 colour launches of a step)
-template <int MODE, int ROWS = -1, int OCC = 1> __global__ void __launch_bounds__(MODE != 0 ? SOLVE_VEL_TPB : SOLVE_TPB, OCC) k_solve_colour(const uint32_t* cstarts_pre, StepParams* sp_pre, DV d_arg, int colour_arg)
+template <int MODE, int ROWS = -1, int OCC = 1> __global__ void __launch_bounds__(MODE != 0 ? SOLVE_VEL_TPB : SOLVE_TPB, OCC) k_solve_colour(const uint32_t* cstarts_pre, StepParams* sp_pre, int colour_arg, DV d_arg)
 {
 	DV d = d_arg; d.sp = sp_pre;
 	const int colour = colour_arg & 0xFF;
+	const uint32_t parity = sp_pre->parity;
 	const uint32_t first = cstarts_pre[colour], end = cstarts_pre[colour + 1];
+	// one wait for the parity, the colour's range, both buffers' pointers and the body records' base: nothing of it depends on anything else of it
+	keep_head<MODE == 2 ? CA_LOC : (MODE == 0 || ROWS == 2) ? CA_ARMS : CA_LAM>(d_arg, parity, first, end, MODE == 2 ? d_arg.pose : d_arg.vel, gridDim.x);
+	const ConstraintArrays ca = cur_arrays(d_arg, parity);      // (this step's buffers by value, resolved before any store)
 	if (MODE != 0) {
 		// velocity and position iterations: two neighbouring lanes per constraint
 		const int side = (int)(threadIdx.x & 1u);
@@ -221,12 +227,12 @@ template <int MODE, int ROWS = -1, int OCC = 1> __global__ void __launch_bounds_
 		// cache lines, and the same XCD meets the same rows again in the next pass.  (The grid is a multiple of eight: launch_solve_colour.)
 		const uint32_t bx = (colour_arg & SOLVE_XCD_CHUNKS) ? xcd_block() : blockIdx.x;      // (a colour of 200k constraints -- config 4 -- streams from HBM whatever the order, and lost 17 % with the chunks)
 		for (uint32_t k = first + ((bx * SOLVE_VEL_TPB + threadIdx.x) >> 1); k < end; k += gridDim.x * (SOLVE_VEL_TPB / 2)) {
-			if (MODE == 1) { if constexpr (ROWS == 2) solve_velocity_pair_norows<VEL_F4>(d, k, side, d.vel); else solve_velocity_pair_t<VEL_F4, ROWS>(d, k, side, d.vel); }
-			else solve_position_pair(d, k, side);
+			if (MODE == 1) { if constexpr (ROWS == 2) solve_velocity_pair_norows<VEL_F4>(d, ca, k, side, d.vel); else solve_velocity_pair_t<VEL_F4, ROWS>(d, ca, k, side, d.vel); }
+			else solve_position_pair(d, ca, k, side);
 		}
 		return;
 	}
-	for (uint32_t k = first + blockIdx.x * SOLVE_TPB + threadIdx.x; k < end; k += gridDim.x * SOLVE_TPB) warm_start_one(d, k);
+	for (uint32_t k = first + blockIdx.x * SOLVE_TPB + threadIdx.x; k < end; k += gridDim.x * SOLVE_TPB) warm_start_one(d, ca, k);
 }
 
 
@@ -236,22 +242,24 @@ template <int MODE, int ROWS = -1, int OCC = 1> __global__ void __launch_bounds_
 // every colour from first_colour on, it is also the catch-all when this step uses more colours than the plan expected.
 // k_solve_tail: warm start of the overflow colour (mode 0) and position iterations (mode 2), one thread per constraint;
 // k_solve_tail_vel: velocity iterations, two lanes per constraint (768 threads = 384 constraints per phase).
-SGP_DEV uint32_t overflow_next(const DV& d, uint32_t first, uint32_t count, uint64_t& last, bool& have_last)
+SGP_DEV uint32_t overflow_next(const ConstraintArrays& ca, uint32_t first, uint32_t count, uint64_t& last, bool& have_last)
 {
 	// the overflow constraint with the lowest priority above `last` (selection by scanning: the overflow colour is rare and short)
 	uint64_t best = ~0ull; uint32_t bslot = first;
 	for (uint32_t k = 0; k < count; ++k) {
-		const uint2 okab = con_ab(CUR(d), first + k); const uint64_t pr = sgp_mix64(((uint64_t)okab.x << 32) | okab.y);
+		const uint2 okab = con_ab(ca, first + k); const uint64_t pr = sgp_mix64(((uint64_t)okab.x << 32) | okab.y);
 		if ((!have_last || pr > last) && pr <= best) { best = pr; bslot = first + k; }
 	}
 	last = best; have_last = true;
 	return bslot;
 }
+SGP_DEV uint32_t overflow_next(const DV& d, uint32_t first, uint32_t count, uint64_t& last, bool& have_last) { return overflow_next(CUR(d), first, count, last, have_last); }
 
 __global__ void __launch_bounds__(512) k_solve_tail(DV d, int first_colour, int mode)
 {
 	// the colour table in LDS: one coalesced load instead of a dependent global load per (mostly empty) colour
 	__shared__ uint32_t cs[SGP_MAX_COLOURS + 1];
+	const ConstraintArrays ca = cur_arrays(d, d.sp->parity);
 	if (threadIdx.x <= SGP_MAX_COLOURS) cs[threadIdx.x] = d.cstarts[threadIdx.x];
 	__syncthreads();
 	if (cs[first_colour] == cs[SGP_MAX_COLOURS]) return;          // nothing from first_colour on (incl. the overflow colour)
@@ -259,7 +267,7 @@ __global__ void __launch_bounds__(512) k_solve_tail(DV d, int first_colour, int 
 		const uint32_t b = cs[c], e = cs[c + 1];
 		if (b == e) continue;
 		for (uint32_t k = b + threadIdx.x; k < e; k += 512) {
-			if (mode == 0) warm_start_one(d, k); else solve_position_one(d, k);
+			if (mode == 0) warm_start_one(d, ca, k); else solve_position_one(d, ca, k);
 		}
 		__syncthreads();      // workgroup scope is enough: all waves of the workgroup share one CU (one L1)
 	}
@@ -267,8 +275,8 @@ __global__ void __launch_bounds__(512) k_solve_tail(DV d, int first_colour, int 
 	if (count == 0 || threadIdx.x != 0) return;
 	uint64_t last = 0; bool have_last = false;
 	for (uint32_t it = 0; it < count; ++it) {
-		const uint32_t bslot = overflow_next(d, first, count, last, have_last);
-		if (mode == 0) warm_start_one(d, bslot); else solve_position_one(d, bslot);
+		const uint32_t bslot = overflow_next(ca, first, count, last, have_last);
+		if (mode == 0) warm_start_one(d, ca, bslot); else solve_position_one(d, ca, bslot);
 	}
 }
 
@@ -276,6 +284,7 @@ __global__ void __launch_bounds__(512) k_solve_tail(DV d, int first_colour, int 
 template <int ROWS> __global__ void __launch_bounds__(TAIL_VEL_TPB) k_solve_tail_vel(DV d, int first_colour)
 {
 	__shared__ uint32_t cs[SGP_MAX_COLOURS + 1];
+	const ConstraintArrays ca = cur_arrays(d, d.sp->parity);
 	if (threadIdx.x <= SGP_MAX_COLOURS) cs[threadIdx.x] = d.cstarts[threadIdx.x];
 	__syncthreads();
 	if (cs[first_colour] == cs[SGP_MAX_COLOURS]) return;
@@ -288,26 +297,26 @@ template <int ROWS> __global__ void __launch_bounds__(TAIL_VEL_TPB) k_solve_tail
 		const uint32_t slot = cs[first_colour] + pair;
 		const bool mine = pair < tail_n;
 		ConHalf h; int my_col = -1;
-		if (mine) { half_load<ROWS>(d, slot, side, h); my_col = (h.np_col >> 8) & 0xFF; }
+		if (mine) { half_load<ROWS>(d, ca, slot, side, h); my_col = (h.np_col >> 8) & 0xFF; }
 		for (int c = first_colour; c < SGP_OVERFLOW_COLOUR; ++c) {
 			if (cs[c] == cs[c + 1]) continue;
 			if (my_col == c) half_solve<VEL_F4>(h, side, d.vel, d.dbg_flags);
 			__syncthreads();
 		}
-		if (mine) half_store(d, slot, side, h);
+		if (mine) half_store(ca, slot, side, h);
 	} else
 	for (int c = first_colour; c < SGP_OVERFLOW_COLOUR; ++c) {
 		const uint32_t b = cs[c], e = cs[c + 1];
 		if (b == e) continue;
-		for (uint32_t k = b + pair; k < e; k += TAIL_VEL_TPB / 2) solve_velocity_pair_t<VEL_F4, ROWS>(d, k, side, d.vel);
+		for (uint32_t k = b + pair; k < e; k += TAIL_VEL_TPB / 2) solve_velocity_pair_t<VEL_F4, ROWS>(d, ca, k, side, d.vel);
 		__syncthreads();
 	}
 	const uint32_t first = cs[SGP_OVERFLOW_COLOUR], count = cs[SGP_OVERFLOW_COLOUR + 1] - first;
 	if (count == 0 || threadIdx.x >= 2) return;                   // lanes 0 and 1: the two sides of one constraint at a time
 	uint64_t last = 0; bool have_last = false;
 	for (uint32_t it = 0; it < count; ++it) {
-		const uint32_t bslot = overflow_next(d, first, count, last, have_last);
-		solve_velocity_pair_t<VEL_F4, ROWS>(d, bslot, side, d.vel);
+		const uint32_t bslot = overflow_next(ca, first, count, last, have_last);
+		solve_velocity_pair_t<VEL_F4, ROWS>(d, ca, bslot, side, d.vel);
 	}
 }
 #define HC_CLASSES 9                  // component size classes: 1 << class constraints
@@ -324,12 +333,13 @@ SGP_DEV bool hc_can_move(const DV& d, uint32_t body) { return d.vel[VEL_F4 * (si
 //     the slot list is cleared to "no constraint"
 __global__ void __launch_bounds__(TPB) k_hc_hook(DV d, int first_colour)
 {
+	const ConstraintArrays ca = cur_arrays(d, d.sp->parity);
 	const uint32_t b = d.cstarts[first_colour], e = d.cstarts[SGP_OVERFLOW_COLOUR];
 	const uint32_t tid = blockIdx.x * TPB + threadIdx.x, stride = gridDim.x * TPB;
 	const uint32_t lim = min(2u * (e - b) + HC_CLASSES * HC_WG_PAIRS, d.cap_hc_list);
 	for (uint32_t i = tid; i < lim; i += stride) d.hc_list[i] = HC_NONE;
 	for (uint32_t k = b + tid; k < e; k += stride) {
-		const uint2 ab = con_ab(CUR(d), k);
+		const uint2 ab = con_ab(ca, k);
 		if (!hc_can_move(d, ab.x) || !hc_can_move(d, ab.y)) continue;
 		uint32_t ra = uf_find(d.hc_root, ab.x), rb = uf_find(d.hc_root, ab.y);
 		while (ra != rb) {
@@ -349,21 +359,23 @@ SGP_DEV uint32_t hc_root_of(const DV& d, uint2 ab)
 // (2) size of every component, and each constraint's rank within its component
 __global__ void __launch_bounds__(TPB) k_hc_count(DV d, int first_colour)
 {
+	const ConstraintArrays ca = cur_arrays(d, d.sp->parity);
 	const uint32_t b = d.cstarts[first_colour], e = d.cstarts[SGP_OVERFLOW_COLOUR];
 	for (uint32_t k = b + blockIdx.x * TPB + threadIdx.x; k < e; k += gridDim.x * TPB) {
-		const uint32_t r = hc_root_of(d, con_ab(CUR(d), k));
+		const uint32_t r = hc_root_of(d, con_ab(ca, k));
 		d.hc_rank[k] = r == HC_NONE ? 0u : atomicAdd(&d.hc_count[r], 1u);
 	}
 }
 // (3) the first constraint of a component takes the component's place in its size class (one atomic per wave and class)
 __global__ void __launch_bounds__(TPB) k_hc_alloc(DV d, int first_colour)
 {
+	const ConstraintArrays ca = cur_arrays(d, d.sp->parity);
 	const uint32_t b = d.cstarts[first_colour], e = d.cstarts[SGP_OVERFLOW_COLOUR];
 	const int lane = (int)(threadIdx.x & 63u);
 	for (uint32_t k0 = b + blockIdx.x * TPB; k0 < e; k0 += gridDim.x * TPB) {          // (uniform per workgroup: the ballots below need whole waves)
 		const uint32_t k = k0 + threadIdx.x;
 		uint32_t r = HC_NONE, size = 0;
-		if (k < e && d.hc_rank[k] == 0u) { r = hc_root_of(d, con_ab(CUR(d), k)); if (r != HC_NONE) size = d.hc_count[r]; }
+		if (k < e && d.hc_rank[k] == 0u) { r = hc_root_of(d, con_ab(ca, k)); if (r != HC_NONE) size = d.hc_count[r]; }
 		const bool lead = r != HC_NONE;
 		int cls = -1;
 		if (lead) {
@@ -391,10 +403,11 @@ SGP_DEV uint32_t hc_class_first(const DV& d, int cls)
 // (4) every constraint goes to its component's place in the list (entry = lane pair of the solve launch), or is marked for the catch-all
 __global__ void __launch_bounds__(TPB) k_hc_scatter(DV d, int first_colour)
 {
+	const ConstraintArrays ca = cur_arrays(d, d.sp->parity);
 	const uint32_t b = d.cstarts[first_colour], e = d.cstarts[SGP_OVERFLOW_COLOUR];
 	if (blockIdx.x == 0 && threadIdx.x == 0) { d.ctr->hc_entries = hc_class_first(d, HC_CLASSES); d.ctr->hc_n = e - b; }
 	for (uint32_t k = b + blockIdx.x * TPB + threadIdx.x; k < e; k += gridDim.x * TPB) {
-		const uint32_t r = hc_root_of(d, con_ab(CUR(d), k));
+		const uint32_t r = hc_root_of(d, con_ab(ca, k));
 		const uint32_t place = r == HC_NONE ? HC_BIG : d.hc_base[r];
 		uint32_t at = HC_NONE;
 		if (place != HC_BIG) {
@@ -403,7 +416,7 @@ __global__ void __launch_bounds__(TPB) k_hc_scatter(DV d, int first_colour)
 		}
 		if (at < d.cap_hc_list) d.hc_list[at] = k;          // (the list has room for every constraint rounded up to its class: at is always inside)
 		else {
-			con_npc(CUR(d), k) |= NPCOL_CATCH_ALL;
+			con_npc(ca, k) |= NPCOL_CATCH_ALL;
 			const uint32_t bi = wave_alloc(&d.ctr->hc_n_big);
 			if (bi < HC_BIG_LIST) d.hc_big_list[bi] = k;          // (the catch-all walks this list instead of searching the colours for the flag)
 		}
@@ -415,19 +428,21 @@ __global__ void __launch_bounds__(TPB) k_hc_scatter(DV d, int first_colour)
 // a workgroup can hold?  Counts the constraints that would not (hc_probe_big); k_hc_init then resets the union-find for the real build.
 __global__ void __launch_bounds__(TPB) k_hc_init(DV d, int first_colour)
 {
+	const ConstraintArrays ca = cur_arrays(d, d.sp->parity);
 	const uint32_t b = d.cstarts[first_colour], e = d.cstarts[SGP_OVERFLOW_COLOUR];
 	for (uint32_t k = b + blockIdx.x * TPB + threadIdx.x; k < e; k += gridDim.x * TPB) {
-		const uint2 ab = con_ab(CUR(d), k);
+		const uint2 ab = con_ab(ca, k);
 		if (hc_can_move(d, ab.x)) { d.hc_root[ab.x] = ab.x; d.hc_count[ab.x] = 0u; }
 		if (hc_can_move(d, ab.y)) { d.hc_root[ab.y] = ab.y; d.hc_count[ab.y] = 0u; }
 	}
 }
 __global__ void __launch_bounds__(TPB) k_hc_probe(DV d, int first_colour)
 {
+	const ConstraintArrays ca = cur_arrays(d, d.sp->parity);
 	const uint32_t b = d.cstarts[first_colour], e = d.cstarts[SGP_OVERFLOW_COLOUR];
 	for (uint32_t k = b + blockIdx.x * TPB + threadIdx.x; k < e; k += gridDim.x * TPB) {
 		if (d.hc_rank[k] != 0u) continue;
-		const uint32_t r = hc_root_of(d, con_ab(CUR(d), k));
+		const uint32_t r = hc_root_of(d, con_ab(ca, k));
 		if (r == HC_NONE) continue;
 		const uint32_t size = d.hc_count[r];
 		if (size > (uint32_t)HC_WG_PAIRS) atomicAdd(&d.ctr->hc_probe_big, size);
@@ -438,6 +453,7 @@ __global__ void __launch_bounds__(TPB) k_hc_probe(DV d, int first_colour)
 //     holds one or two colours and runs one or two phases of the pass, instead of every wave running every phase for a few lanes each
 __global__ void __launch_bounds__(HC_WG_PAIRS) k_hc_sort(DV d)
 {
+	const ConstraintArrays ca = cur_arrays(d, d.sp->parity);
 	__shared__ uint32_t s_cnt[SGP_MAX_COLOURS], s_first[SGP_MAX_COLOURS];
 	__shared__ uint4 s_slot[HC_WG_PAIRS];
 	const uint32_t entries = d.ctr->hc_entries;
@@ -445,7 +461,7 @@ __global__ void __launch_bounds__(HC_WG_PAIRS) k_hc_sort(DV d)
 		if (threadIdx.x < SGP_MAX_COLOURS) s_cnt[threadIdx.x] = 0u;
 		__syncthreads();
 		const uint32_t slot = d.hc_list[e0 + threadIdx.x];
-		const uint4 hd = slot != HC_NONE ? con_hdr(CUR(d), slot) : make_uint4(0u, 0u, 0u, 0u);
+		const uint4 hd = slot != HC_NONE ? con_hdr(ca, slot) : make_uint4(0u, 0u, 0u, 0u);
 		const int npc = (int)hd.z;
 		const uint2 ab = make_uint2(hd.x, hd.y);
 		const int col = slot != HC_NONE ? ((npc >> 8) & 0xFF) : SGP_MAX_COLOURS - 1;      // (unused lane pairs last)
@@ -468,7 +484,7 @@ __global__ void __launch_bounds__(HC_WG_PAIRS) k_hc_sort(DV d)
 // A workgroup's components own their movable bodies, so their solver records live in LDS for the whole pass (read once, written once; a
 // colour phase is an LDS gather, the arithmetic and an LDS scatter): HC_TABLE hash slots keyed by body id, filled by the lanes themselves.
 #define HC_TABLE 1024                 // >= 2 x the bodies a workgroup can meet (one per lane)
-template <int MODE, int ROWS = -1> __global__ void __launch_bounds__(HC_TPB) k_solve_hc(const StepCounters* ctr_pre, const uint4* hc_entry_pre, DV d, int first_colour)      // (leading pointers: preloaded with the wave, k_solve_colour; `d` itself stays as passed -- the catch-all below takes it by reference, and a modified copy would live in scratch)
+template <int MODE, int ROWS = -1> __global__ void __launch_bounds__(HC_TPB) k_solve_hc(const StepCounters* ctr_pre, const uint4* hc_entry_pre, const StepParams* sp_pre, int first_colour, DV d)      // (leading arguments: preloaded with the wave, k_solve_colour; `d` itself stays as passed -- the catch-all below takes it by reference, and a modified copy would live in scratch)
 {
 	constexpr int RS = MODE == 1 ? 2 : 3;      // float4 per body: velocity half (lin + inverse mass, ang) / pose half (pos + inverse mass, rot, inertia)
 	__shared__ float4 s_rec[HC_TABLE * RS];
@@ -477,8 +493,16 @@ template <int MODE, int ROWS = -1> __global__ void __launch_bounds__(HC_TPB) k_s
 	__shared__ uint32_t s_ticket;
 	const int side = (int)(threadIdx.x & 1u);
 	const uint32_t pair = threadIdx.x >> 1;
+	const uint32_t parity = sp_pre->parity;
 	const uint32_t entries = ctr_pre->hc_entries;
 	const int n_colours = (int)ctr_pre->n_colours;
+	// (k_solve_colour: the buffer resolved once, before the first barrier and any store, under one wait -- except on the layouts with rows, where a constraint half
+	// already fills the register file: the resolved pointers cost scalar registers for the whole pass, and the spills of these instances grew with them)
+	constexpr bool RESOLVE = MODE == 2 || ROWS == 2;
+	if constexpr (RESOLVE) keep_head<MODE == 2 ? CA_LOC : CA_ARMS>(d, parity, entries, (uint32_t)n_colours, MODE == 2 ? d.pose : d.vel, gridDim.x);
+	ConstraintArrays resolved;
+	if constexpr (RESOLVE) resolved = cur_arrays(d, parity);
+	const auto ca = [&]() -> const ConstraintArrays& { if constexpr (RESOLVE) return resolved; else return CUR(d); };
 	for (uint32_t e0 = blockIdx.x * HC_WG_PAIRS; e0 < entries; e0 += gridDim.x * HC_WG_PAIRS) {
 		__syncthreads();      // (everyone is done with the previous round's table and mask)
 		for (uint32_t i = threadIdx.x; i < HC_TABLE; i += HC_TPB) s_key[i] = HC_NONE;
@@ -492,7 +516,7 @@ template <int MODE, int ROWS = -1> __global__ void __launch_bounds__(HC_TPB) k_s
 		if (mine) {
 			my_col = ((int)entry.y >> 8) & 0xFF;
 			body = side ? entry.w : entry.z;
-			if (MODE == 1) half_load_known<ROWS>(d, slot, side, (int)entry.y, body, h); else pos_half_load(d, slot, side, (int)entry.y, ph);
+			if (MODE == 1) half_load_known<ROWS>(d, ca(), slot, side, (int)entry.y, body, h); else pos_half_load(ca(), slot, side, (int)entry.y, ph);
 			if (side == 0) atomicOr(&s_present, 1ull << my_col);
 			// this body's LDS slot; the lane that claims it brings the record in
 			at = uf_prio(body) & (HC_TABLE - 1);
@@ -516,7 +540,7 @@ template <int MODE, int ROWS = -1> __global__ void __launch_bounds__(HC_TPB) k_s
 			if (my_col == c) { if (MODE == 1) half_solve<2>(h, side, s_rec, d.dbg_flags); else pos_half_solve(d, ph, side, s_rec + RS * at, V3(s_rec[RS * at + 2])); }
 			__syncthreads();
 		}
-		if (MODE == 1 && mine) half_store(d, slot, side, h);
+		if (MODE == 1 && mine) half_store(ca(), slot, side, h);
 		if (owner && s_rec[RS * at].w > 0.0f) {
 			float4* g = (MODE == 1 ? d.vel + VEL_F4 * (size_t)body : d.pose + POSE_F4 * (size_t)body);
 			g[0] = s_rec[RS * at]; g[1] = s_rec[RS * at + 1];
@@ -532,6 +556,7 @@ template <int MODE, int ROWS = -1> __global__ void __launch_bounds__(HC_TPB) k_s
 	if (s_ticket != gridDim.x - 1u) return;
 	if (threadIdx.x == 0) d.ctr->hc_done = 0u;      // for the next launch
 	__threadfence();          // what the other workgroups wrote (and this compute unit may still hold older copies of)
+	// (the rare path below looks the buffer up at each use, CUR(d): resolved pointers kept alive to here spill scalar registers in the pass above)
 	if (n_big != 0u && n_big <= (uint32_t)HC_BIG_LIST) {
 		// the constraints of the oversized components from their list, up to four per lane pair, colour by colour (constraints of one colour share no
 		// movable body: any order).  Searching every colour's whole range for the flag instead cost 140 us per pass for 288 constraints -- a step of
@@ -540,7 +565,7 @@ template <int MODE, int ROWS = -1> __global__ void __launch_bounds__(HC_TPB) k_s
 		for (uint32_t e = pair; e < n_big; e += HC_WG_PAIRS) { const uint32_t k = d.hc_big_list[e]; mine[cnt] = k; mcol[cnt] = (int)((con_npc(CUR(d), k) >> 8) & 0xFF); ++cnt; }
 		for (int c = first_colour; c < n_colours; ++c) {
 #pragma unroll
-			for (int j = 0; j < 4; ++j) if (j < cnt && mcol[j] == c) { if (MODE == 1) solve_velocity_pair_t<VEL_F4, ROWS>(d, mine[j], side, d.vel); else solve_position_pair(d, mine[j], side); }
+			for (int j = 0; j < 4; ++j) if (j < cnt && mcol[j] == c) { if (MODE == 1) solve_velocity_pair_t<VEL_F4, ROWS>(d, CUR(d), mine[j], side, d.vel); else solve_position_pair(d, CUR(d), mine[j], side); }
 			__syncthreads();
 		}
 	} else
@@ -548,15 +573,15 @@ template <int MODE, int ROWS = -1> __global__ void __launch_bounds__(HC_TPB) k_s
 		const uint32_t cb = d.cstarts[c], ce = d.cstarts[c + 1];
 		for (uint32_t k = cb + pair; k < ce; k += HC_WG_PAIRS) {
 			if (!(con_npc(CUR(d), k) & NPCOL_CATCH_ALL)) continue;
-			if (MODE == 1) solve_velocity_pair_t<VEL_F4, ROWS>(d, k, side, d.vel); else solve_position_pair(d, k, side);
+			if (MODE == 1) solve_velocity_pair_t<VEL_F4, ROWS>(d, CUR(d), k, side, d.vel); else solve_position_pair(d, CUR(d), k, side);
 		}
 		__syncthreads();
 	}
 	if (ocount == 0u || threadIdx.x >= 2u) return;               // lanes 0 and 1: the two sides of one constraint at a time
 	uint64_t last = 0; bool have_last = false;
 	for (uint32_t it = 0; it < ocount; ++it) {
-		const uint32_t bslot = overflow_next(d, ofirst, ocount, last, have_last);
-		if (MODE == 1) solve_velocity_pair_t<VEL_F4, ROWS>(d, bslot, side, d.vel); else solve_position_pair(d, bslot, side);
+		const uint32_t bslot = overflow_next(CUR(d), ofirst, ocount, last, have_last);
+		if (MODE == 1) solve_velocity_pair_t<VEL_F4, ROWS>(d, CUR(d), bslot, side, d.vel); else solve_position_pair(d, CUR(d), bslot, side);
 	}
 }
 
@@ -571,6 +596,7 @@ __global__ void __launch_bounds__(SMALL_TPB) k_solve_small(DV d, int warm_start,
 {
 	__shared__ float4 sv[2 * SMALL_LDS_BODIES];        // 64 KB: [lin vel, effective inverse mass][ang vel, -] per body slot
 	__shared__ uint32_t cs[SGP_MAX_COLOURS + 1];
+	const ConstraintArrays ca = cur_arrays(d, d.sp->parity);
 	const uint32_t n = min(d.sp->n_slots, (uint32_t)SMALL_LDS_BODIES);
 	if (threadIdx.x <= SGP_MAX_COLOURS) cs[threadIdx.x] = d.cstarts[threadIdx.x];
 	for (uint32_t i = threadIdx.x; i < 2 * n; i += SMALL_TPB) sv[i] = d.vel[VEL_F4 * (size_t)(i >> 1) + (i & 1u)];
@@ -588,12 +614,12 @@ __global__ void __launch_bounds__(SMALL_TPB) k_solve_small(DV d, int warm_start,
 			for (int c = 0; c < SGP_OVERFLOW_COLOUR; ++c) {
 				const uint32_t b = cs[c], e = cs[c + 1];
 				if (b == e) continue;
-				if (side == 0 && slot >= b && slot < e) warm_start_one_t<2>(d, slot, sv);      // (the warm start is one thread per constraint)
+				if (side == 0 && slot >= b && slot < e) warm_start_one_t<2>(d, ca, slot, sv);      // (the warm start is one thread per constraint)
 				__syncthreads();
 			}
 		}
 		ConHalf h; int my_col = -1;
-		if (mine) { half_load<0>(d, slot, side, h); my_col = (h.np_col >> 8) & 0xFF; }
+		if (mine) { half_load<0>(d, ca, slot, side, h); my_col = (h.np_col >> 8) & 0xFF; }
 		for (int pass = 0; pass < iterations; ++pass) {
 			for (int c = 0; c < SGP_OVERFLOW_COLOUR; ++c) {
 				if (cs[c] == cs[c + 1]) continue;
@@ -601,15 +627,15 @@ __global__ void __launch_bounds__(SMALL_TPB) k_solve_small(DV d, int warm_start,
 				__syncthreads();
 			}
 		}
-		if (mine) half_store(d, slot, side, h);
+		if (mine) half_store(ca, slot, side, h);
 	} else
 	if (cs[0] != cs[SGP_MAX_COLOURS]) {
 		for (int pass = warm_start ? -1 : 0; pass < iterations; ++pass) {
 			for (int c = 0; c < SGP_OVERFLOW_COLOUR; ++c) {
 				const uint32_t b = cs[c], e = cs[c + 1];
 				if (b == e) continue;
-				if (pass < 0) { for (uint32_t k = b + threadIdx.x; k < e; k += SMALL_TPB) warm_start_one_t<2>(d, k, sv); }
-				else { for (uint32_t k = b + pair; k < e; k += SMALL_TPB / 2) solve_velocity_pair_t<2, 0>(d, k, side, sv); }
+				if (pass < 0) { for (uint32_t k = b + threadIdx.x; k < e; k += SMALL_TPB) warm_start_one_t<2>(d, ca, k, sv); }
+				else { for (uint32_t k = b + pair; k < e; k += SMALL_TPB / 2) solve_velocity_pair_t<2, 0>(d, ca, k, side, sv); }
 				__syncthreads();
 			}
 			const uint32_t first = cs[SGP_OVERFLOW_COLOUR], count = cs[SGP_OVERFLOW_COLOUR + 1] - first;
@@ -617,8 +643,8 @@ __global__ void __launch_bounds__(SMALL_TPB) k_solve_small(DV d, int warm_start,
 				if (threadIdx.x < 2) {                     // lanes 0 and 1: the two sides of one constraint at a time (the warm start: lane 0 alone)
 					uint64_t last = 0; bool have_last = false;
 					for (uint32_t it = 0; it < count; ++it) {
-						const uint32_t bslot = overflow_next(d, first, count, last, have_last);
-						if (pass < 0) { if (side == 0) warm_start_one_t<2>(d, bslot, sv); } else solve_velocity_pair_t<2, 0>(d, bslot, side, sv);
+						const uint32_t bslot = overflow_next(ca, first, count, last, have_last);
+						if (pass < 0) { if (side == 0) warm_start_one_t<2>(d, ca, bslot, sv); } else solve_velocity_pair_t<2, 0>(d, ca, bslot, side, sv);
 					}
 				}
 				__syncthreads();
@@ -637,27 +663,27 @@ __global__ void __launch_bounds__(SMALL_TPB) k_solve_small(DV d, int warm_start,
 // single-workgroup kernels (tail colours, small worlds) keep the record across their colour phases / iterations instead of re-reading it.
 struct ConReg { uint2 ab; float4 nf; int np_col; AxisRows rn[4], rt1[4], rt2[4]; float4 lam[4]; };
 
-SGP_DEV void con_load(const DV& d, uint32_t slot, ConReg& r)
+SGP_DEV void con_load(const DV& d, const ConstraintArrays& ca, uint32_t slot, ConReg& r)
 {
-	const uint4 hd = con_hdr(CUR(d), slot);
+	const uint4 hd = con_hdr(ca, slot);
 	r.ab = make_uint2(hd.x, hd.y);
-	r.nf = CUR(d).n_fric[slot];
+	r.nf = ca.n_fric[slot];
 	r.np_col = (int)hd.z;
 	const int np = r.np_col & 0xFF;
 #pragma unroll
 	for (int i = 0; i < 4; ++i) {
 		if (i < np) {
 			r.rn[i] = load_axis_rows(d, slot, i, 0); r.rt1[i] = load_axis_rows(d, slot, i, 1); r.rt2[i] = load_axis_rows(d, slot, i, 2);
-			r.lam[i] = CUR(d).lam[i][slot];
+			r.lam[i] = ca.lam[i][slot];
 		}
 	}
 }
 
-SGP_DEV void con_store(const DV& d, uint32_t slot, const ConReg& r)
+SGP_DEV void con_store(const ConstraintArrays& ca, uint32_t slot, const ConReg& r)
 {
 	const int np = r.np_col & 0xFF;
 #pragma unroll
-	for (int i = 0; i < 4; ++i) { if (i < np) CUR(d).lam[i][slot] = r.lam[i]; }
+	for (int i = 0; i < 4; ++i) { if (i < np) ca.lam[i][slot] = r.lam[i]; }
 }
 
 template <int VS> SGP_DEV void con_solve_velocity(ConReg& r, float4* vel, uint32_t dbg = 0)
@@ -701,12 +727,12 @@ template <int VS> SGP_DEV void con_solve_velocity(ConReg& r, float4* vel, uint32
 	if (im2 > 0.0f) { vel[VS * (size_t)ab.y] = F4(B.lv, im2); vel[VS * (size_t)ab.y + 1] = F4(B.av, 0.0f); }
 }
 
-template <int VS> SGP_DEV void solve_velocity_one_t(const DV& d, uint32_t slot, float4* vel)
+template <int VS> SGP_DEV void solve_velocity_one_t(const DV& d, const ConstraintArrays& ca, uint32_t slot, float4* vel)
 {
 	ConReg r;
-	con_load(d, slot, r);
+	con_load(d, ca, slot, r);
 	con_solve_velocity<VS>(r, vel, d.dbg_flags);
-	con_store(d, slot, r);
+	con_store(ca, slot, r);
 }
 __global__ void __launch_bounds__(512) k_solve_small_single(DV d, int warm_start, int iterations)
 {
@@ -727,12 +753,12 @@ __global__ void __launch_bounds__(512) k_solve_small_single(DV d, int warm_start
 			for (int c = 0; c < SGP_OVERFLOW_COLOUR; ++c) {
 				const uint32_t b = cs[c], e = cs[c + 1];
 				if (b == e) continue;
-				if (slot >= b && slot < e) warm_start_one_t<2>(d, slot, sv);
+				if (slot >= b && slot < e) warm_start_one_t<2>(d, CUR(d), slot, sv);
 				__syncthreads();
 			}
 		}
 		ConReg r; int my_col = -1;
-		if (mine) { con_load(d, slot, r); my_col = (r.np_col >> 8) & 0xFF; }
+		if (mine) { con_load(d, CUR(d), slot, r); my_col = (r.np_col >> 8) & 0xFF; }
 		for (int pass = 0; pass < iterations; ++pass) {
 			for (int c = 0; c < SGP_OVERFLOW_COLOUR; ++c) {
 				if (cs[c] == cs[c + 1]) continue;
@@ -740,7 +766,7 @@ __global__ void __launch_bounds__(512) k_solve_small_single(DV d, int warm_start
 				__syncthreads();
 			}
 		}
-		if (mine) con_store(d, slot, r);
+		if (mine) con_store(CUR(d), slot, r);
 	} else
 	if (cs[0] != cs[SGP_MAX_COLOURS]) {
 		for (int pass = warm_start ? -1 : 0; pass < iterations; ++pass) {
@@ -748,7 +774,7 @@ __global__ void __launch_bounds__(512) k_solve_small_single(DV d, int warm_start
 				const uint32_t b = cs[c], e = cs[c + 1];
 				if (b == e) continue;
 				for (uint32_t k = b + threadIdx.x; k < e; k += 512) {
-					if (pass < 0) warm_start_one_t<2>(d, k, sv); else solve_velocity_one_t<2>(d, k, sv);
+					if (pass < 0) warm_start_one_t<2>(d, CUR(d), k, sv); else solve_velocity_one_t<2>(d, CUR(d), k, sv);
 				}
 				__syncthreads();
 			}
@@ -763,7 +789,7 @@ __global__ void __launch_bounds__(512) k_solve_small_single(DV d, int warm_start
 							if ((!have_last || pr > last) && pr <= best) { best = pr; bslot = first + k; }
 						}
 						last = best; have_last = true;
-						if (pass < 0) warm_start_one_t<2>(d, bslot, sv); else solve_velocity_one_t<2>(d, bslot, sv);
+						if (pass < 0) warm_start_one_t<2>(d, CUR(d), bslot, sv); else solve_velocity_one_t<2>(d, CUR(d), bslot, sv);
 					}
 				}
 				__syncthreads();
@@ -792,15 +818,15 @@ void launch_solve_colour(const DV& d, int colour, uint32_t est, int mode, hipStr
 	if (blocks > 8192) blocks = 8192;
 	if (mode != 0) blocks = (blocks + 7u) & ~7u;      // (XCD-contiguous chunks: k_solve_colour)
 	if (mode != 0 && est >= 8192u && est <= 65536u) colour |= SOLVE_XCD_CHUNKS;      // (the colour's bodies and rows then fit the eight L2s)
-	if (mode == 0) hipLaunchKernelGGL(k_solve_colour<0>, dim3(blocks), dim3(SOLVE_TPB), 0, s, (const uint32_t*)d.cstarts, d.sp, d, colour);
+	if (mode == 0) hipLaunchKernelGGL(k_solve_colour<0>, dim3(blocks), dim3(SOLVE_TPB), 0, s, (const uint32_t*)d.cstarts, d.sp, colour, d);
 	else if (mode == 1) {
 		const bool many = est > SOLVE_MANY_MIN;
-		if (compact_rows == 2) hipLaunchKernelGGL((k_solve_colour<1, 2>), dim3(blocks), dim3(SOLVE_VEL_TPB), 0, s, (const uint32_t*)d.cstarts, d.sp, d, colour);      // (108 VGPRs: four waves per SIMD as it is, solve_velocity_pair_norows; five spill and lose)
-		else if (compact_rows) { if (many) hipLaunchKernelGGL((k_solve_colour<1, 1, SOLVE_MANY_OCC>), dim3(blocks), dim3(SOLVE_VEL_TPB), 0, s, (const uint32_t*)d.cstarts, d.sp, d, colour); else hipLaunchKernelGGL((k_solve_colour<1, 1>), dim3(blocks), dim3(SOLVE_VEL_TPB), 0, s, (const uint32_t*)d.cstarts, d.sp, d, colour); }
-		else hipLaunchKernelGGL((k_solve_colour<1, 0>), dim3(blocks), dim3(SOLVE_VEL_TPB), 0, s, (const uint32_t*)d.cstarts, d.sp, d, colour);
+		if (compact_rows == 2) hipLaunchKernelGGL((k_solve_colour<1, 2>), dim3(blocks), dim3(SOLVE_VEL_TPB), 0, s, (const uint32_t*)d.cstarts, d.sp, colour, d);      // (108 VGPRs: four waves per SIMD as it is, solve_velocity_pair_norows; five spill and lose)
+		else if (compact_rows) { if (many) hipLaunchKernelGGL((k_solve_colour<1, 1, SOLVE_MANY_OCC>), dim3(blocks), dim3(SOLVE_VEL_TPB), 0, s, (const uint32_t*)d.cstarts, d.sp, colour, d); else hipLaunchKernelGGL((k_solve_colour<1, 1>), dim3(blocks), dim3(SOLVE_VEL_TPB), 0, s, (const uint32_t*)d.cstarts, d.sp, colour, d); }
+		else hipLaunchKernelGGL((k_solve_colour<1, 0>), dim3(blocks), dim3(SOLVE_VEL_TPB), 0, s, (const uint32_t*)d.cstarts, d.sp, colour, d);
 	}
-	else if (est > SOLVE_MANY_MIN) hipLaunchKernelGGL((k_solve_colour<2, -1, SOLVE_MANY_OCC>), dim3(blocks), dim3(SOLVE_VEL_TPB), 0, s, (const uint32_t*)d.cstarts, d.sp, d, colour);
-	else hipLaunchKernelGGL(k_solve_colour<2>, dim3(blocks), dim3(SOLVE_VEL_TPB), 0, s, (const uint32_t*)d.cstarts, d.sp, d, colour);
+	else if (est > SOLVE_MANY_MIN) hipLaunchKernelGGL((k_solve_colour<2, -1, SOLVE_MANY_OCC>), dim3(blocks), dim3(SOLVE_VEL_TPB), 0, s, (const uint32_t*)d.cstarts, d.sp, colour, d);
+	else hipLaunchKernelGGL(k_solve_colour<2>, dim3(blocks), dim3(SOLVE_VEL_TPB), 0, s, (const uint32_t*)d.cstarts, d.sp, colour, d);
 }
 void launch_warm_bodies(const DV& d, uint32_t nb, hipStream_t s) { hipLaunchKernelGGL(k_warm_bodies, dim3(blocks_for(nb)), dim3(TPB), 0, s, d); }
 void launch_solve_tail(const DV& d, int first_colour, int mode, hipStream_t s, int compact_rows)
@@ -834,11 +860,11 @@ void launch_solve_hc(const DV& d, int first_colour, uint32_t est, int mode, hipS
 	// list entries: a component of n constraints takes the next power of two (< 2 n), plus the padding of the classes
 	const uint32_t blocks = std::max(1u, std::min(2048u, (2u * est + HC_CLASSES * HC_WG_PAIRS) / HC_WG_PAIRS));
 	if (mode == 1) {
-		if (compact_rows == 2) hipLaunchKernelGGL((k_solve_hc<1, 2>), dim3(blocks), dim3(HC_TPB), 0, s, (const StepCounters*)d.ctr, (const uint4*)d.hc_entry, d, first_colour);
-		else if (compact_rows) hipLaunchKernelGGL((k_solve_hc<1, 1>), dim3(blocks), dim3(HC_TPB), 0, s, (const StepCounters*)d.ctr, (const uint4*)d.hc_entry, d, first_colour);
-		else hipLaunchKernelGGL((k_solve_hc<1, 0>), dim3(blocks), dim3(HC_TPB), 0, s, (const StepCounters*)d.ctr, (const uint4*)d.hc_entry, d, first_colour);
+		if (compact_rows == 2) hipLaunchKernelGGL((k_solve_hc<1, 2>), dim3(blocks), dim3(HC_TPB), 0, s, (const StepCounters*)d.ctr, (const uint4*)d.hc_entry, (const StepParams*)d.sp, first_colour, d);
+		else if (compact_rows) hipLaunchKernelGGL((k_solve_hc<1, 1>), dim3(blocks), dim3(HC_TPB), 0, s, (const StepCounters*)d.ctr, (const uint4*)d.hc_entry, (const StepParams*)d.sp, first_colour, d);
+		else hipLaunchKernelGGL((k_solve_hc<1, 0>), dim3(blocks), dim3(HC_TPB), 0, s, (const StepCounters*)d.ctr, (const uint4*)d.hc_entry, (const StepParams*)d.sp, first_colour, d);
 	}
-	else hipLaunchKernelGGL((k_solve_hc<2, -1>), dim3(blocks), dim3(HC_TPB), 0, s, (const StepCounters*)d.ctr, (const uint4*)d.hc_entry, d, first_colour);
+	else hipLaunchKernelGGL((k_solve_hc<2, -1>), dim3(blocks), dim3(HC_TPB), 0, s, (const StepCounters*)d.ctr, (const uint4*)d.hc_entry, (const StepParams*)d.sp, first_colour, d);
 }
 void launch_solve_small(const DV& d, int warm_start, int iterations, int lane_pairs, hipStream_t s)
 {

@@ -522,19 +522,22 @@ template <int MODE> __global__ void __launch_bounds__(VEH_SOLVE_TPB) k_vehicle_s
 // The first contact colour of a velocity / position pass with the vehicles' rows in the same launch: no contact of a chassis sits in colour 0
 // (chassis_colours), so the two touch disjoint bodies and the pass order "vehicles, then the contact colours" holds without a launch of
 // its own.  The vehicle workgroups come first in the grid: they are the longer chains.
-template <int MODE, int ROWS = -1> __global__ void __launch_bounds__(SOLVE_VEL_TPB) k_solve_colour_veh(DV d, int colour_arg, uint32_t veh_blocks)
+template <int MODE, int ROWS = -1> __global__ void __launch_bounds__(SOLVE_VEL_TPB) k_solve_colour_veh(const uint32_t* cstarts_pre, const StepParams* sp_pre, int colour_arg, uint32_t veh_blocks, DV d)      // (leading arguments: preloaded with the wave, k_solve_colour)
 {
 	const int colour = colour_arg & 0xFF;
 	if (blockIdx.x < veh_blocks) {
 		veh_block_solve<MODE>(d, blockIdx.x, veh_blocks);
 		return;
 	}
-	const uint32_t first = d.cstarts[colour], end = d.cstarts[colour + 1];
+	const uint32_t parity = sp_pre->parity;
+	const uint32_t first = cstarts_pre[colour], end = cstarts_pre[colour + 1];
+	keep_head<MODE == 2 ? CA_LOC : ROWS == 2 ? CA_ARMS : CA_LAM>(d, parity, first, end, MODE == 2 ? d.pose : d.vel, gridDim.x);      // (k_solve_colour: one wait)
+	const ConstraintArrays ca = cur_arrays(d, parity);
 	const int side = (int)(threadIdx.x & 1u);
 	const uint32_t cb = blockIdx.x - veh_blocks, cg = gridDim.x - veh_blocks;      // (the colour's workgroups: XCD-contiguous chunks as in k_solve_colour; cg is a multiple of eight)
 	const uint32_t bx = (colour_arg & SOLVE_XCD_CHUNKS) ? (cb & 7u) * (cg >> 3) + (cb >> 3) : cb;
 	for (uint32_t k = first + ((bx * SOLVE_VEL_TPB + threadIdx.x) >> 1); k < end; k += cg * (SOLVE_VEL_TPB / 2)) {
-		if (MODE == 1) solve_velocity_pair_t<VEL_F4, ROWS>(d, k, side, d.vel); else solve_position_pair(d, k, side);
+		if (MODE == 1) solve_velocity_pair_t<VEL_F4, ROWS>(d, ca, k, side, d.vel); else solve_position_pair(d, ca, k, side);
 	}
 }
 void launch_solve_colour_veh(const DV& d, int colour, uint32_t est, int mode, hipStream_t s, int compact_rows)
@@ -545,11 +548,11 @@ void launch_solve_colour_veh(const DV& d, int colour, uint32_t est, int mode, hi
 	if (est >= 8192u && est <= 65536u) colour |= SOLVE_XCD_CHUNKS;
 	const uint32_t vb = (d.n_vehicles * 4u + SOLVE_VEL_TPB - 1) / SOLVE_VEL_TPB;
 	if (mode == 1) {
-		if (compact_rows == 2) hipLaunchKernelGGL((k_solve_colour_veh<1, 2>), dim3(vb + blocks), dim3(SOLVE_VEL_TPB), 0, s, d, colour, vb);
-		else if (compact_rows) hipLaunchKernelGGL((k_solve_colour_veh<1, 1>), dim3(vb + blocks), dim3(SOLVE_VEL_TPB), 0, s, d, colour, vb);
-		else hipLaunchKernelGGL((k_solve_colour_veh<1, 0>), dim3(vb + blocks), dim3(SOLVE_VEL_TPB), 0, s, d, colour, vb);
+		if (compact_rows == 2) hipLaunchKernelGGL((k_solve_colour_veh<1, 2>), dim3(vb + blocks), dim3(SOLVE_VEL_TPB), 0, s, (const uint32_t*)d.cstarts, (const StepParams*)d.sp, colour, vb, d);
+		else if (compact_rows) hipLaunchKernelGGL((k_solve_colour_veh<1, 1>), dim3(vb + blocks), dim3(SOLVE_VEL_TPB), 0, s, (const uint32_t*)d.cstarts, (const StepParams*)d.sp, colour, vb, d);
+		else hipLaunchKernelGGL((k_solve_colour_veh<1, 0>), dim3(vb + blocks), dim3(SOLVE_VEL_TPB), 0, s, (const uint32_t*)d.cstarts, (const StepParams*)d.sp, colour, vb, d);
 	}
-	else hipLaunchKernelGGL((k_solve_colour_veh<2, -1>), dim3(vb + blocks), dim3(SOLVE_VEL_TPB), 0, s, d, colour, vb);
+	else hipLaunchKernelGGL((k_solve_colour_veh<2, -1>), dim3(vb + blocks), dim3(SOLVE_VEL_TPB), 0, s, (const uint32_t*)d.cstarts, (const StepParams*)d.sp, colour, vb, d);
 }
 void launch_vehicle_pre(const DV& d, bool cylinder_testers, hipStream_t s)
 {
