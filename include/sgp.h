@@ -365,7 +365,8 @@ const char* sgp_kernel_class_name(int k);
 /* sizeof() of ABI struct number `which` (order: settings, world_desc, body_desc, body_state, body_event, contact_event,
  * ray, hit, step_stats, step_profile, ghost_record, vehicle_desc, vehicle_input, vehicle_state, hull_info, capsule_query,
  * query_contact, mesh_info, heightfield_desc, checkpoint_info, shape_query, -- 21 is not used and stays -1 --, shape_cast, cast_hit,
- * -- 24 is not used and stays -1 --, character_desc, character_input, character_state, character_contact) so bindings can verify their layout. */
+ * -- 24 is not used and stays -1 --, character_desc, character_input, character_state, character_contact, -- 29 is not used and stays -1 --,
+ * particle, particle_state, particle_event) so bindings can verify their layout. */
 int  sgp_abi_sizeof(int which);
 /* activated_obs / newly_activated_obs maintenance + listener callbacks (PhysicsWorld.h:194-200). */
 int  sgp_world_drain_events(sgp_world* w, int kind, void* out, uint32_t cap, uint32_t* n_out);
@@ -689,6 +690,82 @@ int  sgp_characters_get_states(sgp_characters* cs, uint32_t first, uint32_t n, s
 /* The contact-added records since the last drain, ascending character, then order of discovery; *n_out = how many were pending
  * (<= cap are written; all are consumed).  A character holds at most 32 between drains. */
 int  sgp_characters_drain_contacts(sgp_characters* cs, sgp_character_contact* out, uint32_t cap, uint32_t* n_out);
+
+/* ---- batched point particles (ParticleManager, gui_client/ParticleManager.cpp) -----------------------
+ * A batch of point particles that belongs to one world and lives on the device.  sgp_particles_update runs ParticleManager::think
+ * (ParticleManager.cpp:145-274) for every live particle on the world's stream -- one ray along the velocity for dt, answered by the very
+ * function sgp_raycast runs per ray; reflection and restitution on a hit; water, gravity (the reference's literal 9.81) and drag; the
+ * fade and growth of the sprite; removal of the dead -- with the fp32 expressions of the reference in its order (docs/CONTRACT.md,
+ * "Particles") and returns without waiting.  Any body answers the ray: the facade's traceRay treats a body without userdata as a miss,
+ * but every body the facade creates carries its object, so the two agree.  Particles never act on bodies or on each other.
+ * Departures from the reference (docs/GAPS.md): the dead are removed by a STABLE compaction (survivors keep their order; the reference
+ * swaps with the last), and a full batch replaces its particles in round-robin slot order (the reference picks a random victim).
+ * A batch holds no state that a world checkpoint captures.  In a tiled world particles see ghost bodies as bodies; nothing is exchanged. */
+typedef struct sgp_particles sgp_particles;
+#define SGP_PARTICLE_DIE_ON_HIT    1u   /* Particle::die_when_hit_surface (ParticleManager.cpp:189-190,198-206) */
+#define SGP_PARTICLE_EV_DIED       1u   /* cur_opacity <= 0 after the update (ParticleManager.cpp:259-267): the particle is gone          */
+#define SGP_PARTICLE_EV_FOAM       2u   /* addFoamDecal (ParticleManager.cpp:198-206) at (pos.x, pos.y, water_z) with width foam_width    */
+#define SGP_PARTICLE_EV_REPLACED   4u   /* overwritten by a newcomer of a full batch (ParticleManager.cpp:91-96)                          */
+#define SGP_PARTICLES_MAX_CAPACITY (1u << 20)
+/* What the reference's Particle carries for the simulation (ParticleManager.h:25-60).  Colour, theta and the sprite type are render-only
+ * and stay with the caller, keyed by `tag`, which stands for the caller's gl_ob. */
+typedef struct sgp_particle {
+	float    pos[3];
+	float    vel[3];
+	float    area;                 /* cross-sectional area (m^2): 1e-6        */
+	float    mass;                 /* 1e-6; must be > 0                       */
+	float    restitution;          /* 0.5                                     */
+	float    width;                /* 1                                       */
+	float    dwidth_dt;            /* 0.5                                     */
+	float    opacity;              /* cur_opacity: 1                          */
+	float    dopacity_dt;          /* -0.3                                    */
+	uint32_t flags;                /* SGP_PARTICLE_DIE_ON_HIT                 */
+	uint64_t tag;
+} sgp_particle;
+/* A live particle as sgp_particles_read reports it: what updateObjectTransformData needs (ParticleManager.cpp:250-253), and the rest of the moving state */
+typedef struct sgp_particle_state {
+	float    pos[3];
+	float    width;
+	float    vel[3];
+	float    opacity;
+	uint64_t tag;
+	uint32_t flags;
+	uint32_t reserved_;
+} sgp_particle_state;
+typedef struct sgp_particle_event {
+	uint64_t tag;
+	uint32_t kind;                 /* SGP_PARTICLE_EV_* bits                                                            */
+	float    pos[3];               /* of the particle when the event was raised (after the update that raised it)       */
+	float    width;                /* likewise                                                                          */
+	float    foam_width;           /* FOAM: the decal's width = the particle's width BEFORE this update's growth; else 0 */
+} sgp_particle_event;
+/* The defaults of Particle() (ParticleManager.h:35-36); pos, vel, flags and tag are zero. */
+void sgp_default_particle(sgp_particle* out);
+/* capacity in 1 .. SGP_PARTICLES_MAX_CAPACITY (the reference's MAX_NUM_PARTICLES is 2048, ParticleManager.cpp:88); event_capacity: event
+ * records the batch holds between two drains (0: events are only counted). */
+int  sgp_particles_create(sgp_world* w, uint32_t capacity, uint32_t event_capacity, sgp_particles** out);
+/* After sgp_world_destroy of its world this still frees the batch and returns SGP_OK; every other call on such a batch is SGP_ERR_INVALID. */
+int  sgp_particles_destroy(sgp_particles* ps);
+/* addParticle (ParticleManager.cpp:84-142), n at a time: enqueues an append behind the live particles and returns without waiting (the
+ * host need not know the live count).  Newcomers that do not fit replace existing particles at slots cursor++ % capacity of a cursor
+ * that lives on the device (ParticleManager.cpp:91-96 picks rng.nextUInt); every replaced particle raises a REPLACED event, in newcomer
+ * order.  SGP_ERR_INVALID, with nothing added, for a non-finite pos / vel / scalar, mass <= 0 or an unknown flag; SGP_ERR_CAPACITY for
+ * n > capacity. */
+int  sgp_particles_add(sgp_particles* ps, const sgp_particle* particles, uint32_t n);
+/* think(dt) (ParticleManager.cpp:145-274): flushes pending body edits, makes the query grid valid and parks the resident ray server (as
+ * a batched sgp_raycast does), enqueues the update and returns.  No wait, no copy, no allocation; no body and nothing a step reads is
+ * altered.  Water is the world's (sgp_world_set_water).  dt must be finite and >= 0. */
+int  sgp_particles_update(sgp_particles* ps, float dt);
+/* Waits for what is in flight, then writes the live particles in slot order.  *n_out = the live count; it may exceed cap (then only
+ * the first cap are written). */
+int  sgp_particles_read(sgp_particles* ps, sgp_particle_state* out, uint32_t cap, uint32_t* n_out);
+/* The events since the last drain, in the order of the calls that raised them; within one update in ascending slot order, within one
+ * add in newcomer order.  A particle that dies in the water raises ONE record with DIED | FOAM.  *n_out = records held (<= cap are
+ * written; all are consumed), *n_dropped = events that did not fit event_capacity since the last drain. */
+int  sgp_particles_drain_events(sgp_particles* ps, sgp_particle_event* out, uint32_t cap, uint32_t* n_out, uint32_t* n_dropped);
+/* clearParticles (ParticleManager.cpp:74-81): no particle is live afterwards and the replacement cursor is back at slot 0; pending
+ * events stay.  Enqueued, no wait. */
+int  sgp_particles_clear(sgp_particles* ps);
 
 /* ---- overlap queries with any convex shape (JPH::NarrowPhaseQuery::CollideShape) --------------------
  * "What is inside this volume?": a box for a parcel or a trigger volume, a sphere for an explosion or an audio radius, the hull of an

@@ -261,6 +261,27 @@ class CharacterContact(C.Structure):
                 ("point", f32 * 3), ("normal", f32 * 3)]
 
 
+PARTICLE_DIE_ON_HIT = 1                                                  # SGP_PARTICLE_DIE_ON_HIT
+PARTICLE_EV_DIED, PARTICLE_EV_FOAM, PARTICLE_EV_REPLACED = 1, 2, 4       # SGP_PARTICLE_EV_*
+PARTICLES_MAX_CAPACITY = 1 << 20
+
+
+class Particle(C.Structure):
+    """sgp_particle: what the reference's Particle carries for the simulation (ParticleManager.h:25-60); `tag` stands for the caller's gl_ob."""
+    _fields_ = [("pos", f32 * 3), ("vel", f32 * 3), ("area", f32), ("mass", f32), ("restitution", f32), ("width", f32),
+                ("dwidth_dt", f32), ("opacity", f32), ("dopacity_dt", f32), ("flags", u32), ("tag", u64)]
+
+
+class ParticleState(C.Structure):
+    """sgp_particle_state: a live particle as sgp_particles_read reports it."""
+    _fields_ = [("pos", f32 * 3), ("width", f32), ("vel", f32 * 3), ("opacity", f32), ("tag", u64), ("flags", u32), ("reserved_", u32)]
+
+
+class ParticleEvent(C.Structure):
+    """sgp_particle_event: DIED / FOAM / REPLACED of one particle."""
+    _fields_ = [("tag", u64), ("kind", u32), ("pos", f32 * 3), ("width", f32), ("foam_width", f32)]
+
+
 class CompoundChild(C.Structure):
     _fields_ = [("shape_type", i32), ("shape", f32 * 4), ("pos", f32 * 3), ("rot", f32 * 4)]
 
@@ -290,7 +311,8 @@ ABI_SIZEOF_ORDER = ["sgp_settings", "sgp_world_desc", "sgp_body_desc", "sgp_body
 # (index 21 is not used and answers -1 for good: bindings that know 21 structs probe it for the end of the list)
 # (likewise 24, which the bindings that know 24 structs probe)
 ABI_SIZEOF_APPENDED = ["sgp_shape_query", None, "sgp_shape_cast", "sgp_cast_hit",
-                       None, "sgp_character_desc", "sgp_character_input", "sgp_character_state", "sgp_character_contact"]
+                       None, "sgp_character_desc", "sgp_character_input", "sgp_character_state", "sgp_character_contact",
+                       None, "sgp_particle", "sgp_particle_state", "sgp_particle_event"]      # (29 likewise)
 ABI_SIZEOF_ALL = ABI_SIZEOF_ORDER + ABI_SIZEOF_APPENDED
 
 STRUCTS = {"sgp_settings": Settings, "sgp_world_desc": WorldDesc, "sgp_body_desc": BodyDesc,
@@ -301,7 +323,8 @@ STRUCTS = {"sgp_settings": Settings, "sgp_world_desc": WorldDesc, "sgp_body_desc
            "sgp_query_contact": QueryContact, "sgp_mesh_info": MeshInfo, "sgp_heightfield_desc": HeightfieldDesc,
            "sgp_checkpoint_info": CheckpointInfo, "sgp_shape_query": ShapeQuery, "sgp_shape_cast": ShapeCast,
            "sgp_cast_hit": CastHit, "sgp_character_desc": CharacterDesc, "sgp_character_input": CharacterInput,
-           "sgp_character_state": CharacterState, "sgp_character_contact": CharacterContact}
+           "sgp_character_state": CharacterState, "sgp_character_contact": CharacterContact,
+           "sgp_particle": Particle, "sgp_particle_state": ParticleState, "sgp_particle_event": ParticleEvent}
 
 body_desc_dtype = np.dtype(BodyDesc)
 body_state_dtype = np.dtype(BodyState)
@@ -323,6 +346,9 @@ cast_hit_dtype = np.dtype(CastHit)
 character_input_dtype = np.dtype(CharacterInput)
 character_state_dtype = np.dtype(CharacterState)
 character_contact_dtype = np.dtype(CharacterContact)
+particle_dtype = np.dtype(Particle)
+particle_state_dtype = np.dtype(ParticleState)
+particle_event_dtype = np.dtype(ParticleEvent)
 compound_child_dtype = np.dtype(CompoundChild)
 migration_dtype = np.dtype(Migration)
 
@@ -403,6 +429,15 @@ PROTOTYPES = {
     "characters_update": (C.c_int, [vp, f32]),
     "characters_get_states": (C.c_int, [vp, u32, u32, vp]),
     "characters_drain_contacts": (C.c_int, [vp, vp, u32, P(u32)]),
+    # batched point particles (handle: void*)
+    "default_particle": (None, [P(Particle)]),
+    "particles_create": (C.c_int, [vp, u32, u32, P(vp)]),
+    "particles_destroy": (C.c_int, [vp]),
+    "particles_add": (C.c_int, [vp, vp, u32]),
+    "particles_update": (C.c_int, [vp, f32]),
+    "particles_read": (C.c_int, [vp, vp, u32, P(u32)]),
+    "particles_drain_events": (C.c_int, [vp, vp, u32, P(u32), P(u32)]),
+    "particles_clear": (C.c_int, [vp]),
     "world_export_boundary": (C.c_int, [vp, P(f32), P(f32), f32, vp, u32, P(u32)]),
     "world_import_ghosts": (C.c_int, [vp, vp, u32]),
     "tiles_route": (C.c_int, [vp, u32, u32, vp, u32, f32, vp, u32, vp, vp, u32, P(u32)]),

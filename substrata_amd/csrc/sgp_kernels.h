@@ -15,6 +15,7 @@
 //   sgp_k_shapequery.hip   A7     k_sq_wave, k_sq_candidates + k_sq_pairs_prim / k_sq_pairs_hull / k_sq_mesh (sgp_collide_shapes)
 //   sgp_k_shapecast.hip    A7     k_sc_candidates + k_sc_pairs_prim / k_sc_pairs_hull / k_sc_mesh (sgp_cast_shapes)
 //   sgp_k_characters.hip   A7     k_characters_update (a wave per character: the whole Update / ExtendedUpdate), k_characters_push, k_characters_sync (sgp_characters_*)
+//   sgp_k_particles.hip    A7     k_particles_update (a lane per particle: raycast_one + ParticleManager::think), k_particles_scan, k_particles_scatter (stable compaction + events), k_particles_append (sgp_particles_*)
 //   sgp_k_edits.hip        A5/A6  k_apply_cmds, k_ghost_refresh, read-back
 //   sgp_k_tiles.hip        (e)    tile export / routing, re-tiling histograms
 //   sgp_k_checkpoint.hip          k_ckpt_copy: the segmented copy of sgp_world_checkpoint / sgp_world_rollback
@@ -518,6 +519,24 @@ struct CharBufs {
 void launch_characters_update(const DV* d_dev, const CharBufs& b, float dt, hipStream_t s);      // d_dev: a copy of the world's DV in device memory (the phases are functions of their own: they read it through a pointer)
 void launch_characters_push(const DV& d, const CharBufs& b, hipStream_t s);
 void launch_characters_sync(const CharBufs& b, hipStream_t s);
+// ---- batched point particles (sgp_k_particles.hip, sgp_dev_particles.h) ---------------------------------------------------------------------------------
+// Everything lives on the device, the counts included: the host learns them only when it reads.  A particle is a hot half (two float4: pos xyz + width,
+// vel xyz + opacity) that the update reads and writes, and a cold half (two uint4: area, mass, restitution, dwidth_dt | dopacity_dt, flags, tag) that it
+// only reads; both exist twice, and the stable compaction behind every update moves the survivors from one copy to the other (`cur` of a launch: which
+// copy holds the live particles when it starts; the host flips it with every update).
+#define PS_SCAN_THREADS 1024
+struct PsState { uint32_t n_live, cursor, n_prev, ev_base, n_events, pad_[3]; };      // n_prev / ev_base: the live count and the event count the running update started with (k_particles_scan -> k_particles_scatter); n_events counts what was dropped too
+struct PsBufs {
+	float4* hot[2]; uint4* cold[2];      // [2 * slot], [2 * slot + 1]
+	uint2* evw;                          // [slot] of the running update: SGP_PARTICLE_EV_* bits, the foam decal's width (float bits)
+	uint2* wg_counts; uint2* wg_off;     // [64-slot block]: survivors and events of the block, and their exclusive scan
+	PsState* st;
+	sgp_particle_event* events; uint32_t cap, ev_cap;
+};
+// update + scan + scatter over the first `upper` slots (the host's upper bound of the live count); nothing is launched for upper == 0
+void launch_particles_update(const DV& d, const PsBufs& b, uint32_t cur, uint32_t upper, float dt, int water_enabled, float water_z, hipStream_t s);
+void launch_particles_append(const PsBufs& b, uint32_t cur, const sgp_particle* recs, uint32_t n, hipStream_t s);
+void launch_particles_pack(const PsBufs& b, uint32_t cur, uint32_t upper, sgp_particle_state* out, hipStream_t s);      // out[i], i < min(live count, upper)
 void launch_export_boundary(const DV& d, uint32_t nb, float3 lo, float3 hi, float margin, sgp_ghost_record* out, uint32_t cap, uint32_t* count, hipStream_t s);
 
 // ---- tile exchange with the routing on the device (sgp_tiles_*) ----------------------------------------------------

@@ -5,6 +5,7 @@
 //   sgp_world_shapes.hip     meshes, convex hulls, vehicles
 //   sgp_world_queries.hip    rays, capsule queries, sphere casts
 //   sgp_world_characters.hip the batched character controller (sgp_characters_*)
+//   sgp_world_particles.hip  the batched point particles (sgp_particles_*)
 //   sgp_world_tiles.hip      ghost import / export, the tile exchange over RCCL, re-tiling
 //   sgp_world_snapshots.hip  the network snapshot codec and the de-jitter queue (host only)
 //   sgp_world_checkpoint.hip capture, rollback, the checkpoint blob and restore
@@ -269,6 +270,7 @@ uint64_t world_register(); void world_unregister(uint64_t serial); bool world_al
 int ensure_vehicle_capacity(sgp_world* w, uint32_t need);      // grows the vehicle arrays (device pointers change: graphs are invalidated by the caller)
 int shapes_upload_all(sgp_world* w);                           // the host mirrors of the shape tables and pools -> the device (pools grow through the usual path), DV updated, graphs invalidated
 // defined in sgp_world_queries.hip
+int query_prelude(sgp_world* w);          // flush_cmds (edits applied, the resident ray server told to leave) + ensure_query_grid: what precedes a batch of rays (sgp_raycast, sgp_particles_update)
 int ensure_query_grid(sgp_world* w);      // re-bins the bodies when poses changed since the broad-phase grid was built (every query's first step after flush_cmds)
 // defined in sgp_world_bodies.hip
 int add_one(sgp_world* w, const sgp_body_desc* d, uint32_t* id_out, bool ghost);

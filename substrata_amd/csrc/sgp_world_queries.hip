@@ -62,15 +62,8 @@ SGP_API int sgp_raycast(sgp_world* w, const sgp_ray* rays, uint32_t n, sgp_hit* 
 		if (r < 0) return r;
 		if (r == 1) { finish_hit(w, hits); return SGP_OK; }
 	}
-	{ int r = flush_cmds(w); if (r != SGP_OK) return r; }
-	if (!n) return SGP_OK;
-	if (!w->grid_valid && w->high) {
-		// poses changed since the grid was built (a step integrates after its broad phase; edits move bodies): re-bin
-		const DV& d = w->dv; hipStream_t s = w->stream; const uint32_t nb = w->high;
-		launch_step_begin(d, *w->h_sp, nb, false, false, s); w->sp_uploaded = *w->h_sp; w->sp_uploaded_valid = true;
-		launch_bp_bounds(d, nb, s); launch_bp_cell(d, nb, s); launch_bp_scan(d, s); launch_bp_scatter(d, nb, s);
-		w->grid_valid = true;
-	}
+	if (!n) { int r = flush_cmds(w); return r; }
+	{ int r = query_prelude(w); if (r != SGP_OK) return r; }
 	if (n == 1 && w->high) {
 		// a single ray: start (or reach) the resident server behind the grid kernels just queued; the next single rays find it running
 		const int r = ray_through_server(w, rays, hits);
@@ -95,6 +88,15 @@ SGP_API int sgp_raycast(sgp_world* w, const sgp_ray* rays, uint32_t n, sgp_hit* 
 	memcpy(hits, (char*)w->stage_host + rb, sizeof(sgp_hit) * n);
 	for (uint32_t k = 0; k < n; ++k) finish_hit(w, &hits[k]);
 	return SGP_OK;
+}
+
+// What a batch of rays needs before its launch (the batched branch of sgp_raycast, sgp_particles_update): pending body edits flushed -- which also tells
+// a resident ray server to leave --, and the broad-phase grid valid for the poses as they are.  Nothing waits unless an edit was pending.
+int query_prelude(sgp_world* w)
+{
+	hipSetDevice(w->device);
+	{ int r = flush_cmds(w); if (r != SGP_OK) return r; }
+	return ensure_query_grid(w);
 }
 
 int ensure_query_grid(sgp_world* w)

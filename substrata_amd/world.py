@@ -117,6 +117,61 @@ class Characters:
             pass
 
 
+class Particles:
+    """A batch of point particles of one world (sgp_particles): numpy in, numpy out.  add(), update() and clear() enqueue and return; read() and
+    drain_events() wait."""
+
+    def __init__(self, world, capacity, event_capacity=4096):
+        self._w, self._h = world, C.c_void_p()
+        world._check(world._fn("particles_create")(world._h, int(capacity), int(event_capacity), C.byref(self._h)), "particles_create")
+        self.capacity, self.event_capacity = int(capacity), int(event_capacity)
+
+    def defaults(self, n=1):
+        """n records of abi.particle_dtype filled by sgp_default_particle (the defaults of the reference's Particle())."""
+        d = abi.Particle()
+        self._w._fn("default_particle")(C.byref(d))
+        out = np.zeros(int(n), dtype=abi.particle_dtype)
+        out[:] = np.frombuffer(bytes(d), dtype=abi.particle_dtype)[0]
+        return out
+
+    def add(self, particles):
+        particles = np.ascontiguousarray(particles, dtype=abi.particle_dtype).reshape(-1)
+        self._w._check(self._w._fn("particles_add")(self._h, particles.ctypes.data, len(particles)), "particles_add")
+
+    def update(self, dt=1.0 / 60.0):
+        self._w._check(self._w._fn("particles_update")(self._h, float(dt)), "particles_update")
+
+    def clear(self):
+        self._w._check(self._w._fn("particles_clear")(self._h), "particles_clear")
+
+    def read(self, cap=None):
+        """The live particles in slot order (abi.particle_state_dtype)."""
+        cap = self.capacity if cap is None else int(cap)
+        out = np.zeros(cap, dtype=abi.particle_state_dtype)
+        n = C.c_uint32(0)
+        self._w._check(self._w._fn("particles_read")(self._h, out.ctypes.data, cap, C.byref(n)), "particles_read")
+        return out[:min(n.value, cap)].copy()
+
+    def drain_events(self, cap=None):
+        """(events since the last drain as abi.particle_event_dtype, how many more did not fit event_capacity)"""
+        cap = self.event_capacity if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), dtype=abi.particle_event_dtype)
+        n, dropped = C.c_uint32(0), C.c_uint32(0)
+        self._w._check(self._w._fn("particles_drain_events")(self._h, out.ctypes.data, cap, C.byref(n), C.byref(dropped)), "particles_drain_events")
+        return out[:min(n.value, cap)].copy(), int(dropped.value)
+
+    def close(self):
+        if self._h:
+            self._w._fn("particles_destroy")(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class CWorld:
     def __init__(self, lib, prefix, max_bodies=65536, gravity=(0.0, 0.0, -9.81), device=0, settings=None,
                  max_body_pairs=0, max_manifolds=0, large_body_radius=0.0):
@@ -480,6 +535,10 @@ class CWorld:
     def vehicle_reset_drivetrain(self, vid, engine_rpm=0.0, wheel_angular_velocity=0.0):
         self._check(self._fn("vehicle_reset_drivetrain")(self._h, int(vid), float(engine_rpm), float(wheel_angular_velocity)),
                     "vehicle_reset_drivetrain")
+
+    def particles(self, capacity, event_capacity=4096):
+        """A batch of up to `capacity` point particles that belongs to this world."""
+        return Particles(self, capacity, event_capacity)
 
     def characters(self, capacity):
         """A batch of up to `capacity` virtual characters that belongs to this world (close it before the world)."""
