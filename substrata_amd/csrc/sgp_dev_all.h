@@ -8,5 +8,5 @@
 #include "sgp_dev_solve.h"
 #include "sgp_dev_sweep.h"
 #include "sgp_dev_edits.h"
-#include "sgp_dev_queries.h"
 #include "sgp_dev_vehiclecast.h"
+#include "sgp_dev_queries.h"

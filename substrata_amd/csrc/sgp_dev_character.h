@@ -21,51 +21,31 @@ struct CharLds {
 	uint32_t mesh_list[SGP_CHAR_MESH_LIST];
 	uint32_t n_raw, n_cur, n_act, n_k, n_seen, n_mesh, overflow, n_push, n_added;
 };
-struct CharHit { float t; uint32_t id; v3 n; };
 struct CharGround { uint32_t state, body; v3 n, v, p; };
 
 // ---------------------------------------------------------------------------------------------------------------
-// CharacterVirtual::getContacts: k_collide_capsules for one capsule, its records into LDS instead of the caller's buffer
+// CharacterVirtual::getContacts: k_collide_capsules for one capsule (the same capsule_shape, sq_walk, capsule_query_body and contact_record), its records into
+// LDS instead of the caller's buffer
 
-SGP_DEV void char_emit(const DV& d, CharLds& S, float padding, uint32_t j, uint32_t f, int g, const sgd_manifold& m)
-{
-	for (int i = 0; i < m.np; ++i) {
-		const uint32_t slot = atomicAdd(&S.n_raw, 1u);
-		if (slot >= SGP_CHAR_MAX_CONTACTS) continue;
-		CharContact c;
-		c.body = j; c.idx = (uint32_t)(4 * g + i);
-		c.p[0] = m.p1[i].x; c.p[1] = m.p1[i].y; c.p[2] = m.p1[i].z;
-		c.n[0] = m.n.x; c.n[1] = m.n.y; c.n[2] = m.n.z;
-		const float distance = v3_dot(v3_sub(m.p2[i], m.p1[i]), m.n);
-		c.dist = distance - padding;
-		v3 pv = V3(0.0f, 0.0f, 0.0f);
-		if (f_motion(f) != SGP_MOTION_STATIC) pv = v3_add(V3(d.vel[VEL_F4 * (size_t)j]), v3_cross(V3(d.vel[VEL_F4 * (size_t)j + 1]), v3_sub(m.p1[i], V3(d.pose[POSE_F4 * (size_t)j]))));
-		c.v[0] = pv.x; c.v[1] = pv.y; c.v[2] = pv.z;
-		c.bits = ((f & BF_SENSOR) ? 1u : 0u) | (f_motion(f) == SGP_MOTION_DYNAMIC ? 2u : 0u);
-		c.inv_mass = d.pose[POSE_F4 * (size_t)j].w;
-		S.cur[slot] = c;
+struct CharSink {
+	const DV& d; CharLds& S; float padding;
+	SGP_DEV bool list_mesh(uint32_t j) const { const uint32_t at = atomicAdd(&S.n_mesh, 1u); if (at < SGP_CHAR_MESH_LIST) S.mesh_list[at] = j; return at < SGP_CHAR_MESH_LIST; }
+	SGP_DEV void emit(uint32_t j, uint32_t f, int g, const sgd_manifold& m) const
+	{
+		for (int i = 0; i < m.np; ++i) {
+			const uint32_t slot = atomicAdd(&S.n_raw, 1u);
+			if (slot >= SGP_CHAR_MAX_CONTACTS) continue;
+			const sgp_query_contact q = contact_record(d, 0u, j, f, g, m, i);
+			CharContact c;
+			c.body = j; c.idx = q.sub_shape;
+			for (int a = 0; a < 3; ++a) { c.p[a] = q.point[a]; c.n[a] = q.normal[a]; c.v[a] = q.point_velocity[a]; }
+			c.dist = q.distance - padding;
+			c.bits = q.is_sensor | (q.motion_type == SGP_MOTION_DYNAMIC ? 2u : 0u);
+			c.inv_mass = q.inv_mass;
+			S.cur[slot] = c;
+		}
 	}
-}
-
-SGP_DEV void char_query_body(const DV& d, CharLds& S, float padding, float max_sep, uint32_t ignore, const sgd_shape& sc, v3 lo, v3 hi, uint32_t j)
-{
-	if (j == ignore) return;
-	const uint32_t f = d.flags[j];
-	if (!(f & BF_ALIVE) || (f & BF_ALIAS)) return;
-	const uint32_t layer = f_layer(f);
-	if (!(layer == SGP_LAYER_NON_MOVING || layer == SGP_LAYER_MOVING)) return;      // (PlayerPhysicsObjectLayerFilter: collidable_only)
-	const float4 mn = d.aabb_min[j], mx = d.aabb_max[j];
-	if (mx.x < lo.x || mn.x > hi.x || mx.y < lo.y || mn.y > hi.y || mx.z < lo.z || mn.z > hi.z) return;
-	const sgd_shape sb = load_shape(d, j, f);
-	sgd_manifold mm[SGD_MESH_MAX_GROUPS]; int ng; bool dropped = false;
-	if (sb.type == SGP_SHAPE_MESH) {
-		const uint32_t at = atomicAdd(&S.n_mesh, 1u);
-		if (at < SGP_CHAR_MESH_LIST) { S.mesh_list[at] = j; return; }
-		ng = collide_with_mesh(d, j, sc, lo, hi, max_sep, mm, &dropped);      // (more meshes around one capsule than the list holds: this lane walks the rest)
-	}
-	else ng = (sb.type == SGP_SHAPE_HULL ? sgd_collide_hull(&sb, &sc, max_sep, &mm[0]) : sgd_collide(&sb, &sc, max_sep, &mm[0])) ? 1 : 0;   // normal: body -> capsule
-	for (int g = 0; g < ng; ++g) char_emit(d, S, padding, j, f, g, mm[g]);
-}
+};
 
 // the contacts of the capsule at `pos` into S.cur / S.n_cur, sorted; whole wave
 __device__ __noinline__ void char_contacts(const DV& d, MeshPairLds<64>& L, CharLds& S, const CharRec* rc, uint32_t ignore, v3 pos, v3 movement)
@@ -73,32 +53,15 @@ __device__ __noinline__ void char_contacts(const DV& d, MeshPairLds<64>& L, Char
 	const uint32_t lane = threadIdx.x;
 	const float ml = sqrtf(v3_len_sq(movement));
 	const v3 mv = V3(ml > 0.0f ? movement.x / ml : 0.0f, ml > 0.0f ? movement.y / ml : 0.0f, ml > 0.0f ? movement.z / ml : 0.0f);
-	const float padding = rc->padding, max_sep = rc->predictive + rc->padding;
-	sgd_shape sc;
-	sc.pos = v3_add(pos, ch_v3(rc->offset));
+	const float max_sep = rc->predictive + rc->padding;
 	quat qq; qq.x = 0.0f; qq.y = 0.0f; qq.z = 0.0f; qq.w = 1.0f;
-	sc.R = quat_to_m33(qq); sc.type = SGP_SHAPE_CAPSULE; sc.p0 = rc->radius; sc.p1 = rc->half_height; sc.p2 = 0.0f; sc.hull = nullptr;
-	const v3 ax = v3_scale(sc.R.c2, rc->half_height);
-	const float e = rc->radius + max_sep;
-	const v3 ext = V3(fabsf(ax.x) + e, fabsf(ax.y) + e, fabsf(ax.z) + e);
-	const v3 lo = v3_sub(sc.pos, ext), hi = v3_add(sc.pos, ext);
+	sgd_shape sc; v3 lo, hi;
+	capsule_shape(v3_add(pos, ch_v3(rc->offset)), qq, rc->radius, rc->half_height, max_sep, sc, lo, hi);
+	const CharSink sink = { d, S, rc->padding };
 	__syncthreads();      // (everybody is done with the previous S.cur)
 	if (lane == 0) { S.n_mesh = 0; S.n_raw = 0; }
 	__syncthreads();
-	for (uint32_t l = lane; l < d.sp->n_large; l += 64) char_query_body(d, S, padding, max_sep, ignore, sc, lo, hi, d.large_ids[l]);
-	{
-		uint32_t seen = 0;
-		large_grid_query(d, lo, hi, [&](uint32_t i) { if ((seen++ & 63u) == lane) char_query_body(d, S, padding, max_sep, ignore, sc, lo, hi, i); });
-	}
-	const BpGrid g = *d.grid;
-	if (g.n_cells > 0 && g.min_x <= g.max_x) {
-		const int x0 = max((int)floorf((lo.x - g.ox) * g.inv_cell) - 1, 0), x1 = min((int)floorf((hi.x - g.ox) * g.inv_cell) + 1, g.nx - 1);
-		const int y0 = max((int)floorf((lo.y - g.oy) * g.inv_cell) - 1, 0), y1 = min((int)floorf((hi.y - g.oy) * g.inv_cell) + 1, g.ny - 1);
-		const int z0 = max((int)floorf((lo.z - g.oz) * g.inv_cell) - 1, 0), z1 = min((int)floorf((hi.z - g.oz) * g.inv_cell) + 1, g.nz - 1);
-		if (x0 <= x1) for (int z = z0; z <= z1; ++z) for (int y = y0; y <= y1; ++y) {
-			grid_row_runs(d, g, x0, x1, y, z, [&](uint32_t c0, uint32_t c1) { for (uint32_t c = c0 + lane; c < c1; c += 64) char_query_body(d, S, padding, max_sep, ignore, sc, lo, hi, __float_as_uint(d.sorted_max[c].w)); });
-		}
-	}
+	sq_walk<64>(d, lo, hi, lane, [&](uint32_t j) { capsule_query_body(d, ignore, true, max_sep, sc, lo, hi, j, sink); });      // (collidable only: PlayerPhysicsObjectLayerFilter)
 	__syncthreads();
 	const uint32_t nm = min(S.n_mesh, (uint32_t)SGP_CHAR_MESH_LIST);
 	const v3 es = V3(max_sep, max_sep, max_sep);
@@ -111,7 +74,7 @@ __device__ __noinline__ void char_contacts(const DV& d, MeshPairLds<64>& L, Char
 			const sgd_mesh_group& grp = L.mc.g[lane];
 			sgd_manifold mm;
 			sgd_hull_reduce(grp.n, grp.p_mesh, grp.p_body, grp.np, &mm);
-			char_emit(d, S, padding, mid, d.flags[mid], (int)lane, mm);
+			sink.emit(mid, d.flags[mid], (int)lane, mm);
 		}
 		__syncthreads();
 	}
@@ -130,56 +93,21 @@ __device__ __noinline__ void char_contacts(const DV& d, MeshPairLds<64>& L, Char
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// sgp_spherecast for one sphere by the wave: spherecast_body's pad, cut-off and filters; the candidates dealt to the lanes, each lane keeping its closest hit, the
-// answer the least (t, body id) of the lanes -- k_spherecast's, whose tie rule makes the result independent of the order of the tests
-
-SGP_DEV void char_cast_body(const DV& d, uint32_t ignore, float max_t, float rs, v3 o, v3 dir, uint32_t j, CharHit& best)
-{
-	if (j == ignore) return;
-	const uint32_t f = d.flags[j];
-	if (!(f & BF_ALIVE) || (f & (BF_SENSOR | BF_ALIAS))) return;
-	const uint32_t layer = f_layer(f);
-	if (!(layer == SGP_LAYER_NON_MOVING || layer == SGP_LAYER_MOVING)) return;
-	const float4 mn = d.aabb_min[j], mx = d.aabb_max[j];
-	const float e = rs + 1.0e-3f;
-	if (!ray_aabb(o, dir, make_float4(mn.x - e, mn.y - e, mn.z - e, 0.0f), make_float4(mx.x + e, mx.y + e, mx.z + e, 0.0f), max_t)) return;
-	const float4 sh = d.pose[POSE_F4 * (size_t)j + 3];
-	const float prm[3] = { sh.x, sh.y, sh.z };
-	v3 n, p;
-	const float t = f_shape(f) == SGP_SHAPE_MESH ? cast_sphere_mesh(d, j, o, dir, best.t, rs, &n, &p)
-	              : sgd_cast_sphere_body((int)f_shape(f), prm, f_shape(f) == SGP_SHAPE_HULL ? body_hull(d, sh) : nullptr, V3(d.pose[POSE_F4 * (size_t)j]), quat_to_m33(Q4(d.pose[POSE_F4 * (size_t)j + 1])), o, dir, best.t, rs, &n, &p);
-	if (t >= 0.0f && t <= best.t && (t < best.t || best.id == SGP_INVALID_ID || j < best.id)) { best.t = t; best.id = j; best.n = n; }
-}
+// sgp_spherecast for one sphere by the wave: k_spherecast's walk and candidate test (spherecast_walk, spherecast_body), the candidates dealt to the lanes, each lane
+// keeping its closest hit, the answer the least (t, body id) of the lanes -- k_spherecast's, whose tie rule makes the result independent of the order of the tests
 
 // returns sgp_hit's id, t (0 without a hit) and normal, the same in every lane
-__device__ __noinline__ CharHit char_spherecast(const DV& d, v3 o, v3 dir, float max_t, float rs, uint32_t ignore)
+__device__ __noinline__ SphereHit char_spherecast(const DV& d, v3 o, v3 dir, float max_t, float rs, uint32_t ignore)
 {
 	const uint32_t lane = threadIdx.x;
-	CharHit best; best.t = max_t; best.id = SGP_INVALID_ID; best.n = V3(0.0f, 0.0f, 0.0f);
-	for (uint32_t l = lane; l < d.sp->n_large; l += 64) char_cast_body(d, ignore, max_t, rs, o, dir, d.large_ids[l], best);
-	const v3 e = v3_add(o, v3_scale(dir, max_t));
-	{
-		const float m = rs + 2.0e-3f;
-		uint32_t seen = 0;
-		large_grid_query(d, V3(fminf(o.x, e.x) - m, fminf(o.y, e.y) - m, fminf(o.z, e.z) - m), V3(fmaxf(o.x, e.x) + m, fmaxf(o.y, e.y) + m, fmaxf(o.z, e.z) + m),
-		                 [&](uint32_t i) { if ((seen++ & 63u) == lane) char_cast_body(d, ignore, max_t, rs, o, dir, i, best); });
-	}
-	const BpGrid g = *d.grid;
-	if (g.n_cells > 0 && g.min_x <= g.max_x) {
-		const float m = rs + 1.0e-3f;
-		const int x0 = max((int)floorf((fminf(o.x, e.x) - m - g.ox) * g.inv_cell) - 1, 0), x1 = min((int)floorf((fmaxf(o.x, e.x) + m - g.ox) * g.inv_cell) + 1, g.nx - 1);
-		const int y0 = max((int)floorf((fminf(o.y, e.y) - m - g.oy) * g.inv_cell) - 1, 0), y1 = min((int)floorf((fmaxf(o.y, e.y) + m - g.oy) * g.inv_cell) + 1, g.ny - 1);
-		const int z0 = max((int)floorf((fminf(o.z, e.z) - m - g.oz) * g.inv_cell) - 1, 0), z1 = min((int)floorf((fmaxf(o.z, e.z) + m - g.oz) * g.inv_cell) + 1, g.nz - 1);
-		if (x0 <= x1) for (int z = z0; z <= z1; ++z) for (int y = y0; y <= y1; ++y) {
-			grid_row_runs(d, g, x0, x1, y, z, [&](uint32_t c0, uint32_t c1) { for (uint32_t c = c0 + lane; c < c1; c += 64) char_cast_body(d, ignore, max_t, rs, o, dir, __float_as_uint(d.sorted_max[c].w), best); });
-		}
-	}
+	SphereHit best; best.t = max_t; best.id = SGP_INVALID_ID; best.n = V3(0.0f, 0.0f, 0.0f);
+	spherecast_walk<64>(d, o, dir, max_t, rs, lane, [&](uint32_t j) { spherecast_body(d, ignore, true, max_t, rs, o, dir, j, best); });
 	float wt = best.id != SGP_INVALID_ID ? best.t : 3.0e38f; uint32_t wid = best.id;
 	for (int off = 32; off >= 1; off >>= 1) {
 		const float ot = __shfl_xor(wt, off, 64); const uint32_t oid = (uint32_t)__shfl_xor((int)wid, off, 64);
 		if (oid != SGP_INVALID_ID && (wid == SGP_INVALID_ID || ot < wt || (ot == wt && oid < wid))) { wt = ot; wid = oid; }
 	}
-	CharHit h; h.id = wid; h.t = 0.0f; h.n = V3(0.0f, 0.0f, 0.0f);
+	SphereHit h; h.id = wid; h.t = 0.0f; h.n = V3(0.0f, 0.0f, 0.0f);
 	if (wid != SGP_INVALID_ID) {
 		const unsigned long long owners = __ballot(best.id == wid && best.t == wt);
 		const int src = __ffsll((long long)owners) - 1;
@@ -199,7 +127,7 @@ SGP_DEV float char_sweep_fraction(const DV& d, const CharRec* rc, v3 pos, v3 dis
 	float travel = len;
 	for (int k = 0; k < 2; ++k) {
 		const v3 o = v3_add(c, v3_scale(up, (k ? 1.0f : -1.0f) * rc->half_height));
-		const CharHit h = char_spherecast(d, o, dir, len + rc->padding, rc->radius, ignore);
+		const SphereHit h = char_spherecast(d, o, dir, len + rc->padding, rc->radius, ignore);
 		if (h.id != SGP_INVALID_ID && h.t > 1.0e-5f) {
 			if (h.n.x * dir.x + h.n.y * dir.y + h.n.z * dir.z < -0.05f) travel = ch_min(travel, ch_max(0.0f, h.t - rc->padding));
 		}
@@ -213,7 +141,7 @@ SGP_DEV float char_cast_down(const DV& d, const CharRec* rc, v3 pos, v3 step, ui
 	const float len = sqrtf(v3_len_sq(step));
 	if (len < 1.0e-6f) return -1.0f;
 	const v3 dir = v3_scale(step, 1.0f / len), o = v3_sub(v3_add(pos, ch_v3(rc->offset)), v3_scale(ch_v3(rc->up), rc->half_height));
-	const CharHit h = char_spherecast(d, o, dir, len, rc->radius, ignore);
+	const SphereHit h = char_spherecast(d, o, dir, len, rc->radius, ignore);
 	if (h.id == SGP_INVALID_ID) return -1.0f;
 	*normal_out = h.n;
 	return h.t;

@@ -176,47 +176,20 @@ __global__ void __launch_bounds__(64) k_ray_server(DV d, RayMailbox* mb, uint32_
 // ---------------------------------------------------------------------------------------------------------------
 // Shape queries of the character controller (JPH::CharacterVirtual: CollideShape with a maximum separation, swept test).
 
-// the points of one manifold (normal: body -> capsule) as contacts of query k with body j
-SGP_DEV void capsule_emit(const DV& d, uint32_t k, uint32_t j, uint32_t f, int g, const sgd_manifold& m, sgp_query_contact* out, uint32_t cap, uint32_t* count)
-{
-	for (int i = 0; i < m.np; ++i) {
-		const uint32_t slot = atomicAdd(count, 1u);
-		if (slot >= cap) continue;
-		sgp_query_contact c;
-		c.query = k; c.body = j; c.sub_shape = (uint32_t)(4 * g + i);      // point index for the host's sort; the host then stores the compound child index here
-		c.point[0] = m.p1[i].x; c.point[1] = m.p1[i].y; c.point[2] = m.p1[i].z;
-		c.normal[0] = m.n.x; c.normal[1] = m.n.y; c.normal[2] = m.n.z;
-		c.distance = v3_dot(v3_sub(m.p2[i], m.p1[i]), m.n);
-		v3 pv = V3(0.0f, 0.0f, 0.0f);
-		if (f_motion(f) != SGP_MOTION_STATIC) pv = v3_add(V3(d.vel[VEL_F4 * (size_t)j]), v3_cross(V3(d.vel[VEL_F4 * (size_t)j + 1]), v3_sub(m.p1[i], V3(d.pose[POSE_F4 * (size_t)j]))));
-		c.point_velocity[0] = pv.x; c.point_velocity[1] = pv.y; c.point_velocity[2] = pv.z;
-		c.motion_type = f_motion(f); c.is_sensor = (f & BF_SENSOR) ? 1u : 0u; c.inv_mass = d.pose[POSE_F4 * (size_t)j].w; c.userdata = 0;
-		out[slot] = c;
-	}
-}
-
-// One candidate body of a query, by one lane: the filters, then the collision test -- except for mesh bodies, which go on the wave's list (their
-// triangles are the whole wave's work).
+// where the answers of one query capsule go: the records into the caller's buffer (a slot per point from the global counter), mesh bodies onto the wave's list
 #define QUERY_MESH_LIST 32
-SGP_DEV void capsule_query_body(const DV& d, const sgp_capsule_query& q, uint32_t k, const sgd_shape& sc, v3 lo, v3 hi, uint32_t j, sgp_query_contact* out, uint32_t cap, uint32_t* count, uint32_t* mesh_list, uint32_t* n_mesh)
-{
-	if (j == q.ignore_id) return;
-	const uint32_t f = d.flags[j];
-	if (!(f & BF_ALIVE) || (f & BF_ALIAS)) return;
-	const uint32_t layer = f_layer(f);
-	if (q.collidable_only && !(layer == SGP_LAYER_NON_MOVING || layer == SGP_LAYER_MOVING)) return;
-	const float4 mn = d.aabb_min[j], mx = d.aabb_max[j];
-	if (mx.x < lo.x || mn.x > hi.x || mx.y < lo.y || mn.y > hi.y || mx.z < lo.z || mn.z > hi.z) return;
-	const sgd_shape sb = load_shape(d, j, f);
-	sgd_manifold mm[SGD_MESH_MAX_GROUPS]; int ng; bool dropped = false;
-	if (sb.type == SGP_SHAPE_MESH) {
-		const uint32_t at = atomicAdd(n_mesh, 1u);
-		if (at < QUERY_MESH_LIST) { mesh_list[at] = j; return; }
-		ng = collide_with_mesh(d, j, sc, lo, hi, q.max_separation, mm, &dropped);      // (more meshes around one capsule than the list holds: this lane walks the rest)
+struct CapsuleSink {
+	const DV& d; uint32_t k; sgp_query_contact* out; uint32_t cap; uint32_t* count; uint32_t* mesh_list; uint32_t* n_mesh;
+	SGP_DEV bool list_mesh(uint32_t j) const { const uint32_t at = atomicAdd(n_mesh, 1u); if (at < QUERY_MESH_LIST) mesh_list[at] = j; return at < QUERY_MESH_LIST; }
+	// the points of one manifold (normal: body -> capsule) as contacts of query k with body j
+	SGP_DEV void emit(uint32_t j, uint32_t f, int g, const sgd_manifold& m) const
+	{
+		for (int i = 0; i < m.np; ++i) {
+			const uint32_t slot = atomicAdd(count, 1u);
+			if (slot < cap) out[slot] = contact_record(d, k, j, f, g, m, i);
+		}
 	}
-	else ng = (sb.type == SGP_SHAPE_HULL ? sgd_collide_hull(&sb, &sc, q.max_separation, &mm[0]) : sgd_collide(&sb, &sc, q.max_separation, &mm[0])) ? 1 : 0;   // normal: body -> capsule
-	for (int g = 0; g < ng; ++g) capsule_emit(d, k, j, f, g, mm[g], out, cap, count);
-}
+};
 
 // ONE WAVE PER QUERY CAPSULE (the character controller asks for one or a few per update, and waits for the answer): the candidate bodies -- the
 // large ones, and those of the broad-phase cells its bounds reach -- dealt to the 64 lanes; the mesh bodies among them (a player stands on one and
@@ -230,30 +203,13 @@ __global__ void __launch_bounds__(64) k_collide_capsules(DV d, const sgp_capsule
 	if (k >= n) return;
 	const uint32_t lane = threadIdx.x;
 	const sgp_capsule_query q = qs[k];
-	sgd_shape sc;
-	sc.pos = V3(q.pos[0], q.pos[1], q.pos[2]);
 	quat qq; qq.x = q.rot[0]; qq.y = q.rot[1]; qq.z = q.rot[2]; qq.w = q.rot[3];
-	sc.R = quat_to_m33(qq); sc.type = SGP_SHAPE_CAPSULE; sc.p0 = q.radius; sc.p1 = q.half_height; sc.p2 = 0.0f; sc.hull = nullptr;
-	const v3 ax = v3_scale(sc.R.c2, q.half_height);
-	const float e = q.radius + q.max_separation;
-	const v3 ext = V3(fabsf(ax.x) + e, fabsf(ax.y) + e, fabsf(ax.z) + e);
-	const v3 lo = v3_sub(sc.pos, ext), hi = v3_add(sc.pos, ext);
+	sgd_shape sc; v3 lo, hi;
+	capsule_shape(V3(q.pos[0], q.pos[1], q.pos[2]), qq, q.radius, q.half_height, q.max_separation, sc, lo, hi);
+	const CapsuleSink sink = { d, k, out, cap, count, mesh_list, &n_mesh };
 	if (lane == 0) n_mesh = 0;
 	__syncthreads();
-	for (uint32_t l = lane; l < d.sp->n_large; l += 64) capsule_query_body(d, q, k, sc, lo, hi, d.large_ids[l], out, cap, count, mesh_list, &n_mesh);
-	{
-		uint32_t seen = 0;      // static large bodies around the capsule, dealt to the lanes in the order the grid yields them
-		large_grid_query(d, lo, hi, [&](uint32_t i) { if ((seen++ & 63u) == lane) capsule_query_body(d, q, k, sc, lo, hi, i, out, cap, count, mesh_list, &n_mesh); });
-	}
-	const BpGrid g = *d.grid;
-	if (g.n_cells > 0 && g.min_x <= g.max_x) {
-		const int x0 = max((int)floorf((lo.x - g.ox) * g.inv_cell) - 1, 0), x1 = min((int)floorf((hi.x - g.ox) * g.inv_cell) + 1, g.nx - 1);
-		const int y0 = max((int)floorf((lo.y - g.oy) * g.inv_cell) - 1, 0), y1 = min((int)floorf((hi.y - g.oy) * g.inv_cell) + 1, g.ny - 1);
-		const int z0 = max((int)floorf((lo.z - g.oz) * g.inv_cell) - 1, 0), z1 = min((int)floorf((hi.z - g.oz) * g.inv_cell) + 1, g.nz - 1);
-		if (x0 <= x1) for (int z = z0; z <= z1; ++z) for (int y = y0; y <= y1; ++y) {
-			grid_row_runs(d, g, x0, x1, y, z, [&](uint32_t c0, uint32_t c1) { for (uint32_t c = c0 + lane; c < c1; c += 64) capsule_query_body(d, q, k, sc, lo, hi, __float_as_uint(d.sorted_max[c].w), out, cap, count, mesh_list, &n_mesh); });
-		}
-	}
+	sq_walk<64>(d, lo, hi, lane, [&](uint32_t j) { capsule_query_body(d, q.ignore_id, q.collidable_only != 0u, q.max_separation, sc, lo, hi, j, sink); });
 	__syncthreads();
 	const uint32_t nm = min(n_mesh, (uint32_t)QUERY_MESH_LIST);
 	const v3 es = V3(q.max_separation, q.max_separation, q.max_separation);
@@ -266,31 +222,13 @@ __global__ void __launch_bounds__(64) k_collide_capsules(DV d, const sgp_capsule
 			const sgd_mesh_group& grp = L.mc.g[lane];
 			sgd_manifold mm;
 			sgd_hull_reduce(grp.n, grp.p_mesh, grp.p_body, grp.np, &mm);
-			capsule_emit(d, k, mid, d.flags[mid], (int)lane, mm, out, cap, count);
+			sink.emit(mid, d.flags[mid], (int)lane, mm);
 		}
 		__syncthreads();
 	}
 }
 
-SGP_DEV void spherecast_body(const DV& d, const sgp_ray& ry, float rs, v3 o, v3 dir, uint32_t j, RayBest& best)
-{
-	if (j == ry.ignore_id) return;
-	const uint32_t f = d.flags[j];
-	if (!(f & BF_ALIVE) || (f & (BF_SENSOR | BF_ALIAS))) return;
-	const uint32_t layer = f_layer(f);
-	if (ry.collidable_only && !(layer == SGP_LAYER_NON_MOVING || layer == SGP_LAYER_MOVING)) return;
-	const float4 mn = d.aabb_min[j], mx = d.aabb_max[j];
-	const float e = rs + 1.0e-3f;
-	if (!ray_aabb(o, dir, make_float4(mn.x - e, mn.y - e, mn.z - e, 0.0f), make_float4(mx.x + e, mx.y + e, mx.z + e, 0.0f), ry.max_t)) return;      // full length: see veh_cast_test
-	const float4 sh = d.pose[POSE_F4 * (size_t)j + 3];
-	const float prm[3] = { sh.x, sh.y, sh.z };
-	v3 n, p;
-	const float t = f_shape(f) == SGP_SHAPE_MESH ? cast_sphere_mesh(d, j, o, dir, best.t, rs, &n, &p)
-	              : sgd_cast_sphere_body((int)f_shape(f), prm, f_shape(f) == SGP_SHAPE_HULL ? body_hull(d, sh) : nullptr, V3(d.pose[POSE_F4 * (size_t)j]), quat_to_m33(Q4(d.pose[POSE_F4 * (size_t)j + 1])), o, dir, best.t, rs, &n, &p);
-	if (t >= 0.0f && t <= best.t && (t < best.t || best.id == SGP_INVALID_ID || j < best.id)) { best.t = t; best.id = j; best.n = n; }
-}
-
-// one thread per cast; cells under the swept sphere's bounds (casts are short: a character's step)
+// one thread per cast (spherecast_walk, spherecast_body: sgp_dev_queries.h)
 __global__ void __launch_bounds__(64) k_spherecast(DV d, const sgp_ray* rays, const float* radii, uint32_t n, sgp_hit* hits)
 {
 	const uint32_t k = blockIdx.x * 64 + threadIdx.x;
@@ -298,26 +236,8 @@ __global__ void __launch_bounds__(64) k_spherecast(DV d, const sgp_ray* rays, co
 	const sgp_ray ry = rays[k];
 	const float rs = radii[k];
 	const v3 o = V3(ry.origin[0], ry.origin[1], ry.origin[2]), dir = V3(ry.dir[0], ry.dir[1], ry.dir[2]);
-	RayBest best; best.t = ry.max_t; best.id = SGP_INVALID_ID; best.n = V3(0.0f, 0.0f, 0.0f);
-	for (uint32_t l = 0; l < d.sp->n_large; ++l) spherecast_body(d, ry, rs, o, dir, d.large_ids[l], best);
-	{
-		// the static large bodies under the swept sphere's bounds (casts are short)
-		const v3 e = v3_add(o, v3_scale(dir, ry.max_t));
-		const float m = rs + 2.0e-3f;
-		large_grid_query(d, V3(fminf(o.x, e.x) - m, fminf(o.y, e.y) - m, fminf(o.z, e.z) - m), V3(fmaxf(o.x, e.x) + m, fmaxf(o.y, e.y) + m, fmaxf(o.z, e.z) + m),
-		                 [&](uint32_t i) { spherecast_body(d, ry, rs, o, dir, i, best); });
-	}
-	const BpGrid g = *d.grid;
-	if (g.n_cells > 0 && g.min_x <= g.max_x) {
-		const v3 e = v3_add(o, v3_scale(dir, ry.max_t));
-		const float m = rs + 1.0e-3f;
-		const int x0 = max((int)floorf((fminf(o.x, e.x) - m - g.ox) * g.inv_cell) - 1, 0), x1 = min((int)floorf((fmaxf(o.x, e.x) + m - g.ox) * g.inv_cell) + 1, g.nx - 1);
-		const int y0 = max((int)floorf((fminf(o.y, e.y) - m - g.oy) * g.inv_cell) - 1, 0), y1 = min((int)floorf((fmaxf(o.y, e.y) + m - g.oy) * g.inv_cell) + 1, g.ny - 1);
-		const int z0 = max((int)floorf((fminf(o.z, e.z) - m - g.oz) * g.inv_cell) - 1, 0), z1 = min((int)floorf((fmaxf(o.z, e.z) + m - g.oz) * g.inv_cell) + 1, g.nz - 1);
-		if (x0 <= x1) for (int z = z0; z <= z1; ++z) for (int y = y0; y <= y1; ++y) {
-			grid_row_runs(d, g, x0, x1, y, z, [&](uint32_t c0, uint32_t c1) { for (uint32_t c = c0; c < c1; ++c) spherecast_body(d, ry, rs, o, dir, __float_as_uint(d.sorted_max[c].w), best); });
-		}
-	}
+	SphereHit best; best.t = ry.max_t; best.id = SGP_INVALID_ID; best.n = V3(0.0f, 0.0f, 0.0f);
+	spherecast_walk<1>(d, o, dir, ry.max_t, rs, 0u, [&](uint32_t j) { spherecast_body(d, ry.ignore_id, ry.collidable_only != 0u, ry.max_t, rs, o, dir, j, best); });
 	sgp_hit h;
 	h.id = best.id; h.t = best.id == SGP_INVALID_ID ? 0.0f : best.t;
 	h.normal[0] = best.n.x; h.normal[1] = best.n.y; h.normal[2] = best.n.z;

@@ -35,11 +35,6 @@ SGP_DEV void sc_swept(const sgp_shape_cast& c, v3& lo, v3& hi)
 	const float g = 1.0e-6f * (c.max_t + fabsf(c.pos[0]) + fabsf(c.pos[1]) + fabsf(c.pos[2]));
 	lo = v3_sub(v3_min(lo, v3_add(lo, mv)), V3(g, g, g)); hi = v3_add(v3_max(hi, v3_add(hi, mv)), V3(g, g, g));
 }
-SGP_DEV void sc_append(const ScBufs& b, int which, uint2* list, uint32_t k, uint32_t j)
-{
-	const uint32_t at = wave_alloc(&b.ctr[which]);
-	if (at < b.pcap) list[at] = make_uint2(k, j);
-}
 SGP_DEV void sc_emit(const ScBufs& b, uint32_t k, uint32_t j, const ScHit& h, int rc)
 {
 	if (rc == 2) atomicAdd(&b.ctr[SC_N_CAPPED], 1u);
@@ -67,9 +62,9 @@ __global__ void __launch_bounds__(64) k_sc_candidates(DV d, ScBufs b)
 			uint32_t f;
 			if (!sq_passes(d, q, lo, hi, j, &f) || (f & BF_SENSOR)) return;      // (sensors never answer a cast, as for rays and sphere casts)
 			const uint32_t st = f_shape(f);
-			if (st == SGP_SHAPE_MESH) sc_append(b, SC_N_MESH, b.mesh, k, j);
-			else if (st == SGP_SHAPE_HULL || c.shape_type == SGP_SHAPE_HULL) sc_append(b, SC_N_HULL, b.hull, k, j);
-			else sc_append(b, SC_N_PRIM, b.prim, k, j);
+			if (st == SGP_SHAPE_MESH) pair_append(b.lists, &b.ctr[SC_N_MESH], b.lists.mesh, k, j);
+			else if (st == SGP_SHAPE_HULL || c.shape_type == SGP_SHAPE_HULL) pair_append(b.lists, &b.ctr[SC_N_HULL], b.lists.hull, k, j);
+			else pair_append(b.lists, &b.ctr[SC_N_PRIM], b.lists.prim, k, j);
 		});
 	}
 }
@@ -78,10 +73,10 @@ __global__ void __launch_bounds__(64) k_sc_candidates(DV d, ScBufs b)
 __global__ void __launch_bounds__(64) k_sc_pairs_prim(DV d, ScBufs b)
 {
 	__shared__ float s_clip[2 * SGD_LPOLY_FLOATS];
-	const uint32_t n = min(b.ctr[SC_N_PRIM], b.pcap);
+	const uint32_t n = min(b.ctr[SC_N_PRIM], b.lists.pcap);
 	float* clip = &s_clip[threadIdx.x];
 	for (uint32_t p = blockIdx.x * 64u + threadIdx.x; p < n; p += gridDim.x * 64u) {
-		const uint2 kj = b.prim[p];
+		const uint2 kj = b.lists.prim[p];
 		const sgp_shape_cast c = b.cs[kj.x];
 		const sgp_shape_query q = sc_as_query(c);
 		sgd_shape X; v3 lo, hi;
@@ -99,9 +94,9 @@ __global__ void __launch_bounds__(64) k_sc_pairs_prim(DV d, ScBufs b)
 // ... and the pairs with a convex hull on either side (the sequential separating-axis search: its long loops and clip buffers stay out of the kernel above)
 __global__ void __launch_bounds__(64) k_sc_pairs_hull(DV d, ScBufs b)
 {
-	const uint32_t n = min(b.ctr[SC_N_HULL], b.pcap);
+	const uint32_t n = min(b.ctr[SC_N_HULL], b.lists.pcap);
 	for (uint32_t p = blockIdx.x * 64u + threadIdx.x; p < n; p += gridDim.x * 64u) {
-		const uint2 kj = b.hull[p];
+		const uint2 kj = b.lists.hull[p];
 		const sgp_shape_cast c = b.cs[kj.x];
 		const sgp_shape_query q = sc_as_query(c);
 		sgd_shape X; v3 lo, hi;
@@ -135,11 +130,11 @@ __global__ void __launch_bounds__(64) k_sc_mesh(DV d, ScBufs b)
 {
 	__shared__ float s_lpoly[3 * SGD_LPOLY_FLOATS];
 	__shared__ ScMeshLds L;
-	const uint32_t n = min(b.ctr[SC_N_MESH], b.pcap);
+	const uint32_t n = min(b.ctr[SC_N_MESH], b.lists.pcap);
 	const uint32_t lane = threadIdx.x;
 	const sgd_box_code box_code = sgd_box_code_of(&d.hulls[0]);
 	for (uint32_t p = blockIdx.x; p < n; p += gridDim.x) {
-		const uint2 kj = b.mesh[p];
+		const uint2 kj = b.lists.mesh[p];
 		const uint32_t mid = kj.y;
 		const sgp_shape_cast c = b.cs[kj.x];
 		const sgp_shape_query q = sc_as_query(c);
@@ -244,14 +239,13 @@ __global__ void __launch_bounds__(64) k_sc_mesh(DV d, ScBufs b)
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// launch wrapper (the list kernels stride over what the lists hold when they start: their grids follow the capacity, which the host sized from the last call)
+// launch wrapper (the grids of the list kernels: list_blocks, sgp_kernels.h)
 
-static inline uint32_t sc_list_blocks(uint32_t items, uint32_t per_block, uint32_t most) { return std::min(std::max((items + per_block - 1u) / per_block, 1u), most); }
 void launch_shape_casts(const DV& d, const ScBufs& b, hipStream_t s)
 {
 	if (!b.n) return;
 	hipLaunchKernelGGL(k_sc_candidates, dim3(std::min(b.n, 65536u)), dim3(64), 0, s, d, b);
-	hipLaunchKernelGGL(k_sc_pairs_prim, dim3(sc_list_blocks(b.pcap, 64u, 4096u)), dim3(64), 0, s, d, b);
-	hipLaunchKernelGGL(k_sc_pairs_hull, dim3(sc_list_blocks(b.pcap, 64u, 4096u)), dim3(64), 0, s, d, b);
-	hipLaunchKernelGGL(k_sc_mesh, dim3(sc_list_blocks(std::min(b.pcap, 4u * b.n), 1u, 4096u)), dim3(64), 0, s, d, b);
+	hipLaunchKernelGGL(k_sc_pairs_prim, dim3(list_blocks(b.lists.pcap, 64u, 4096u)), dim3(64), 0, s, d, b);
+	hipLaunchKernelGGL(k_sc_pairs_hull, dim3(list_blocks(b.lists.pcap, 64u, 4096u)), dim3(64), 0, s, d, b);
+	hipLaunchKernelGGL(k_sc_mesh, dim3(list_blocks(std::min(b.lists.pcap, 4u * b.n), 1u, 4096u)), dim3(64), 0, s, d, b);
 }

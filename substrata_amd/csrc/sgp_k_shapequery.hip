@@ -24,24 +24,11 @@ SGP_DEV bool sq_collide_hull(const DV& d, const sgd_shape& X, float max_sep, uin
 	return sgd_collide_hull(&sb, &X, max_sep, m) != 0;
 }
 
-// how many records manifold g of a (query, body) pair gives, and the records (capsule_emit's, field by field) from slot `base` on
+// how many records manifold g of a (query, body) pair gives, and the records (contact_record: the capsule query's) from slot `base` on
 SGP_DEV int sq_num_records(const sgp_shape_query& q, int g, const sgd_manifold& m)
 {
 	if (q.flags & SGP_QUERY_DEEPEST_ONLY) return (g == 0 && m.np > 0) ? 1 : 0;
 	return m.np;
-}
-SGP_DEV void sq_record(const DV& d, uint32_t k, uint32_t j, uint32_t f, int g, const sgd_manifold& m, int i, sgp_query_contact* dst)
-{
-	sgp_query_contact c;
-	c.query = k; c.body = j; c.sub_shape = (uint32_t)(4 * g + i);      // point index for the host's sort; the host then stores the compound child index here
-	c.point[0] = m.p1[i].x; c.point[1] = m.p1[i].y; c.point[2] = m.p1[i].z;
-	c.normal[0] = m.n.x; c.normal[1] = m.n.y; c.normal[2] = m.n.z;
-	c.distance = v3_dot(v3_sub(m.p2[i], m.p1[i]), m.n);
-	v3 pv = V3(0.0f, 0.0f, 0.0f);
-	if (f_motion(f) != SGP_MOTION_STATIC) pv = v3_add(V3(d.vel[VEL_F4 * (size_t)j]), v3_cross(V3(d.vel[VEL_F4 * (size_t)j + 1]), v3_sub(m.p1[i], V3(d.pose[POSE_F4 * (size_t)j]))));
-	c.point_velocity[0] = pv.x; c.point_velocity[1] = pv.y; c.point_velocity[2] = pv.z;
-	c.motion_type = f_motion(f); c.is_sensor = (f & BF_SENSOR) ? 1u : 0u; c.inv_mass = d.pose[POSE_F4 * (size_t)j].w; c.userdata = 0;
-	*dst = c;
 }
 SGP_DEV void sq_emit_at(const DV& d, const SqBufs& b, const sgp_shape_query& q, uint32_t k, uint32_t j, uint32_t f, int g, const sgd_manifold& m, uint32_t base)
 {
@@ -52,12 +39,12 @@ SGP_DEV void sq_emit_at(const DV& d, const SqBufs& b, const sgp_shape_query& q, 
 		for (int i = 1; i < 4; ++i) if (i < m.np) { const float di = v3_dot(v3_sub(m.p2[i], m.p1[i]), m.n); if (di < bd) { bd = di; best = i; } }      // (ties: the lower point index)
 		if (base < b.cap) {
 #pragma unroll
-			for (int i = 0; i < 4; ++i) if (i == best) sq_record(d, k, j, f, g, m, i, &b.out[base]);      // (static slots: the manifold stays in registers)
+			for (int i = 0; i < 4; ++i) if (i == best) b.out[base] = contact_record(d, k, j, f, g, m, i);      // (static slots: the manifold stays in registers)
 		}
 		return;
 	}
 #pragma unroll
-	for (int i = 0; i < 4; ++i) if (i < m.np && base + (uint32_t)i < b.cap) sq_record(d, k, j, f, g, m, i, &b.out[base + (uint32_t)i]);
+	for (int i = 0; i < 4; ++i) if (i < m.np && base + (uint32_t)i < b.cap) b.out[base + (uint32_t)i] = contact_record(d, k, j, f, g, m, i);
 }
 // ... with the slots taken by this lane alone (divergent callers)
 SGP_DEV void sq_emit(const DV& d, const SqBufs& b, const sgp_shape_query& q, uint32_t k, uint32_t j, uint32_t f, int g, const sgd_manifold& m)
@@ -78,12 +65,6 @@ SGP_DEV uint32_t sq_wave_slots(uint32_t* counter, int nr)
 	base = (uint32_t)__shfl((int)base, 0, 64);
 	return base + (uint32_t)(incl - nr);
 }
-// a candidate on its list (the lanes of the wave that append to the same list at the same time share one atomic)
-SGP_DEV void sq_append(const SqBufs& b, int which, uint2* list, uint32_t k, uint32_t j)
-{
-	const uint32_t at = wave_alloc(&b.ctr[which]);
-	if (at < b.pcap) list[at] = make_uint2(k, j);
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // a wave per query
@@ -100,7 +81,7 @@ __global__ void __launch_bounds__(64) k_sq_wave(DV d, SqBufs b)
 			uint32_t f;
 			if (!sq_passes(d, q, lo, hi, j, &f)) return;
 			const uint32_t st = f_shape(f);
-			if (st == SGP_SHAPE_MESH) { sq_append(b, SQ_N_MESH, b.mesh, k, j); return; }      // (its triangles are a whole wave's work: k_sq_mesh)
+			if (st == SGP_SHAPE_MESH) { pair_append(b.lists, &b.ctr[SQ_N_MESH], b.lists.mesh, k, j); return; }      // (its triangles are a whole wave's work: k_sq_mesh)
 			sgd_manifold m;
 			const bool hit = (st == SGP_SHAPE_HULL || q.shape_type == SGP_SHAPE_HULL) ? sq_collide_hull(d, X, q.max_separation, j, f, &m) : sq_collide_prim(d, X, q.max_separation, j, f, &s_clip[lane], &m);
 			if (hit) sq_emit(d, b, q, k, j, f, 0, m);
@@ -122,9 +103,9 @@ __global__ void __launch_bounds__(64) k_sq_candidates(DV d, SqBufs b)
 		uint32_t f;
 		if (!sq_passes(d, q, lo, hi, j, &f)) return;
 		const uint32_t st = f_shape(f);
-		if (st == SGP_SHAPE_MESH) sq_append(b, SQ_N_MESH, b.mesh, k, j);
-		else if (st == SGP_SHAPE_HULL || q.shape_type == SGP_SHAPE_HULL) sq_append(b, SQ_N_HULL, b.hull, k, j);
-		else sq_append(b, SQ_N_PRIM, b.prim, k, j);
+		if (st == SGP_SHAPE_MESH) pair_append(b.lists, &b.ctr[SQ_N_MESH], b.lists.mesh, k, j);
+		else if (st == SGP_SHAPE_HULL || q.shape_type == SGP_SHAPE_HULL) pair_append(b.lists, &b.ctr[SQ_N_HULL], b.lists.hull, k, j);
+		else pair_append(b.lists, &b.ctr[SQ_N_PRIM], b.lists.prim, k, j);
 	});
 }
 
@@ -132,7 +113,7 @@ __global__ void __launch_bounds__(64) k_sq_candidates(DV d, SqBufs b)
 __global__ void __launch_bounds__(64) k_sq_pairs_prim(DV d, SqBufs b)
 {
 	__shared__ float s_clip[2 * SGD_LPOLY_FLOATS];
-	const uint32_t n = min(b.ctr[SQ_N_PRIM], b.pcap);
+	const uint32_t n = min(b.ctr[SQ_N_PRIM], b.lists.pcap);
 	const uint32_t lane = threadIdx.x;
 	for (uint32_t p0 = blockIdx.x * 64u; p0 < n; p0 += gridDim.x * 64u) {
 		const uint32_t p = p0 + lane;
@@ -140,7 +121,7 @@ __global__ void __launch_bounds__(64) k_sq_pairs_prim(DV d, SqBufs b)
 		uint2 kj = make_uint2(0u, 0u); uint32_t f = 0; int nr = 0;
 		sgp_shape_query q;
 		if (p < n) {
-			kj = b.prim[p];
+			kj = b.lists.prim[p];
 			q = b.qs[kj.x];
 			sgd_shape X; v3 lo, hi;
 			sq_shape<false>(d, q, X, lo, hi);
@@ -154,9 +135,9 @@ __global__ void __launch_bounds__(64) k_sq_pairs_prim(DV d, SqBufs b)
 // ... and the pairs with a convex hull on either side (the sequential separating-axis search: its clip buffers and long loops stay out of the kernel above)
 __global__ void __launch_bounds__(64) k_sq_pairs_hull(DV d, SqBufs b)
 {
-	const uint32_t n = min(b.ctr[SQ_N_HULL], b.pcap);
+	const uint32_t n = min(b.ctr[SQ_N_HULL], b.lists.pcap);
 	for (uint32_t p = blockIdx.x * 64u + threadIdx.x; p < n; p += gridDim.x * 64u) {
-		const uint2 kj = b.hull[p];
+		const uint2 kj = b.lists.hull[p];
 		const sgp_shape_query q = b.qs[kj.x];
 		sgd_shape X; v3 lo, hi;
 		sq_shape<false>(d, q, X, lo, hi);
@@ -172,10 +153,10 @@ __global__ void __launch_bounds__(64) k_sq_pairs_hull(DV d, SqBufs b)
 __global__ void __launch_bounds__(64) k_sq_mesh(DV d, SqBufs b)
 {
 	__shared__ MeshPairLds<64> L;
-	const uint32_t n = min(b.ctr[SQ_N_MESH], b.pcap);
+	const uint32_t n = min(b.ctr[SQ_N_MESH], b.lists.pcap);
 	const uint32_t lane = threadIdx.x;
 	for (uint32_t p = blockIdx.x; p < n; p += gridDim.x) {
-		const uint2 kj = b.mesh[p];
+		const uint2 kj = b.lists.mesh[p];
 		const sgp_shape_query q = b.qs[kj.x];
 		const uint32_t mid = kj.y;
 		sgd_shape X; v3 lo, hi;
@@ -197,20 +178,19 @@ __global__ void __launch_bounds__(64) k_sq_mesh(DV d, SqBufs b)
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// launch wrappers (the list kernels stride over what the lists hold when they start: their grids follow the capacities, which the host sized from the last call)
+// launch wrappers (the grids of the list kernels: list_blocks, sgp_kernels.h)
 
-static inline uint32_t sq_list_blocks(uint32_t items, uint32_t per_block, uint32_t most) { return std::min(std::max((items + per_block - 1u) / per_block, 1u), most); }
 void launch_shape_queries_wave(const DV& d, const SqBufs& b, hipStream_t s)
 {
 	if (!b.n) return;
 	hipLaunchKernelGGL(k_sq_wave, dim3(std::min(b.n, 65536u)), dim3(64), 0, s, d, b);
-	hipLaunchKernelGGL(k_sq_mesh, dim3(sq_list_blocks(std::min(b.pcap, 4u * b.n), 1u, 4096u)), dim3(64), 0, s, d, b);
+	hipLaunchKernelGGL(k_sq_mesh, dim3(list_blocks(std::min(b.lists.pcap, 4u * b.n), 1u, 4096u)), dim3(64), 0, s, d, b);
 }
 void launch_shape_queries_pairs(const DV& d, const SqBufs& b, hipStream_t s)
 {
 	if (!b.n) return;
 	hipLaunchKernelGGL(k_sq_candidates, dim3((b.n + 63u) / 64u), dim3(64), 0, s, d, b);
-	hipLaunchKernelGGL(k_sq_pairs_prim, dim3(sq_list_blocks(b.pcap, 64u, 4096u)), dim3(64), 0, s, d, b);
-	hipLaunchKernelGGL(k_sq_pairs_hull, dim3(sq_list_blocks(b.pcap, 64u, 4096u)), dim3(64), 0, s, d, b);
-	hipLaunchKernelGGL(k_sq_mesh, dim3(sq_list_blocks(std::min(b.pcap, 4u * b.n), 1u, 4096u)), dim3(64), 0, s, d, b);
+	hipLaunchKernelGGL(k_sq_pairs_prim, dim3(list_blocks(b.lists.pcap, 64u, 4096u)), dim3(64), 0, s, d, b);
+	hipLaunchKernelGGL(k_sq_pairs_hull, dim3(list_blocks(b.lists.pcap, 64u, 4096u)), dim3(64), 0, s, d, b);
+	hipLaunchKernelGGL(k_sq_mesh, dim3(list_blocks(std::min(b.lists.pcap, 4u * b.n), 1u, 4096u)), dim3(64), 0, s, d, b);
 }

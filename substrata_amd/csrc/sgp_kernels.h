@@ -463,11 +463,16 @@ void launch_spherecast(const DV& d, const sgp_ray* rays, const float* radii, uin
 // does not fit in `out` is counted, not written), then the candidate (query, body) pairs found per list (likewise) -- the host compares them with the capacities
 // and runs the call again with larger ones when something did not fit.
 enum { SQ_N_OUT = 0, SQ_N_PRIM = 1, SQ_N_HULL = 2, SQ_N_MESH = 3 };
+// the three candidate lists of a call (overlap queries and shape casts alike), pcap entries each: (query, body) pairs of sphere / box / capsule shapes, pairs with a
+// convex hull on either side, pairs whose body is a mesh or a height field.  The list kernels stride over what the lists hold when they start, so their grids follow
+// the capacity (list_blocks), which the host sized from the last call.
+struct PairLists { uint2* prim; uint2* hull; uint2* mesh; uint32_t pcap; };
+static inline uint32_t list_blocks(uint32_t items, uint32_t per_block, uint32_t most) { const uint32_t b = (items + per_block - 1u) / per_block; return b < 1u ? 1u : (b > most ? most : b); }
 struct SqBufs {
 	const sgp_shape_query* qs; uint32_t n;
 	sgp_query_contact* out; uint32_t cap;
 	uint32_t* ctr;
-	uint2* prim; uint2* hull; uint2* mesh; uint32_t pcap;      // pairs of sphere / box / capsule shapes, pairs with a convex hull on either side, pairs whose body is a mesh; pcap entries each
+	PairLists lists;
 };
 void launch_shape_queries_wave(const DV& d, const SqBufs& b, hipStream_t s);       // a wave per query (mesh bodies: through the mesh list, a wave per pair)
 void launch_shape_queries_pairs(const DV& d, const SqBufs& b, hipStream_t s);      // candidate pairs by a thread per query, then a thread per pair (mesh bodies: a wave per pair)
@@ -481,8 +486,9 @@ struct ScBufs {
 	const sgp_shape_cast* cs; uint32_t n;
 	sgp_cast_hit* out;
 	uint32_t* ctr;
-	uint2* prim; uint2* hull; uint2* mesh; uint32_t pcap;      // as SqBufs: sphere / box / capsule pairs, pairs with a convex hull on either side, pairs whose body is a mesh or a height field
+	PairLists lists;
 };
+static_assert(sizeof(SqBufs) == 72 && sizeof(ScBufs) == 64, "SqBufs / ScBufs: by-value kernel arguments, the lists last");
 void launch_shape_casts(const DV& d, const ScBufs& b, hipStream_t s);
 // ---- batched virtual characters (sgp_k_characters.hip, sgp_dev_character.h) -----------------------------------------------------------------------------
 // The host owns the descriptions and the inputs (CharRec, CharIn: uploaded when they change); the device owns the state (CharState, the active contacts and

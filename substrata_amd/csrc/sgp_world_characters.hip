@@ -3,8 +3,7 @@
 // already reported live on the device and are touched by the kernels of sgp_k_characters.hip alone.  An update enqueues and returns.
 #include "sgp_world_internal.h"
 
-struct sgp_characters {
-	sgp_world* w = nullptr; uint64_t world_serial = 0; int device = 0;
+struct sgp_characters : WorldBatch {
 	uint32_t cap = 0, high = 0, n_alive = 0;
 	std::vector<CharRec> rec; std::vector<CharIn> in; std::vector<uint32_t> free_list;
 	bool rec_dirty = false, in_dirty = false;
@@ -12,15 +11,11 @@ struct sgp_characters {
 	DV* d_dv = nullptr; DV dv_uploaded; bool dv_valid = false;
 	CharRec* d_rec = nullptr; CharIn* d_in = nullptr; CharState* d_st = nullptr; CharContact* d_active = nullptr; uint32_t* d_seen = nullptr;
 	CharPush* d_push = nullptr; uint32_t* d_n_push = nullptr; CharAdded* d_added = nullptr; uint32_t* d_n_added = nullptr;
-	// pinned staging of the uploads ([DV][records][inputs]); `uploaded` is recorded behind the copies that read it, and waited for before it is written again
-	char* h_up = nullptr; hipEvent_t uploaded = nullptr; bool upload_in_flight = false;
+	size_t up_rec = 0, up_in = 0;      // the pinned staging of the uploads (WorldBatch::h_up): [DV][records at up_rec][inputs at up_in]
 };
 
 // a tile's world: ghosts imported, or queued for import
 static bool world_holds_ghosts(const sgp_world* w) { return !w->ghost_map.empty() || !w->ghost_seq.empty() || !w->ghost_refresh.empty() || !w->rec_creates.empty(); }
-static bool chars_usable(const sgp_characters* cs) { return cs && cs->w && world_alive(cs->world_serial); }
-static size_t up_rec_off() { return (sizeof(DV) + 15) & ~size_t(15); }
-static size_t up_in_off(const sgp_characters* cs) { return up_rec_off() + ((sizeof(CharRec) * cs->cap + 15) & ~size_t(15)); }
 
 static CharBufs chars_bufs(const sgp_characters* cs)
 {
@@ -51,21 +46,9 @@ SGP_API void sgp_default_character_desc(sgp_character_desc* d)
 SGP_API int sgp_characters_destroy(sgp_characters* cs)
 {
 	if (!cs) return fail(SGP_ERR_INVALID, "sgp_characters_destroy: NULL");
-	hipSetDevice(cs->device);
-	if (chars_usable(cs)) hipStreamSynchronize(cs->w->stream);      // (a destroyed world has waited for its stream already)
-	void* dev[] = { cs->d_dv, cs->d_rec, cs->d_in, cs->d_st, cs->d_active, cs->d_seen, cs->d_push, cs->d_n_push, cs->d_added, cs->d_n_added };
-	for (void* p : dev) if (p) hipFree(p);
-	if (cs->h_up) hipHostFree(cs->h_up);
-	if (cs->uploaded) hipEventDestroy(cs->uploaded);
+	cs->release();
 	delete cs;
 	return SGP_OK;
-}
-
-template <typename T> static bool chars_alloc(T*& p, size_t n, hipStream_t s)
-{
-	const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-	if (hipMalloc((void**)&p, bytes) != hipSuccess) { p = nullptr; return false; }
-	return hipMemsetAsync(p, 0, bytes, s) == hipSuccess;
 }
 
 SGP_API int sgp_characters_create(sgp_world* w, uint32_t capacity, sgp_characters** out)
@@ -74,17 +57,18 @@ SGP_API int sgp_characters_create(sgp_world* w, uint32_t capacity, sgp_character
 	if (world_holds_ghosts(w)) return fail(SGP_ERR_INVALID, "sgp_characters_create: the world holds ghost bodies (characters of tiled worlds are not supported)");
 	hipSetDevice(w->device);
 	sgp_characters* cs = new sgp_characters();
-	cs->w = w; cs->world_serial = w->serial; cs->device = w->device; cs->cap = capacity;
+	cs->cap = capacity;
 	cs->rec.resize(capacity); cs->in.resize(capacity);
 	memset(cs->rec.data(), 0, sizeof(CharRec) * capacity); memset(cs->in.data(), 0, sizeof(CharIn) * capacity);
 	for (uint32_t i = 0; i < capacity; ++i) cs->in[i].ignore = SGP_INVALID_ID;
-	hipStream_t s = w->stream;
 	const size_t n = capacity;
-	bool ok = chars_alloc(cs->d_dv, 1, s) && chars_alloc(cs->d_rec, n, s) && chars_alloc(cs->d_in, n, s) && chars_alloc(cs->d_st, n, s)
-	       && chars_alloc(cs->d_active, n * SGP_CHAR_MAX_CONTACTS, s) && chars_alloc(cs->d_seen, n * SGP_CHAR_MAX_CONTACTS, s)
-	       && chars_alloc(cs->d_push, n * SGP_CHAR_MAX_PUSHES, s) && chars_alloc(cs->d_n_push, n + 1, s) && chars_alloc(cs->d_added, n * SGP_CHAR_MAX_ADDED, s) && chars_alloc(cs->d_n_added, n, s);
-	ok = ok && hipHostMalloc((void**)&cs->h_up, up_in_off(cs) + sizeof(CharIn) * n, hipHostMallocDefault) == hipSuccess;
-	ok = ok && hipEventCreateWithFlags(&cs->uploaded, hipEventDisableTiming) == hipSuccess;
+	StageCarve up;
+	up.add(sizeof(DV)); cs->up_rec = up.add(sizeof(CharRec) * n); cs->up_in = up.add(sizeof(CharIn) * n);
+	bool ok = cs->adopt(w);
+	ok = ok && cs->alloc(cs->d_dv, 1) && cs->alloc(cs->d_rec, n) && cs->alloc(cs->d_in, n) && cs->alloc(cs->d_st, n)
+	        && cs->alloc(cs->d_active, n * SGP_CHAR_MAX_CONTACTS) && cs->alloc(cs->d_seen, n * SGP_CHAR_MAX_CONTACTS)
+	        && cs->alloc(cs->d_push, n * SGP_CHAR_MAX_PUSHES) && cs->alloc(cs->d_n_push, n + 1) && cs->alloc(cs->d_added, n * SGP_CHAR_MAX_ADDED) && cs->alloc(cs->d_n_added, n);
+	ok = ok && cs->pin(up.total);
 	if (!ok) { (void)hipGetLastError(); sgp_characters_destroy(cs); return fail(SGP_ERR_HIP, "sgp_characters_create: allocation"); }
 	*out = cs;
 	return SGP_OK;
@@ -108,7 +92,7 @@ static const char* character_desc_fault(const sgp_character_desc& d)
 
 SGP_API int sgp_character_add(sgp_characters* cs, const sgp_character_desc* desc, const float pos[3], uint32_t* id_out)
 {
-	if (!chars_usable(cs) || !desc || !pos || !id_out) return fail(SGP_ERR_INVALID, "sgp_character_add: NULL, or the batch's world is gone");
+	if (!batch_usable(cs) || !desc || !pos || !id_out) return fail(SGP_ERR_INVALID, "sgp_character_add: NULL, or the batch's world is gone");
 	if (!finite3(pos)) return fail(SGP_ERR_INVALID, "sgp_character_add: non-finite position");
 	if (const char* what = character_desc_fault(*desc)) { char msg[160]; snprintf(msg, sizeof(msg), "sgp_character_add: %s", what); return fail(SGP_ERR_INVALID, msg); }
 	uint32_t id;
@@ -142,7 +126,7 @@ static bool char_live(const sgp_characters* cs, uint32_t id) { return id < cs->h
 
 SGP_API int sgp_character_remove(sgp_characters* cs, uint32_t id)
 {
-	if (!chars_usable(cs) || !char_live(cs, id)) return fail(SGP_ERR_INVALID, "sgp_character_remove: no such character");
+	if (!batch_usable(cs) || !char_live(cs, id)) return fail(SGP_ERR_INVALID, "sgp_character_remove: no such character");
 	hipSetDevice(cs->w->device);
 	HIP_TRY(hipMemsetAsync(cs->d_n_added + id, 0, sizeof(uint32_t), cs->w->stream));      // (its pending contact records go with it: the slot's next character starts with none)
 	cs->rec[id].alive = 0; cs->rec_dirty = true;
@@ -152,7 +136,7 @@ SGP_API int sgp_character_remove(sgp_characters* cs, uint32_t id)
 
 SGP_API int sgp_characters_set_pose(sgp_characters* cs, const uint32_t* ids, const float* pos, uint32_t n)
 {
-	if (!chars_usable(cs) || (n && (!ids || !pos))) return fail(SGP_ERR_INVALID, "sgp_characters_set_pose: NULL");
+	if (!batch_usable(cs) || (n && (!ids || !pos))) return fail(SGP_ERR_INVALID, "sgp_characters_set_pose: NULL");
 	for (uint32_t i = 0; i < n; ++i) if (!char_live(cs, ids[i]) || !finite3(pos + 3 * i)) return fail(SGP_ERR_INVALID, "sgp_characters_set_pose: no such character, or a non-finite position");      // (all or nothing)
 	for (uint32_t i = 0; i < n; ++i) { CharRec& r = cs->rec[ids[i]]; memcpy(r.pose, pos + 3 * i, 12); r.pose_serial++; }
 	if (n) cs->rec_dirty = true;
@@ -161,7 +145,7 @@ SGP_API int sgp_characters_set_pose(sgp_characters* cs, const uint32_t* ids, con
 
 SGP_API int sgp_characters_set_shape(sgp_characters* cs, uint32_t id, float radius, float half_height, const float offset[3])
 {
-	if (!chars_usable(cs) || !char_live(cs, id) || !offset) return fail(SGP_ERR_INVALID, "sgp_characters_set_shape: no such character");
+	if (!batch_usable(cs) || !char_live(cs, id) || !offset) return fail(SGP_ERR_INVALID, "sgp_characters_set_shape: no such character");
 	if (!std::isfinite(radius) || !std::isfinite(half_height) || !finite3(offset) || !(radius > 0.0f) || !(half_height >= 0.0f)) return fail(SGP_ERR_INVALID, "sgp_characters_set_shape: a non-finite or non-positive capsule size");
 	CharRec& r = cs->rec[id];
 	r.radius = radius; r.half_height = half_height; memcpy(r.offset, offset, 12);
@@ -171,7 +155,7 @@ SGP_API int sgp_characters_set_shape(sgp_characters* cs, uint32_t id, float radi
 
 SGP_API int sgp_characters_set_inputs(sgp_characters* cs, uint32_t first, uint32_t n, const sgp_character_input* inputs)
 {
-	if (!chars_usable(cs) || (n && !inputs)) return fail(SGP_ERR_INVALID, "sgp_characters_set_inputs: NULL");
+	if (!batch_usable(cs) || (n && !inputs)) return fail(SGP_ERR_INVALID, "sgp_characters_set_inputs: NULL");
 	if ((uint64_t)first + n > cs->high) return fail(SGP_ERR_INVALID, "sgp_characters_set_inputs: range beyond the last character");
 	for (uint32_t i = 0; i < n; ++i) {
 		if (!finite3(inputs[i].velocity)) return fail(SGP_ERR_INVALID, "sgp_characters_set_inputs: non-finite velocity");
@@ -191,36 +175,32 @@ static int chars_upload(sgp_characters* cs, bool with_dv)
 	sgp_world* w = cs->w;
 	const bool dv_dirty = with_dv && (!cs->dv_valid || memcmp(&cs->dv_uploaded, &w->dv, sizeof(DV)) != 0);
 	if (!dv_dirty && !cs->rec_dirty && !cs->in_dirty) return SGP_OK;
-	if (cs->upload_in_flight) { HIP_TRY(hipEventSynchronize(cs->uploaded)); cs->upload_in_flight = false; }
+	{ int r = cs->upload_begin(); if (r != SGP_OK) return r; }
 	if (dv_dirty) {
 		memcpy(cs->h_up, &w->dv, sizeof(DV));
 		HIP_TRY(hipMemcpyAsync(cs->d_dv, cs->h_up, sizeof(DV), hipMemcpyHostToDevice, w->stream));
 		memcpy(&cs->dv_uploaded, &w->dv, sizeof(DV)); cs->dv_valid = true;
 	}
 	if (cs->rec_dirty && cs->high) {
-		memcpy(cs->h_up + up_rec_off(), cs->rec.data(), sizeof(CharRec) * cs->high);
-		HIP_TRY(hipMemcpyAsync(cs->d_rec, cs->h_up + up_rec_off(), sizeof(CharRec) * cs->high, hipMemcpyHostToDevice, w->stream));
+		memcpy(cs->h_up + cs->up_rec, cs->rec.data(), sizeof(CharRec) * cs->high);
+		HIP_TRY(hipMemcpyAsync(cs->d_rec, cs->h_up + cs->up_rec, sizeof(CharRec) * cs->high, hipMemcpyHostToDevice, w->stream));
 	}
 	if (cs->in_dirty && cs->high) {
-		memcpy(cs->h_up + up_in_off(cs), cs->in.data(), sizeof(CharIn) * cs->high);
-		HIP_TRY(hipMemcpyAsync(cs->d_in, cs->h_up + up_in_off(cs), sizeof(CharIn) * cs->high, hipMemcpyHostToDevice, w->stream));
+		memcpy(cs->h_up + cs->up_in, cs->in.data(), sizeof(CharIn) * cs->high);
+		HIP_TRY(hipMemcpyAsync(cs->d_in, cs->h_up + cs->up_in, sizeof(CharIn) * cs->high, hipMemcpyHostToDevice, w->stream));
 	}
 	cs->rec_dirty = cs->in_dirty = false;
-	HIP_TRY(hipEventRecord(cs->uploaded, w->stream));
-	cs->upload_in_flight = true;
-	return SGP_OK;
+	return cs->upload_end();
 }
 
 SGP_API int sgp_characters_update(sgp_characters* cs, float dt)
 {
-	if (!chars_usable(cs)) return fail(SGP_ERR_INVALID, "sgp_characters_update: NULL, or the batch's world is gone");
+	if (!batch_usable(cs)) return fail(SGP_ERR_INVALID, "sgp_characters_update: NULL, or the batch's world is gone");
 	if (!std::isfinite(dt) || !(dt > 0.0f)) return fail(SGP_ERR_INVALID, "sgp_characters_update: dt must be finite and positive");
 	sgp_world* w = cs->w;
-	hipSetDevice(w->device);
 	if (world_holds_ghosts(w)) return fail(SGP_ERR_INVALID, "sgp_characters_update: the world holds ghost bodies (characters of tiled worlds are not supported)");
-	{ int r = flush_cmds(w); if (r != SGP_OK) return r; }
+	{ int r = (cs->high && cs->n_alive) ? query_prelude(w) : flush_cmds(w); if (r != SGP_OK) return r; }
 	if (!cs->high || !cs->n_alive) return SGP_OK;
-	ensure_query_grid(w);
 	{ int r = chars_upload(cs, true); if (r != SGP_OK) return r; }
 	{ int r = flush_event_reset(w); if (r != SGP_OK) return r; }      // (a push may wake a body: an activation event)
 	const CharBufs b = chars_bufs(cs);
@@ -234,7 +214,7 @@ SGP_API int sgp_characters_update(sgp_characters* cs, float dt)
 
 SGP_API int sgp_characters_get_states(sgp_characters* cs, uint32_t first, uint32_t n, sgp_character_state* out)
 {
-	if (!chars_usable(cs) || (n && !out)) return fail(SGP_ERR_INVALID, "sgp_characters_get_states: NULL, or the batch's world is gone");
+	if (!batch_usable(cs) || (n && !out)) return fail(SGP_ERR_INVALID, "sgp_characters_get_states: NULL, or the batch's world is gone");
 	if ((uint64_t)first + n > cs->cap) return fail(SGP_ERR_INVALID, "sgp_characters_get_states: range beyond the batch's capacity");
 	if (!n) return SGP_OK;
 	sgp_world* w = cs->w;
@@ -268,7 +248,7 @@ SGP_API int sgp_characters_get_states(sgp_characters* cs, uint32_t first, uint32
 
 SGP_API int sgp_characters_drain_contacts(sgp_characters* cs, sgp_character_contact* out, uint32_t cap, uint32_t* n_out)
 {
-	if (!chars_usable(cs) || (cap && !out) || !n_out) return fail(SGP_ERR_INVALID, "sgp_characters_drain_contacts: NULL, or the batch's world is gone");
+	if (!batch_usable(cs) || (cap && !out) || !n_out) return fail(SGP_ERR_INVALID, "sgp_characters_drain_contacts: NULL, or the batch's world is gone");
 	*n_out = 0;
 	if (!cs->high) return SGP_OK;
 	sgp_world* w = cs->w;

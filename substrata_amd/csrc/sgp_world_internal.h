@@ -3,9 +3,11 @@
 //   sgp_world.hip            defaults, world construction, the launch plan and the step (think), command flush, events
 //   sgp_world_bodies.hip     body lifecycle, setters, forces, read-back (addObject / setters / getters of PhysicsWorld)
 //   sgp_world_shapes.hip     meshes, convex hulls, vehicles
-//   sgp_world_queries.hip    rays, capsule queries, sphere casts
+//   sgp_world_queries.hip    rays, capsule queries, sphere casts, shape queries (sgp_collide_shapes), shape casts (sgp_cast_shapes); the query prologue
 //   sgp_world_characters.hip the batched character controller (sgp_characters_*)
 //   sgp_world_particles.hip  the batched point particles (sgp_particles_*)
+//                            (what the two batches share -- owner, zeroed device arrays, the upload fence: WorldBatch, below)
+//   sgp_stage_carve.h        the regions of one call in the stage buffer (host only, no HIP types)
 //   sgp_world_tiles.hip      ghost import / export, the tile exchange over RCCL, re-tiling
 //   sgp_world_snapshots.hip  the network snapshot codec and the de-jitter queue (host only)
 //   sgp_world_checkpoint.hip capture, rollback, the checkpoint blob and restore
@@ -27,6 +29,7 @@
 #include "sgp_kernels.h"
 #include "sgp_device_vehicle.h"
 #include "sgp_hull_build.h"
+#include "sgp_stage_carve.h"
 
 #define SGP_API extern "C" __attribute__((visibility("default")))
 
@@ -147,7 +150,7 @@ struct sgp_world {
 	uint32_t ray_server_launches = 0, ray_server_rays = 0;
 	// sgp_collide_shapes: which organisation answers (SGP_QUERY_PATH: 0 by the number of queries, 1 a wave per query, 2 candidate pairs), and what the last call
 	// needed per query -- the first guess of the next call's list and output capacities (a guess only: a call that overflows them grows them and runs again)
-	int query_path = 0; uint32_t sq_wave_max_n = 32; float sq_pairs_per_query = 2.0f, sq_out_per_query = 4.0f; uint32_t sq_reruns = 0, sq_last_n = 0, sq_last_out = 0, sq_last_pairs = 0;
+	int query_path = 0; uint32_t sq_wave_max_n = 32; float sq_pairs_per_query = 2.0f, sq_out_per_query = 4.0f; uint32_t sq_last_n = 0, sq_last_out = 0, sq_last_pairs = 0;
 	// sgp_cast_shapes: what the last call needed per cast (the first guess of the next call's list capacity), runs repeated because a list was too small, pairs that ran into the iteration cap
 	float sc_pairs_per_cast = 2.0f; uint32_t sc_reruns = 0, sc_capped = 0;
 	bool last_step_idle = false;       // the last step was skipped (every body asleep, nothing edited): no vehicle took part in it, whatever its record says
@@ -222,7 +225,52 @@ inline int ensure_stage(sgp_world* w, size_t bytes)
 	return SGP_OK;
 }
 
+// a region of the stage buffer (offsets: StageCarve) on the host and on the device
+template <class T> inline T* stage_h(sgp_world* w, size_t off) { return StageCarve::at<T>(w->stage_host, off); }
+template <class T> inline T* stage_d(sgp_world* w, size_t off) { return StageCarve::at<T>(w->stage_dev, off); }
+
 inline uint32_t next_pow2(uint32_t v) { uint32_t p = 1; while (p < v) p <<= 1; return p; }
+
+bool world_alive(uint64_t serial);      // (defined in sgp_world.hip)
+
+// What the device-resident batches of a world (sgp_characters, sgp_particles) share: who owns the batch; device arrays zeroed on the world's stream; a pinned
+// upload buffer with its fence -- `uploaded` is recorded behind the copy that reads the buffer and waited for before the buffer is written again, so that add,
+// update and clear never wait for the stream --; the destroy sequence.
+struct WorldBatch {
+	sgp_world* w = nullptr; uint64_t world_serial = 0; int device = 0;
+	std::vector<void*> dev;      // the device arrays of alloc(), freed by release()
+	char* h_up = nullptr; hipEvent_t uploaded = nullptr; bool upload_in_flight = false;
+
+	bool usable() const { return w && world_alive(world_serial); }
+	bool adopt(sgp_world* world)
+	{
+		w = world; world_serial = world->serial; device = world->device;
+		return hipEventCreateWithFlags(&uploaded, hipEventDisableTiming) == hipSuccess;
+	}
+	template <typename T> bool alloc(T*& p, size_t n)
+	{
+		const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
+		if (hipMalloc((void**)&p, bytes) != hipSuccess) { p = nullptr; return false; }
+		dev.push_back(p);
+		return hipMemsetAsync(p, 0, bytes, w->stream) == hipSuccess;
+	}
+	bool pin(size_t bytes)      // a new upload buffer (the caller has seen to it that nothing reads the old one)
+	{
+		if (h_up) { hipHostFree(h_up); h_up = nullptr; }
+		return hipHostMalloc((void**)&h_up, bytes, hipHostMallocDefault) == hipSuccess;
+	}
+	int upload_begin() { if (upload_in_flight) { HIP_TRY(hipEventSynchronize(uploaded)); upload_in_flight = false; } return SGP_OK; }      // before h_up is written
+	int upload_end() { HIP_TRY(hipEventRecord(uploaded, w->stream)); upload_in_flight = true; return SGP_OK; }                              // behind the copies that read it
+	void release()
+	{
+		hipSetDevice(device);
+		if (usable()) hipStreamSynchronize(w->stream);      // (a destroyed world has waited for its stream already)
+		for (void* p : dev) hipFree(p);
+		if (h_up) hipHostFree(h_up);
+		if (uploaded) hipEventDestroy(uploaded);
+	}
+};
+static inline bool batch_usable(const WorldBatch* b) { return b && b->usable(); }
 
 
 // ---- helpers used by several files -----------------------------------------------------------------------------------------------------------
@@ -270,7 +318,7 @@ uint64_t world_register(); void world_unregister(uint64_t serial); bool world_al
 int ensure_vehicle_capacity(sgp_world* w, uint32_t need);      // grows the vehicle arrays (device pointers change: graphs are invalidated by the caller)
 int shapes_upload_all(sgp_world* w);                           // the host mirrors of the shape tables and pools -> the device (pools grow through the usual path), DV updated, graphs invalidated
 // defined in sgp_world_queries.hip
-int query_prelude(sgp_world* w);          // flush_cmds (edits applied, the resident ray server told to leave) + ensure_query_grid: what precedes a batch of rays (sgp_raycast, sgp_particles_update)
+int query_prelude(sgp_world* w);          // flush_cmds (edits applied, the resident ray server told to leave) + ensure_query_grid: what precedes the launch of every query, characters' and particles' update
 int ensure_query_grid(sgp_world* w);      // re-bins the bodies when poses changed since the broad-phase grid was built (every query's first step after flush_cmds)
 // defined in sgp_world_bodies.hip
 int add_one(sgp_world* w, const sgp_body_desc* d, uint32_t* id_out, bool ghost);

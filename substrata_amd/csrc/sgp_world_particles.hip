@@ -3,8 +3,7 @@
 // host keeps an upper bound of the live count (what the grids cover) and learns the counts when it reads.  add, update and clear enqueue and return.
 #include "sgp_world_internal.h"
 
-struct sgp_particles {
-	sgp_world* w = nullptr; uint64_t world_serial = 0; int device = 0;
+struct sgp_particles : WorldBatch {
 	uint32_t cap = 0, ev_cap = 0;
 	uint32_t cur = 0;        // which copy of the arrays holds the live particles (every update compacts into the other one)
 	uint32_t upper = 0;      // the live count is at most this: grows with every add, exact after a read
@@ -12,11 +11,9 @@ struct sgp_particles {
 	// what the device counts said at the last read, while nothing has been enqueued since (a drain right after a read needs no wait of its own for them)
 	PsState st_host; bool st_known = false;
 	PsState* h_st = nullptr;      // pinned
-	// pinned staging of the newcomers and its device copy (both grown by add); `uploaded` is recorded behind the copy that reads the pinned buffer, and waited for before it is written again
-	sgp_particle* h_up = nullptr; sgp_particle* d_up = nullptr; uint32_t up_cap = 0; hipEvent_t uploaded = nullptr; bool upload_in_flight = false;
+	// the device copy of the newcomers' pinned staging (WorldBatch::h_up): up_cap records each, both grown by add
+	sgp_particle* d_up = nullptr; uint32_t up_cap = 0;
 };
-
-static bool particles_usable(const sgp_particles* ps) { return ps && ps->w && world_alive(ps->world_serial); }
 
 SGP_API void sgp_default_particle(sgp_particle* p)
 {
@@ -29,22 +26,11 @@ SGP_API void sgp_default_particle(sgp_particle* p)
 SGP_API int sgp_particles_destroy(sgp_particles* ps)
 {
 	if (!ps) return fail(SGP_ERR_INVALID, "sgp_particles_destroy: NULL");
-	hipSetDevice(ps->device);
-	if (particles_usable(ps)) hipStreamSynchronize(ps->w->stream);      // (a destroyed world has waited for its stream already)
-	void* dev[] = { ps->b.hot[0], ps->b.hot[1], ps->b.cold[0], ps->b.cold[1], ps->b.evw, ps->b.wg_counts, ps->b.wg_off, ps->b.st, ps->b.events, ps->d_up };
-	for (void* p : dev) if (p) hipFree(p);
-	if (ps->h_up) hipHostFree(ps->h_up);
+	ps->release();
+	if (ps->d_up) hipFree(ps->d_up);
 	if (ps->h_st) hipHostFree(ps->h_st);
-	if (ps->uploaded) hipEventDestroy(ps->uploaded);
 	delete ps;
 	return SGP_OK;
-}
-
-template <typename T> static bool particles_alloc(T*& p, size_t n, hipStream_t s)
-{
-	const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-	if (hipMalloc((void**)&p, bytes) != hipSuccess) { p = nullptr; return false; }
-	return hipMemsetAsync(p, 0, bytes, s) == hipSuccess;
 }
 
 SGP_API int sgp_particles_create(sgp_world* w, uint32_t capacity, uint32_t event_capacity, sgp_particles** out)
@@ -52,16 +38,15 @@ SGP_API int sgp_particles_create(sgp_world* w, uint32_t capacity, uint32_t event
 	if (!w || !out || capacity == 0 || capacity > SGP_PARTICLES_MAX_CAPACITY) return fail(SGP_ERR_INVALID, "sgp_particles_create: NULL world or out, or a capacity of 0 or beyond 2^20");
 	hipSetDevice(w->device);
 	sgp_particles* ps = new sgp_particles();
-	ps->w = w; ps->world_serial = w->serial; ps->device = w->device; ps->cap = capacity; ps->ev_cap = event_capacity;
+	ps->cap = capacity; ps->ev_cap = event_capacity;
 	memset(&ps->b, 0, sizeof(ps->b)); memset(&ps->st_host, 0, sizeof(ps->st_host));
 	ps->b.cap = capacity; ps->b.ev_cap = event_capacity;
-	hipStream_t s = w->stream;
 	const size_t n = capacity, blocks = (n + 63) / 64;
-	bool ok = particles_alloc(ps->b.hot[0], 2 * n, s) && particles_alloc(ps->b.hot[1], 2 * n, s) && particles_alloc(ps->b.cold[0], 2 * n, s) && particles_alloc(ps->b.cold[1], 2 * n, s)
-	       && particles_alloc(ps->b.evw, n, s) && particles_alloc(ps->b.wg_counts, blocks, s) && particles_alloc(ps->b.wg_off, blocks, s) && particles_alloc(ps->b.st, 1, s)
-	       && particles_alloc(ps->b.events, event_capacity, s);
+	bool ok = ps->adopt(w);
+	ok = ok && ps->alloc(ps->b.hot[0], 2 * n) && ps->alloc(ps->b.hot[1], 2 * n) && ps->alloc(ps->b.cold[0], 2 * n) && ps->alloc(ps->b.cold[1], 2 * n)
+	        && ps->alloc(ps->b.evw, n) && ps->alloc(ps->b.wg_counts, blocks) && ps->alloc(ps->b.wg_off, blocks) && ps->alloc(ps->b.st, 1)
+	        && ps->alloc(ps->b.events, event_capacity);
 	ok = ok && hipHostMalloc((void**)&ps->h_st, sizeof(PsState), hipHostMallocDefault) == hipSuccess;
-	ok = ok && hipEventCreateWithFlags(&ps->uploaded, hipEventDisableTiming) == hipSuccess;
 	if (!ok) { (void)hipGetLastError(); sgp_particles_destroy(ps); return fail(SGP_ERR_HIP, "sgp_particles_create: allocation"); }
 	*out = ps;
 	return SGP_OK;
@@ -82,11 +67,10 @@ static int particles_ensure_staging(sgp_particles* ps, uint32_t n)
 	if (n <= ps->up_cap) return SGP_OK;
 	HIP_TRY(hipStreamSynchronize(ps->w->stream));      // (an append in flight reads the buffers about to go)
 	ps->upload_in_flight = false;
-	if (ps->h_up) { hipHostFree(ps->h_up); ps->h_up = nullptr; }
 	if (ps->d_up) { hipFree(ps->d_up); ps->d_up = nullptr; }
 	ps->up_cap = 0;
 	const uint32_t want = std::min<uint64_t>(ps->cap, std::max<uint64_t>(256, (uint64_t)n + n / 2));
-	HIP_TRY(hipHostMalloc((void**)&ps->h_up, sizeof(sgp_particle) * (size_t)want, hipHostMallocDefault));
+	if (!ps->pin(sizeof(sgp_particle) * (size_t)want)) return fail(SGP_ERR_HIP, "hipHostMalloc", hipGetLastError());
 	HIP_TRY(hipMalloc((void**)&ps->d_up, sizeof(sgp_particle) * (size_t)want));
 	ps->up_cap = want;
 	return SGP_OK;
@@ -94,7 +78,7 @@ static int particles_ensure_staging(sgp_particles* ps, uint32_t n)
 
 SGP_API int sgp_particles_add(sgp_particles* ps, const sgp_particle* recs, uint32_t n)
 {
-	if (!particles_usable(ps) || (n && !recs)) return fail(SGP_ERR_INVALID, "sgp_particles_add: NULL, or the batch's world is gone");
+	if (!batch_usable(ps) || (n && !recs)) return fail(SGP_ERR_INVALID, "sgp_particles_add: NULL, or the batch's world is gone");
 	if (n > ps->cap) return fail(SGP_ERR_CAPACITY, "sgp_particles_add: more particles than the batch's capacity");
 	for (uint32_t k = 0; k < n; ++k) if (const char* what = particle_fault(recs[k])) {      // (all or nothing)
 		char msg[160]; snprintf(msg, sizeof(msg), "sgp_particles_add: particle %u: %s", k, what);
@@ -105,11 +89,10 @@ SGP_API int sgp_particles_add(sgp_particles* ps, const sgp_particle* recs, uint3
 	hipSetDevice(w->device);
 	ray_server_stop(w);      // (a resident ray server must not keep this call's stream work waiting)
 	{ int r = particles_ensure_staging(ps, n); if (r != SGP_OK) return r; }
-	if (ps->upload_in_flight) { HIP_TRY(hipEventSynchronize(ps->uploaded)); ps->upload_in_flight = false; }
+	{ int r = ps->upload_begin(); if (r != SGP_OK) return r; }
 	memcpy(ps->h_up, recs, sizeof(sgp_particle) * (size_t)n);
 	HIP_TRY(hipMemcpyAsync(ps->d_up, ps->h_up, sizeof(sgp_particle) * (size_t)n, hipMemcpyHostToDevice, w->stream));
-	HIP_TRY(hipEventRecord(ps->uploaded, w->stream));
-	ps->upload_in_flight = true;
+	{ int r = ps->upload_end(); if (r != SGP_OK) return r; }
 	launch_particles_append(ps->b, ps->cur, ps->d_up, n, w->stream);
 	ps->upper = (uint32_t)std::min<uint64_t>(ps->cap, (uint64_t)ps->upper + n);
 	ps->st_known = false;
@@ -119,7 +102,7 @@ SGP_API int sgp_particles_add(sgp_particles* ps, const sgp_particle* recs, uint3
 
 SGP_API int sgp_particles_update(sgp_particles* ps, float dt)
 {
-	if (!particles_usable(ps)) return fail(SGP_ERR_INVALID, "sgp_particles_update: NULL, or the batch's world is gone");
+	if (!batch_usable(ps)) return fail(SGP_ERR_INVALID, "sgp_particles_update: NULL, or the batch's world is gone");
 	if (!std::isfinite(dt) || !(dt >= 0.0f)) return fail(SGP_ERR_INVALID, "sgp_particles_update: dt must be finite and not negative");
 	sgp_world* w = ps->w;
 	{ int r = query_prelude(w); if (r != SGP_OK) return r; }
@@ -133,7 +116,7 @@ SGP_API int sgp_particles_update(sgp_particles* ps, float dt)
 
 SGP_API int sgp_particles_clear(sgp_particles* ps)
 {
-	if (!particles_usable(ps)) return fail(SGP_ERR_INVALID, "sgp_particles_clear: NULL, or the batch's world is gone");
+	if (!batch_usable(ps)) return fail(SGP_ERR_INVALID, "sgp_particles_clear: NULL, or the batch's world is gone");
 	sgp_world* w = ps->w;
 	hipSetDevice(w->device);
 	ray_server_stop(w);
@@ -144,7 +127,7 @@ SGP_API int sgp_particles_clear(sgp_particles* ps)
 
 SGP_API int sgp_particles_read(sgp_particles* ps, sgp_particle_state* out, uint32_t cap, uint32_t* n_out)
 {
-	if (!particles_usable(ps) || (cap && !out) || !n_out) return fail(SGP_ERR_INVALID, "sgp_particles_read: NULL, or the batch's world is gone");
+	if (!batch_usable(ps) || (cap && !out) || !n_out) return fail(SGP_ERR_INVALID, "sgp_particles_read: NULL, or the batch's world is gone");
 	*n_out = 0;
 	sgp_world* w = ps->w;
 	hipSetDevice(w->device);
@@ -165,7 +148,7 @@ SGP_API int sgp_particles_read(sgp_particles* ps, sgp_particle_state* out, uint3
 
 SGP_API int sgp_particles_drain_events(sgp_particles* ps, sgp_particle_event* out, uint32_t cap, uint32_t* n_out, uint32_t* n_dropped)
 {
-	if (!particles_usable(ps) || (cap && !out) || !n_out || !n_dropped) return fail(SGP_ERR_INVALID, "sgp_particles_drain_events: NULL, or the batch's world is gone");
+	if (!batch_usable(ps) || (cap && !out) || !n_out || !n_dropped) return fail(SGP_ERR_INVALID, "sgp_particles_drain_events: NULL, or the batch's world is gone");
 	*n_out = 0; *n_dropped = 0;
 	sgp_world* w = ps->w;
 	hipSetDevice(w->device);

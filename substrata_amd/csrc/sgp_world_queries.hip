@@ -1,4 +1,5 @@
-// sgp_world_queries.hip -- ray queries (PhysicsWorld::traceRay, PhysicsWorld.cpp:1668-1725), the character controller's capsule queries and sphere casts.
+// sgp_world_queries.hip -- ray queries (PhysicsWorld::traceRay, PhysicsWorld.cpp:1668-1725), the character controller's capsule queries and sphere casts, overlap
+// queries and shape casts with any convex shape.  Every entry point goes through query_prelude before it launches and lays its buffers out with StageCarve.
 #include "sgp_world_internal.h"
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -70,27 +71,29 @@ SGP_API int sgp_raycast(sgp_world* w, const sgp_ray* rays, uint32_t n, sgp_hit* 
 		if (r < 0) return r;
 		if (r == 1) { finish_hit(w, hits); return SGP_OK; }
 	}
-	const size_t rb = (sizeof(sgp_ray) * n + 15) & ~size_t(15);
-	{ int r = ensure_stage(w, rb + sizeof(sgp_hit) * n); if (r != SGP_OK) return r; }
-	memcpy(w->stage_host, rays, sizeof(sgp_ray) * n);
+	StageCarve c;
+	const size_t rays_off = c.add(sizeof(sgp_ray) * n), hits_off = c.add(sizeof(sgp_hit) * n);
+	{ int r = ensure_stage(w, c.total); if (r != SGP_OK) return r; }
+	sgp_hit* hh = stage_h<sgp_hit>(w, hits_off);
+	memcpy(stage_h<sgp_ray>(w, rays_off), rays, sizeof(sgp_ray) * n);
 	if (n <= 64) {
 		// a handful of rays (the facade's traceRay is n = 1): the kernel reads them from, and writes the hits to, the pinned host buffer
 		// directly -- one launch and one sync instead of two copies around it
-		launch_raycast(w->dv, (const sgp_ray*)w->stage_host, n, (sgp_hit*)((char*)w->stage_host + rb), w->stream);
+		launch_raycast(w->dv, stage_h<sgp_ray>(w, rays_off), n, hh, w->stream);
 		HIP_TRY(hipStreamSynchronize(w->stream));
 	} else {
-		HIP_TRY(hipMemcpyAsync(w->stage_dev, w->stage_host, sizeof(sgp_ray) * n, hipMemcpyHostToDevice, w->stream));
-		sgp_hit* dh = (sgp_hit*)((char*)w->stage_dev + rb);
-		launch_raycast(w->dv, (const sgp_ray*)w->stage_dev, n, dh, w->stream);
-		HIP_TRY(hipMemcpyAsync((char*)w->stage_host + rb, dh, sizeof(sgp_hit) * n, hipMemcpyDeviceToHost, w->stream));
+		HIP_TRY(hipMemcpyAsync(stage_d<sgp_ray>(w, rays_off), stage_h<sgp_ray>(w, rays_off), sizeof(sgp_ray) * n, hipMemcpyHostToDevice, w->stream));
+		sgp_hit* dh = stage_d<sgp_hit>(w, hits_off);
+		launch_raycast(w->dv, stage_d<sgp_ray>(w, rays_off), n, dh, w->stream);
+		HIP_TRY(hipMemcpyAsync(hh, dh, sizeof(sgp_hit) * n, hipMemcpyDeviceToHost, w->stream));
 		HIP_TRY(hipStreamSynchronize(w->stream));
 	}
-	memcpy(hits, (char*)w->stage_host + rb, sizeof(sgp_hit) * n);
+	memcpy(hits, hh, sizeof(sgp_hit) * n);
 	for (uint32_t k = 0; k < n; ++k) finish_hit(w, &hits[k]);
 	return SGP_OK;
 }
 
-// What a batch of rays needs before its launch (the batched branch of sgp_raycast, sgp_particles_update): pending body edits flushed -- which also tells
+// What every query needs before its launch (all entry points of this file, sgp_characters_update, sgp_particles_update): pending body edits flushed -- which also tells
 // a resident ray server to leave --, and the broad-phase grid valid for the poses as they are.  Nothing waits unless an edit was pending.
 int query_prelude(sgp_world* w)
 {
@@ -111,34 +114,37 @@ int ensure_query_grid(sgp_world* w)
 	return SGP_OK;
 }
 
+// The contact records of a call as the ABI reports them: the first n_sorted records sorted by (query, body, point) -- the kernels leave the contact's point
+// index in sub_shape --, then userdata and the compound's id and child index in the first n_filled of them
+static void finish_contacts(sgp_world* w, sgp_query_contact* h, uint32_t n_sorted, uint32_t n_filled)
+{
+	std::sort(h, h + n_sorted, [](const sgp_query_contact& a, const sgp_query_contact& b) {
+		if (a.query != b.query) return a.query < b.query;
+		if (a.body != b.body) return a.body < b.body;
+		return a.sub_shape < b.sub_shape; });
+	for (uint32_t i = 0; i < n_filled; ++i) { h[i].userdata = w->hb[h[i].body].userdata; h[i].body = compound_id_of(w, h[i].body, &h[i].sub_shape); }
+}
+
 // CharacterVirtual's CollideShape (PlayerPhysics.cpp:258-353): contacts of capsules with everything within max_separation
 SGP_API int sgp_collide_capsules(sgp_world* w, const sgp_capsule_query* qs, uint32_t n, sgp_query_contact* out, uint32_t cap, uint32_t* n_out)
 {
 	if (!w || (!qs && n) || (!out && cap) || !n_out) return fail(SGP_ERR_INVALID, "sgp_collide_capsules: NULL");
-	hipSetDevice(w->device);
-	{ int r = flush_cmds(w); if (r != SGP_OK) return r; }
+	{ int r = n ? query_prelude(w) : flush_cmds(w); if (r != SGP_OK) return r; }
 	*n_out = 0;
 	if (!n) return SGP_OK;
-	ensure_query_grid(w);
-	const size_t qb = (sizeof(sgp_capsule_query) * n + 15) & ~size_t(15);
-	const size_t ob = sizeof(sgp_query_contact) * std::max(cap, 1u);
-	{ int r = ensure_stage(w, qb + ob + 16); if (r != SGP_OK) return r; }
-	memcpy(w->stage_host, qs, sizeof(sgp_capsule_query) * n);
-	HIP_TRY(hipMemcpyAsync(w->stage_dev, w->stage_host, sizeof(sgp_capsule_query) * n, hipMemcpyHostToDevice, w->stream));
-	sgp_query_contact* dout = (sgp_query_contact*)((char*)w->stage_dev + qb);
-	uint32_t* dcount = (uint32_t*)((char*)w->stage_dev + qb + ob);
-	HIP_TRY(hipMemsetAsync(dcount, 0, sizeof(uint32_t), w->stream));
-	launch_collide_capsules(w->dv, (const sgp_capsule_query*)w->stage_dev, n, dout, cap, dcount, w->stream);
-	HIP_TRY(hipMemcpyAsync((char*)w->stage_host + qb, dout, ob + 16, hipMemcpyDeviceToHost, w->stream));
+	StageCarve c;
+	const size_t q_off = c.add(sizeof(sgp_capsule_query) * n), out_off = c.add(sizeof(sgp_query_contact) * std::max(cap, 1u)), count_off = c.add(16);
+	{ int r = ensure_stage(w, c.total); if (r != SGP_OK) return r; }
+	memcpy(stage_h<char>(w, q_off), qs, sizeof(sgp_capsule_query) * n);
+	HIP_TRY(hipMemcpyAsync(stage_d<char>(w, q_off), stage_h<char>(w, q_off), sizeof(sgp_capsule_query) * n, hipMemcpyHostToDevice, w->stream));
+	HIP_TRY(hipMemsetAsync(stage_d<uint32_t>(w, count_off), 0, sizeof(uint32_t), w->stream));
+	launch_collide_capsules(w->dv, stage_d<sgp_capsule_query>(w, q_off), n, stage_d<sgp_query_contact>(w, out_off), cap, stage_d<uint32_t>(w, count_off), w->stream);
+	HIP_TRY(hipMemcpyAsync(stage_h<char>(w, out_off), stage_d<char>(w, out_off), c.total - out_off, hipMemcpyDeviceToHost, w->stream));      // (the records and the count behind them)
 	HIP_TRY(hipStreamSynchronize(w->stream));
-	const uint32_t cnt = *(const uint32_t*)((char*)w->stage_host + qb + ob);
+	const uint32_t cnt = *stage_h<uint32_t>(w, count_off);
 	const uint32_t m = std::min(cnt, cap);
-	sgp_query_contact* h = (sgp_query_contact*)((char*)w->stage_host + qb);
-	std::sort(h, h + m, [](const sgp_query_contact& a, const sgp_query_contact& b) {
-		if (a.query != b.query) return a.query < b.query;
-		if (a.body != b.body) return a.body < b.body;
-		return a.sub_shape < b.sub_shape; });         // (the kernel leaves the contact's point index in this field)
-	for (uint32_t i = 0; i < m; ++i) { h[i].userdata = w->hb[h[i].body].userdata; h[i].body = compound_id_of(w, h[i].body, &h[i].sub_shape); }
+	sgp_query_contact* h = stage_h<sgp_query_contact>(w, out_off);
+	finish_contacts(w, h, m, m);
 	memcpy(out, h, sizeof(sgp_query_contact) * m);
 	*n_out = cnt;
 	return SGP_OK;
@@ -164,6 +170,31 @@ static const char* shape_query_fault(const sgp_world* w, const sgp_shape_query& 
 	}
 }
 
+// One run of a call with candidate lists (sgp_collide_shapes, sgp_cast_shapes): the stage buffer carved into [records][counters][out][three lists of pcap pairs],
+// the records uploaded, the counters zeroed, launch(records, counters, out, lists) on the device's regions, the counters read back into ctr (the call's one wait).
+// Returns through *most the longest list the kernels counted -- above pcap the caller grows pcap and runs the call again, by its own rule -- and through *out_off
+// where `out` lies in both buffers.
+template <class Launch> static int run_list_call(sgp_world* w, const void* recs, size_t rec_bytes, uint32_t* ctr, size_t ctr_bytes, size_t out_bytes, uint64_t pcap, size_t* out_off, uint32_t* most, Launch launch)
+{
+	StageCarve c;
+	const size_t rec_off = c.add(rec_bytes), ctr_off = c.add(ctr_bytes);
+	*out_off = c.add(out_bytes);
+	const size_t lists_off = c.add(3 * sizeof(uint2) * (size_t)pcap);
+	{ int r = ensure_stage(w, c.total); if (r != SGP_OK) return r; }
+	memcpy(stage_h<char>(w, rec_off), recs, rec_bytes);
+	HIP_TRY(hipMemcpyAsync(stage_d<char>(w, rec_off), stage_h<char>(w, rec_off), rec_bytes, hipMemcpyHostToDevice, w->stream));
+	PairLists lists;
+	lists.prim = stage_d<uint2>(w, lists_off); lists.hull = lists.prim + pcap; lists.mesh = lists.hull + pcap; lists.pcap = (uint32_t)pcap;
+	HIP_TRY(hipMemsetAsync(stage_d<char>(w, ctr_off), 0, ctr_bytes, w->stream));
+	launch(stage_d<char>(w, rec_off), stage_d<uint32_t>(w, ctr_off), stage_d<char>(w, *out_off), lists);
+	HIP_TRY(hipMemcpyAsync(stage_h<char>(w, ctr_off), stage_d<char>(w, ctr_off), ctr_bytes, hipMemcpyDeviceToHost, w->stream));
+	HIP_TRY(hipStreamSynchronize(w->stream));
+	memcpy(ctr, stage_h<char>(w, ctr_off), ctr_bytes);
+	*most = std::max(ctr[SQ_N_PRIM], std::max(ctr[SQ_N_HULL], ctr[SQ_N_MESH]));
+	return SGP_OK;
+}
+static_assert(SQ_N_PRIM == SC_N_PRIM && SQ_N_HULL == SC_N_HULL && SQ_N_MESH == SC_N_MESH, "run_list_call reads the list counters of either call");
+
 SGP_API int sgp_collide_shapes(sgp_world* w, const sgp_shape_query* qs, uint32_t n, sgp_query_contact* out, uint32_t cap, uint32_t* n_out)
 {
 	if (!w || (!qs && n) || (!out && cap) || !n_out) return fail(SGP_ERR_INVALID, "sgp_collide_shapes: NULL");
@@ -171,62 +202,40 @@ SGP_API int sgp_collide_shapes(sgp_world* w, const sgp_shape_query* qs, uint32_t
 		char msg[160]; snprintf(msg, sizeof(msg), "sgp_collide_shapes: query %u: %s", k, what);
 		return fail(SGP_ERR_INVALID, msg);
 	}
-	hipSetDevice(w->device);
-	{ int r = flush_cmds(w); if (r != SGP_OK) return r; }
+	{ int r = n ? query_prelude(w) : flush_cmds(w); if (r != SGP_OK) return r; }
 	*n_out = 0;
 	if (!n) return SGP_OK;
-	ensure_query_grid(w);
 	const bool by_wave = w->query_path == 1 || (w->query_path == 0 && n <= w->sq_wave_max_n);
 	// Capacities: a first guess from what the last call needed per query.  The kernels count everything they find, also what did not fit; a call that overflowed
 	// a list or the output runs again with room for what was counted (a list that overflowed hid some of the output: that run may be followed by one more).
-	const size_t qb = (sizeof(sgp_shape_query) * n + 15) & ~size_t(15);
 	uint64_t ocap = std::max<uint64_t>(64, (uint64_t)((double)w->sq_out_per_query * n) + 1), pcap = std::max<uint64_t>(64, (uint64_t)((double)w->sq_pairs_per_query * n) + 1);
 	if (n == w->sq_last_n) { ocap = std::max<uint64_t>(ocap, w->sq_last_out + w->sq_last_out / 4); pcap = std::max<uint64_t>(pcap, w->sq_last_pairs + w->sq_last_pairs / 4); }      // (the same batch again, as every frame: what it needed last time)
-	uint32_t ctr[4] = { 0, 0, 0, 0 };
+	uint32_t ctr[4] = { 0, 0, 0, 0 }, most = 0;
 	size_t out_off = 0;
 	for (int attempt = 0;; ++attempt) {
 		if (attempt == 6) return fail(SGP_ERR_CAPACITY, "sgp_collide_shapes: the answer kept outgrowing its buffers");      // (cannot happen while the world stands still: the counts are exact)
 		if (ocap > 0x7FFFFFFFull || pcap > 0x7FFFFFFFull) return fail(SGP_ERR_CAPACITY, "sgp_collide_shapes: more than 2^31 contacts or candidate pairs");
-		out_off = qb + 16;
-		const size_t lists_off = out_off + sizeof(sgp_query_contact) * (size_t)ocap;
-		{ int r = ensure_stage(w, lists_off + 3 * sizeof(uint2) * (size_t)pcap); if (r != SGP_OK) return r; }
-		memcpy(w->stage_host, qs, sizeof(sgp_shape_query) * n);
-		HIP_TRY(hipMemcpyAsync(w->stage_dev, w->stage_host, sizeof(sgp_shape_query) * n, hipMemcpyHostToDevice, w->stream));
-		char* dev = (char*)w->stage_dev;
-		SqBufs b;
-		b.qs = (const sgp_shape_query*)dev; b.n = n;
-		b.ctr = (uint32_t*)(dev + qb);
-		b.out = (sgp_query_contact*)(dev + out_off); b.cap = (uint32_t)ocap;
-		b.prim = (uint2*)(dev + lists_off); b.hull = b.prim + pcap; b.mesh = b.hull + pcap; b.pcap = (uint32_t)pcap;
-		HIP_TRY(hipMemsetAsync(b.ctr, 0, 16, w->stream));
-		if (by_wave) launch_shape_queries_wave(w->dv, b, w->stream); else launch_shape_queries_pairs(w->dv, b, w->stream);
-		HIP_TRY(hipMemcpyAsync((char*)w->stage_host + qb, b.ctr, 16, hipMemcpyDeviceToHost, w->stream));
-		HIP_TRY(hipStreamSynchronize(w->stream));
-		memcpy(ctr, (char*)w->stage_host + qb, 16);
-		const uint32_t most = std::max(ctr[SQ_N_PRIM], std::max(ctr[SQ_N_HULL], ctr[SQ_N_MESH]));
+		const int r = run_list_call(w, qs, sizeof(sgp_shape_query) * n, ctr, sizeof(ctr), sizeof(sgp_query_contact) * (size_t)ocap, pcap, &out_off, &most, [&](char* recs, uint32_t* dctr, char* dout, const PairLists& lists) {
+			SqBufs b;
+			b.qs = (const sgp_shape_query*)recs; b.n = n; b.out = (sgp_query_contact*)dout; b.cap = (uint32_t)ocap; b.ctr = dctr; b.lists = lists;
+			if (by_wave) launch_shape_queries_wave(w->dv, b, w->stream); else launch_shape_queries_pairs(w->dv, b, w->stream);
+		});
+		if (r != SGP_OK) return r;
 		if (ctr[SQ_N_OUT] <= ocap && most <= pcap) break;
-		w->sq_reruns++;
 		if (most > pcap) { ocap = std::max<uint64_t>(ocap, (uint64_t)ctr[SQ_N_OUT] * 2u); pcap = most; }
 		else ocap = ctr[SQ_N_OUT];
 	}
 	const uint32_t cnt = ctr[SQ_N_OUT];
-	{
-		const uint32_t most = std::max(ctr[SQ_N_PRIM], std::max(ctr[SQ_N_HULL], ctr[SQ_N_MESH]));
-		// (per query at most 8: one huge volume must not size the buffers of the next call's thousands of small ones)
-		w->sq_out_per_query = std::min(8.0f, 1.25f * (float)cnt / (float)n + 1.0f); w->sq_pairs_per_query = std::min(8.0f, 1.25f * (float)most / (float)n + 1.0f);
-		w->sq_last_n = n; w->sq_last_out = cnt; w->sq_last_pairs = most;
-	}
-	sgp_query_contact* h = (sgp_query_contact*)((char*)w->stage_host + out_off);
+	// (per query at most 8: one huge volume must not size the buffers of the next call's thousands of small ones)
+	w->sq_out_per_query = std::min(8.0f, 1.25f * (float)cnt / (float)n + 1.0f); w->sq_pairs_per_query = std::min(8.0f, 1.25f * (float)most / (float)n + 1.0f);
+	w->sq_last_n = n; w->sq_last_out = cnt; w->sq_last_pairs = most;
+	sgp_query_contact* h = stage_h<sgp_query_contact>(w, out_off);
 	if (cnt) {
-		HIP_TRY(hipMemcpyAsync(h, (char*)w->stage_dev + out_off, sizeof(sgp_query_contact) * (size_t)cnt, hipMemcpyDeviceToHost, w->stream));
+		HIP_TRY(hipMemcpyAsync(h, stage_d<char>(w, out_off), sizeof(sgp_query_contact) * (size_t)cnt, hipMemcpyDeviceToHost, w->stream));
 		HIP_TRY(hipStreamSynchronize(w->stream));
 	}
-	std::sort(h, h + cnt, [](const sgp_query_contact& a, const sgp_query_contact& b) {
-		if (a.query != b.query) return a.query < b.query;
-		if (a.body != b.body) return a.body < b.body;
-		return a.sub_shape < b.sub_shape; });         // (the kernels leave the contact's point index in this field)
 	const uint32_t m = std::min(cnt, cap);      // the FIRST cap records of the whole sorted answer
-	for (uint32_t i = 0; i < m; ++i) { h[i].userdata = w->hb[h[i].body].userdata; h[i].body = compound_id_of(w, h[i].body, &h[i].sub_shape); }
+	finish_contacts(w, h, cnt, m);
 	if (m) memcpy(out, h, sizeof(sgp_query_contact) * m);
 	*n_out = cnt;
 	return SGP_OK;
@@ -252,47 +261,33 @@ SGP_API int sgp_cast_shapes(sgp_world* w, const sgp_shape_cast* cs, uint32_t n, 
 		char msg[160]; snprintf(msg, sizeof(msg), "sgp_cast_shapes: cast %u: %s", k, what);
 		return fail(SGP_ERR_INVALID, msg);
 	}
-	hipSetDevice(w->device);
-	{ int r = flush_cmds(w); if (r != SGP_OK) return r; }
+	{ int r = n ? query_prelude(w) : flush_cmds(w); if (r != SGP_OK) return r; }
 	if (!n) return SGP_OK;
-	ensure_query_grid(w);
 	// Capacity of the three candidate lists: a first guess from what the last call needed per cast.  The kernels count every candidate they find, also what did not
 	// fit; a call that overflowed a list runs again with room for what was counted (the counts are exact while the world stands still: one more run at most).
-	const size_t cb = (sizeof(sgp_shape_cast) * n + 15) & ~size_t(15);
 	uint64_t pcap = std::max<uint64_t>(64, (uint64_t)((double)w->sc_pairs_per_cast * n) + 1);
-	uint32_t ctr[SC_N_CTR];
+	uint32_t ctr[SC_N_CTR], most = 0;
 	size_t out_off = 0;
 	for (int attempt = 0;; ++attempt) {
 		if (attempt == 4) return fail(SGP_ERR_CAPACITY, "sgp_cast_shapes: the candidate lists kept outgrowing their buffers");
 		if (pcap > 0x3FFFFFFFull) return fail(SGP_ERR_CAPACITY, "sgp_cast_shapes: more than 2^30 candidate pairs");
-		out_off = cb + sizeof(uint32_t) * SC_N_CTR;
-		const size_t lists_off = out_off + sizeof(sgp_cast_hit) * 3 * (size_t)pcap;
-		{ int r = ensure_stage(w, lists_off + 3 * sizeof(uint2) * (size_t)pcap); if (r != SGP_OK) return r; }
-		memcpy(w->stage_host, cs, sizeof(sgp_shape_cast) * n);
-		HIP_TRY(hipMemcpyAsync(w->stage_dev, w->stage_host, sizeof(sgp_shape_cast) * n, hipMemcpyHostToDevice, w->stream));
-		char* dev = (char*)w->stage_dev;
-		ScBufs b;
-		b.cs = (const sgp_shape_cast*)dev; b.n = n;
-		b.ctr = (uint32_t*)(dev + cb);
-		b.out = (sgp_cast_hit*)(dev + out_off);
-		b.prim = (uint2*)(dev + lists_off); b.hull = b.prim + pcap; b.mesh = b.hull + pcap; b.pcap = (uint32_t)pcap;
-		HIP_TRY(hipMemsetAsync(b.ctr, 0, sizeof(uint32_t) * SC_N_CTR, w->stream));
-		launch_shape_casts(w->dv, b, w->stream);
-		HIP_TRY(hipMemcpyAsync((char*)w->stage_host + cb, b.ctr, sizeof(uint32_t) * SC_N_CTR, hipMemcpyDeviceToHost, w->stream));
-		HIP_TRY(hipStreamSynchronize(w->stream));
-		memcpy(ctr, (char*)w->stage_host + cb, sizeof(ctr));
-		const uint32_t most = std::max(ctr[SC_N_PRIM], std::max(ctr[SC_N_HULL], ctr[SC_N_MESH]));
+		const int r = run_list_call(w, cs, sizeof(sgp_shape_cast) * n, ctr, sizeof(ctr), sizeof(sgp_cast_hit) * 3 * (size_t)pcap, pcap, &out_off, &most, [&](char* recs, uint32_t* dctr, char* dout, const PairLists& lists) {
+			ScBufs b;
+			b.cs = (const sgp_shape_cast*)recs; b.n = n; b.out = (sgp_cast_hit*)dout; b.ctr = dctr; b.lists = lists;
+			launch_shape_casts(w->dv, b, w->stream);
+		});
+		if (r != SGP_OK) return r;
 		if (most <= pcap) break;
 		w->sc_reruns++;
 		pcap = most;
 	}
 	if (ctr[SC_N_DROPPED]) return fail(SGP_ERR_CAPACITY, "sgp_cast_shapes: a mesh tree is deeper than the walk's stack");
 	w->sc_capped += ctr[SC_N_CAPPED];
-	w->sc_pairs_per_cast = std::min(16.0f, 1.25f * (float)std::max(ctr[SC_N_PRIM], std::max(ctr[SC_N_HULL], ctr[SC_N_MESH])) / (float)n + 1.0f);
+	w->sc_pairs_per_cast = std::min(16.0f, 1.25f * (float)most / (float)n + 1.0f);
 	const uint32_t cnt = ctr[SC_N_OUT];
-	const sgp_cast_hit* h = (const sgp_cast_hit*)((char*)w->stage_host + out_off);
+	sgp_cast_hit* h = stage_h<sgp_cast_hit>(w, out_off);
 	if (cnt) {
-		HIP_TRY(hipMemcpyAsync((char*)w->stage_host + out_off, (char*)w->stage_dev + out_off, sizeof(sgp_cast_hit) * (size_t)cnt, hipMemcpyDeviceToHost, w->stream));
+		HIP_TRY(hipMemcpyAsync(h, stage_d<char>(w, out_off), sizeof(sgp_cast_hit) * (size_t)cnt, hipMemcpyDeviceToHost, w->stream));
 		HIP_TRY(hipStreamSynchronize(w->stream));
 	}
 	// per cast the least record by (t, id, triangle): whatever order the records arrived in
@@ -322,25 +317,18 @@ SGP_API int sgp_cast_shapes_counters(sgp_world* w, uint32_t counters_out[2])
 SGP_API int sgp_spherecast(sgp_world* w, const sgp_ray* rays, const float* radii, uint32_t n, sgp_hit* hits)
 {
 	if (!w || (n && (!rays || !radii || !hits))) return fail(SGP_ERR_INVALID, "sgp_spherecast: NULL");
-	hipSetDevice(w->device);
-	{ int r = flush_cmds(w); if (r != SGP_OK) return r; }
+	{ int r = n ? query_prelude(w) : flush_cmds(w); if (r != SGP_OK) return r; }
 	if (!n) return SGP_OK;
-	ensure_query_grid(w);
-	const size_t rb = (sizeof(sgp_ray) * n + 15) & ~size_t(15), fb = (sizeof(float) * n + 15) & ~size_t(15);
-	{ int r = ensure_stage(w, rb + fb + sizeof(sgp_hit) * n); if (r != SGP_OK) return r; }
-	memcpy(w->stage_host, rays, sizeof(sgp_ray) * n);
-	memcpy((char*)w->stage_host + rb, radii, sizeof(float) * n);
-	HIP_TRY(hipMemcpyAsync(w->stage_dev, w->stage_host, rb + sizeof(float) * n, hipMemcpyHostToDevice, w->stream));
-	sgp_hit* dh = (sgp_hit*)((char*)w->stage_dev + rb + fb);
-	launch_spherecast(w->dv, (const sgp_ray*)w->stage_dev, (const float*)((char*)w->stage_dev + rb), n, dh, w->stream);
-	HIP_TRY(hipMemcpyAsync((char*)w->stage_host + rb + fb, dh, sizeof(sgp_hit) * n, hipMemcpyDeviceToHost, w->stream));
+	StageCarve c;
+	const size_t rays_off = c.add(sizeof(sgp_ray) * n), radii_off = c.add(sizeof(float) * n), hits_off = c.add(sizeof(sgp_hit) * n);
+	{ int r = ensure_stage(w, c.total); if (r != SGP_OK) return r; }
+	memcpy(stage_h<char>(w, rays_off), rays, sizeof(sgp_ray) * n);
+	memcpy(stage_h<char>(w, radii_off), radii, sizeof(float) * n);
+	HIP_TRY(hipMemcpyAsync(stage_d<char>(w, rays_off), stage_h<char>(w, rays_off), radii_off + sizeof(float) * n - rays_off, hipMemcpyHostToDevice, w->stream));      // (the rays and the radii behind them)
+	launch_spherecast(w->dv, stage_d<sgp_ray>(w, rays_off), stage_d<float>(w, radii_off), n, stage_d<sgp_hit>(w, hits_off), w->stream);
+	HIP_TRY(hipMemcpyAsync(stage_h<char>(w, hits_off), stage_d<char>(w, hits_off), sizeof(sgp_hit) * n, hipMemcpyDeviceToHost, w->stream));
 	HIP_TRY(hipStreamSynchronize(w->stream));
-	memcpy(hits, (char*)w->stage_host + rb + fb, sizeof(sgp_hit) * n);
-	for (uint32_t k = 0; k < n; ++k) {
-		hits[k].userdata = hits[k].id != SGP_INVALID_ID ? w->hb[hits[k].id].userdata : 0;
-		hits[k].sub_shape = 0;
-		if (hits[k].id != SGP_INVALID_ID) hits[k].id = compound_id_of(w, hits[k].id, &hits[k].sub_shape);
-	}
+	memcpy(hits, stage_h<char>(w, hits_off), sizeof(sgp_hit) * n);
+	for (uint32_t k = 0; k < n; ++k) finish_hit(w, &hits[k]);
 	return SGP_OK;
 }
-

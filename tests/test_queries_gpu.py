@@ -102,6 +102,102 @@ def test_capsule_queries_on_a_mesh_with_active_edges_match_oracle(oracle):
     tw.close()
 
 
+def _walk_scene(w):
+    """All three sources of candidates of the queries' walk (sq_walk) in one small scene: 36 static large tiles (at least 32 of them: the static large bodies'
+    grid), one moving large body (the linear list of large bodies) and 40 small bodies (the cell rows).  Never stepped: the bodies hang where they are put."""
+    rng = np.random.default_rng(17)
+    tiles = scenes._blank(36)
+    gx, gy = np.meshgrid(np.arange(6), np.arange(6), indexing="ij")
+    tiles["pos"][:, 0] = -5.0 + 2.0 * gx.ravel(); tiles["pos"][:, 1] = -5.0 + 2.0 * gy.ravel(); tiles["pos"][:, 2] = 0.25 + 0.05 * (np.arange(36) % 4)
+    tiles["shape"][:, :3] = (0.95, 0.95, 0.25)
+    mover = scenes.dynamic_bodies(1)
+    mover["motion_type"] = abi.MOTION_KINEMATIC; mover["shape"][0, :3] = (1.2, 0.4, 0.8); mover["pos"][0] = (0.3, 0.2, 1.6); mover["lin_vel"][0] = (0.5, 0.0, 0.0)
+    small = scenes.dynamic_bodies(40)
+    small["pos"] = rng.uniform([-5, -5, 0.8], [5, 5, 2.2], size=(40, 3)); small["shape"][:, :3] = rng.uniform(0.15, 0.3, size=(40, 3))
+    small["shape_type"][::2] = abi.SHAPE_SPHERE
+    ids = w.add_batch(np.concatenate([tiles, mover, small]))
+    assert np.array_equal(ids, np.arange(77))
+    return range(0, 36), 36, range(37, 77)
+
+
+def test_the_walk_agrees_between_its_one_lane_and_wave_instances_and_between_capsule_entry_points():
+    """sq_walk's instances against each other, bit for bit, where all three sources of candidates answer.  (1) Its two-bounds form: sgp_spherecast (one lane takes
+    every candidate) against the sweep of a character of a batch (the candidates dealt to 64 lanes) along the same segment.  A character with no contact at its
+    start, one collision iteration and a capsule of half height 0 moves by velocity * dt * min(len, max(0, t - padding)) / len, t being the sphere cast's answer
+    over len + padding when that hit faces the motion (char_sweep_fraction): the expected position is evaluated here in fp32 from sgp_spherecast's hit.
+    (2) Its one-bounds form: sgp_collide_capsules for one capsule against the capsule-typed sgp_collide_shapes in both organisations."""
+    from test_shape_queries_gpu import make_world, capsule_as_shape, assert_records_equal_bitwise
+    f = np.float32
+    worlds = {path: make_world(path, max_bodies=256, large_body_radius=1.0) for path in ("wave", "pairs")}
+    for w in worlds.values():
+        tile_ids, mover_id, small_ids = _walk_scene(w)
+    w = worlds["wave"]
+    rng = np.random.default_rng(3)
+
+    # (1) the starts: free of contacts within the character's reach (so that no constraint touches the velocity)
+    radius, padding, predictive, dt = f(0.3), f(0.02), f(0.1), f(0.05)
+    n = 160
+    start = rng.uniform([-5, -5, 1.0], [5, 5, 3.0], size=(n, 3))
+    start[:48] = rng.uniform([-1.8, -1.4, 1.0], [2.4, 1.8, 3.3], size=(48, 3))      # (a good share of them around the moving large body)
+    start = start.astype(f)
+    vel = (rng.normal(size=(n, 3)) * (0.6, 0.6, 0.3) + (0, 0, -0.8)); vel = (vel / np.linalg.norm(vel, axis=1, keepdims=True) * rng.uniform(10.0, 30.0, size=(n, 1))).astype(f)
+    q = np.zeros(n, dtype=abi.capsule_query_dtype)
+    q["pos"] = start; q["rot"] = (0, 0, 0, 1); q["radius"] = radius; q["half_height"] = 0.0; q["max_separation"] = 0.13; q["ignore_id"] = abi.INVALID_ID; q["collidable_only"] = 1
+    touched = np.unique(w.collide_capsules(q, cap=16384)["query"])
+    free = np.setdiff1d(np.arange(n), touched)[:64]
+    assert len(free) == 64
+    start, vel = start[free], vel[free]
+    disp = vel * dt                                                                   # solveConstraints without constraints: 0 + velocity * time
+    length = np.sqrt(disp[:, 0] * disp[:, 0] + disp[:, 1] * disp[:, 1] + disp[:, 2] * disp[:, 2])
+    direction = disp * (f(1.0) / length)[:, None]
+    rays = np.zeros(64, dtype=abi.ray_dtype)
+    rays["origin"] = start; rays["dir"] = direction; rays["max_t"] = length + padding; rays["ignore_id"] = abi.INVALID_ID; rays["collidable_only"] = 1
+    hits = w.spherecast(rays, np.full(64, radius, f))
+    hit = hits["id"] != abi.INVALID_ID
+    hn = hits["normal"]
+    facing = (hn[:, 0] * direction[:, 0] + hn[:, 1] * direction[:, 1] + hn[:, 2] * direction[:, 2]) < f(-0.05)
+    stops = hit & (hits["t"] > f(1.0e-5)) & facing
+    travel = np.where(stops, np.minimum(length, np.maximum(f(0.0), hits["t"] - padding)), length)
+    expected = start + disp * (travel / length)[:, None]
+    assert expected.dtype == np.float32
+    # every source of candidates stopped somebody, and somebody went the whole way
+    stoppers = set(hits["id"][stops].tolist())
+    assert stoppers & set(tile_ids) and mover_id in stoppers and stoppers & set(small_ids) and (~hit).any(), sorted(stoppers)
+
+    cs = w.characters(64)
+    d = cs.default_desc()
+    d.radius = float(radius); d.half_height = 0.0; d.up[:] = (0.0, 0.0, 1.0); d.character_padding = float(padding); d.predictive_contact_distance = float(predictive)
+    d.max_collision_iterations = 1
+    for p in start:
+        cs.add(d, p)
+    inp = np.zeros(64, dtype=abi.character_input_dtype)
+    inp["velocity"] = vel; inp["ignore_id"] = abi.INVALID_ID; inp["flags"] = 0      # CharacterVirtual::Update: no stick-to-floor, no stairs
+    cs.set_inputs(0, inp)
+    cs.update(float(dt))
+    got = cs.states(0, 64)
+    cs.close()
+    assert not got["overflow"].any()
+    assert got["pos"].tobytes() == expected.tobytes(), np.abs(got["pos"] - expected).max()
+
+    # (2) one capsule at a time, where the mover, tiles and small bodies are within reach
+    c = np.zeros(12, dtype=abi.capsule_query_dtype)
+    c["pos"] = rng.uniform([-2.0, -1.5, 0.9], [2.5, 1.5, 1.8], size=(12, 3))
+    quat = rng.normal(size=(12, 4)); quat /= np.linalg.norm(quat, axis=1, keepdims=True)
+    c["rot"] = quat; c["rot"][:6] = (0, 0, 0, 1)
+    c["radius"] = 0.4; c["half_height"] = 0.8; c["max_separation"] = 0.3; c["ignore_id"] = abi.INVALID_ID; c["ignore_id"][::5] = mover_id; c["collidable_only"] = 1
+    bodies = set()
+    for k in range(12):
+        ref = w.collide_capsules(c[k:k + 1], cap=1024)
+        bodies |= set(ref["body"].tolist())
+        for path, wp in worlds.items():
+            got, total = wp.collide_shapes(capsule_as_shape(c[k:k + 1]), cap=1024)
+            assert total == len(ref) < 1024, (k, path)
+            assert_records_equal_bitwise(got, ref)
+    assert bodies & set(tile_ids) and mover_id in bodies and bodies & set(small_ids), sorted(bodies)
+    for wp in worlds.values():
+        wp.close()
+
+
 def test_single_rays_through_the_resident_server_equal_the_batched_answers():
     """PhysicsWorld::traceRay is called one ray at a time by unchanged callers (ParticleManager.cpp:164, HoverCarPhysics.cpp:348): such rays go to a
     resident wave through a host-mapped mailbox (round 5) that traces each with all 64 lanes.  The answers must be those of the batched kernel, bit for
