@@ -767,6 +767,120 @@ int  sgp_particles_drain_events(sgp_particles* ps, sgp_particle_event* out, uint
  * events stay.  Enqueued, no wait. */
 int  sgp_particles_clear(sgp_particles* ps);
 
+/* ---- batched hover cars and boats (HoverCarPhysics, BoatPhysics of gui_client) ------------------------
+ * A batch of scripted craft that belongs to one world and lives on the device.  sgp_crafts_update runs HoverCarPhysics::update
+ * (HoverCarPhysics.cpp:76-407) or BoatPhysics::update (BoatPhysics.cpp:105-391) for every craft of the batch in one launch on the world's
+ * stream, a lane per craft: it reads the body's pose, velocities and submerged volume where they live, evaluates the reference's fp32
+ * expressions in the reference's order (docs/CONTRACT.md, "Crafts") and adds every force and torque to the body's accumulators in the order of
+ * the reference's AddForce / AddTorque calls, with the arithmetic of sgp_body_activate / sgp_body_add_force / _force_at / _torque.  A hover
+ * car with a driver casts its one ray with the function sgp_raycast runs per ray.  The dust, spray and foam an update makes go to an attached
+ * sgp_particles batch without leaving the device.  Nothing is read back, nothing waits.
+ * Departures from the reference (docs/GAPS.md): the random numbers are a counter-based generator of this library (glare-core's PCG32 is not
+ * reproduced); a batch holds no state that a world checkpoint captures; tiled worlds are refused; sgp_world_step_n advances n steps with ONE
+ * update's forces where the reference updates per sub-step: step one at a time.
+ * The caller creates a boat's body with use_zero_linear_drag = 1 (BoatPhysics.cpp:36 sets it on the object: the boat computes its own drag). */
+typedef struct sgp_crafts sgp_crafts;
+#define SGP_CRAFT_HOVERCAR 0u
+#define SGP_CRAFT_BOAT     1u
+#define SGP_CRAFT_MAX_SPLASH_POINTS 8
+#define SGP_CRAFT_MAX_EMIT 22      /* particles one craft can make in one update: 6 jet foam + 2 x 8 splash (a hover car makes at most 4) */
+#define SGP_CRAFTS_MAX_CAPACITY (1u << 16)
+#define SGP_CRAFT_IN_DRIVER 1u     /* user_in_driver_seat.  Setting it on a boat stops its righting (BoatPhysics.cpp:80) */
+#define SGP_CRAFT_IN_BOOST  2u     /* SHIFT_down: only the speed of a boat's jet foam (BoatPhysics.cpp:202) */
+#define SGP_CRAFT_ST_BODY_GONE 1u  /* the body the craft was added on has been removed (its slot may hold another body): the craft is skipped */
+/* sgp_craft_state::branches: which branches of the reference fired in the last update */
+#define SGP_CRAFT_BR_HOVER       (1u << 0)    /* HoverCarPhysics.cpp:152-160 */
+#define SGP_CRAFT_BR_UNFLIP      (1u << 1)    /* :168-175 (the world-space up force) */
+#define SGP_CRAFT_BR_DRAG        (1u << 2)    /* :240-267, BoatPhysics.cpp:240-267 */
+#define SGP_CRAFT_BR_LIFT_TOP    (1u << 3)    /* :280-287 */
+#define SGP_CRAFT_BR_LIFT_BOTTOM (1u << 4)    /* :292-299 */
+#define SGP_CRAFT_BR_LIFT_RIGHT  (1u << 5)    /* :309-313 */
+#define SGP_CRAFT_BR_LIFT_LEFT   (1u << 6)    /* :318-322 */
+#define SGP_CRAFT_BR_THRUST      (1u << 7)    /* BoatPhysics.cpp:183-216 */
+#define SGP_CRAFT_BR_RUDDER      (1u << 8)    /* :219-226 */
+#define SGP_CRAFT_BR_RIGHTING    (1u << 9)    /* :363-388 */
+#define SGP_CRAFT_BR_RAY_BODY    (1u << 10)   /* HoverCarPhysics.cpp:378-400 (dust) */
+#define SGP_CRAFT_BR_RAY_WATER   (1u << 11)   /* :353-375 (spray) */
+#define SGP_CRAFT_BR_ACTIVATE    (1u << 12)   /* the ActivateBody on user input (:116-117, BoatPhysics.cpp:176-177) */
+#define SGP_CRAFT_BR_SPLASH0     (1u << 16)   /* BoatPhysics.cpp:335-355 for splash point p: bit 16 + p */
+/* kinds of the particles a craft makes: bits 28..31 of the low word of their tag */
+#define SGP_CRAFT_PK_SPRAY  0u     /* hover car over water: Colour3f(0.6), ParticleType_Smoke */
+#define SGP_CRAFT_PK_DUST   1u     /* hover car over ground: Colour3f(0.6, 0.4, 0.3), ParticleType_Smoke */
+#define SGP_CRAFT_PK_JET    2u     /* boat jet foam: Colour3f(0.6), ParticleType_Foam */
+#define SGP_CRAFT_PK_SPLASH 3u     /* boat splash: Colour3f(0.6), ParticleType_Foam */
+typedef struct sgp_craft_desc {
+	uint32_t kind;                 /* SGP_CRAFT_HOVERCAR | SGP_CRAFT_BOAT                                               */
+	uint32_t body;                 /* a live dynamic body, no other craft of the batch on it                            */
+	float    mass;                 /* hovercar_mass / boat_mass; > 0                                                    */
+	float    model_to_y_forwards_rot_1[4];
+	float    model_to_y_forwards_rot_2[4];
+	uint32_t seed;                 /* of the craft's random numbers                                                     */
+	uint64_t tag;                  /* the caller's (its WorldObject*); not interpreted                                  */
+	float    trace_origin_os[3];   /* hover car: where the dust ray starts, object space with the object's scale applied
+	                                  (HoverCarPhysics.cpp:331-337: aabb_os.centroid() - up_ms * axisLength * 0.51, scaled) */
+	float    thrust_force;         /* the rest: boats (BoatScriptSettings); 40000                                       */
+	float    propellor_point_os[3];                /* (0, 0.2, -6.2) */
+	float    propellor_sideways_offset;            /* 1     */
+	float    rudder_deflection_force_factor;       /* 500   */
+	float    thrust_vector_lateral_amount;         /* 0     */
+	float    jet_particle_initial_width;           /* 1     */
+	float    front_cross_sectional_area;           /* 2     */
+	float    side_cross_sectional_area;            /* 4     */
+	float    top_cross_sectional_area;             /* 8     */
+	uint32_t n_splash_points;      /* <= SGP_CRAFT_MAX_SPLASH_POINTS                                                    */
+	float    splash_points[32];    /* SGP_CRAFT_MAX_SPLASH_POINTS x (point_os xyz, right_sign); right_sign is clamped to [-1, 1] (BoatPhysics.cpp:55) */
+	float    shape_volume;         /* filled by sgp_craft_add from sgp_body_get_volume (0 -> 1, BoatPhysics.cpp:43-45); what the caller puts here is ignored */
+} sgp_craft_desc;
+/* Resolved analog values; the key mapping of HoverCarPhysics.cpp:82-110 / BoatPhysics.cpp:110-131 is the facade's (shim/CraftBatch.h). */
+typedef struct sgp_craft_input {
+	float    forward;              /* boats: with the boost doubling and the 0.2 of reversing already applied           */
+	float    right;
+	float    up;                   /* hover cars                                                                        */
+	float    hand_brake;           /* hover cars: only wakes the body                                                   */
+	uint32_t flags;                /* SGP_CRAFT_IN_*                                                                    */
+} sgp_craft_input;
+typedef struct sgp_craft_state {
+	float    force[3];             /* what the last update added to the body's force accumulator                        */
+	float    torque[3];            /* ... and to its torque accumulator (forces at a point: about the body position)    */
+	uint32_t branches;             /* SGP_CRAFT_BR_*                                                                    */
+	float    unflip_time_remaining;      /* unflip_up_force_time_remaining (-1: not unflipping)                         */
+	float    righting_time_remaining;
+	float    trace_origin[3];      /* last_trace_origin_ws                                                              */
+	float    trace_t;              /* hit_t of the last ray; 0 without a hit                                            */
+	uint32_t trace_body;           /* SGP_INVALID_ID: no ray cast, or nothing hit                                       */
+	uint32_t n_emitted;            /* particles the last update made (counted with or without a batch attached)         */
+	uint32_t status;               /* SGP_CRAFT_ST_*                                                                    */
+	uint32_t update_index;         /* updates this craft has run                                                        */
+	uint32_t reserved_;
+} sgp_craft_state;
+/* Zeros, identity rotations, and for SGP_CRAFT_BOAT the defaults of Scripting.cpp:229-239; mass 1000. */
+void sgp_default_craft_desc(uint32_t kind, sgp_craft_desc* out);
+/* capacity in 1 .. SGP_CRAFTS_MAX_CAPACITY.  A world that holds ghost bodies (a tile) is refused, as by sgp_characters_create. */
+int  sgp_crafts_create(sgp_world* w, uint32_t capacity, sgp_crafts** out);
+/* After sgp_world_destroy of its world this still frees the batch and returns SGP_OK; every other call on such a batch is SGP_ERR_INVALID. */
+int  sgp_crafts_destroy(sgp_crafts* cs);
+/* Ids are slots of the batch; a removed slot is reused and carries nothing over (timers at -1, update index and particle counter at 0).
+ * SGP_ERR_INVALID, with nothing added, for a NULL, a non-finite value, mass <= 0, an unknown kind, a body that is not live and dynamic, a
+ * second craft on the same body and n_splash_points > SGP_CRAFT_MAX_SPLASH_POINTS; SGP_ERR_CAPACITY for a full batch. */
+int  sgp_craft_add(sgp_crafts* cs, const sgp_craft_desc* desc, uint32_t* id_out);
+int  sgp_craft_remove(sgp_crafts* cs, uint32_t id);
+/* Inputs of crafts [first, first + n); they stay in force until set again. */
+int  sgp_crafts_set_inputs(sgp_crafts* cs, uint32_t first, uint32_t n, const sgp_craft_input* inputs);
+/* startRightingVehicle: a boat's righting timer starts at 2 s with its next update (a hover car's does nothing, as in the reference). */
+int  sgp_crafts_start_righting(sgp_crafts* cs, const uint32_t* ids, uint32_t n);
+/* The batch that receives the particles (NULL: none; they are then only counted).  It must belong to the same world and hold at least
+ * crafts capacity x SGP_CRAFT_MAX_EMIT particles (else SGP_ERR_CAPACITY): one update's output then always fits one append.  New particles go
+ * behind the live ones in ascending craft order, then the reference's emission order, with the semantics of sgp_particles_add (overflow
+ * replaces round-robin and raises REPLACED events in newcomer order).  Particle tag = craft id << 32 | kind << 28 | per-craft counter.
+ * Detach (NULL) before the particle batch is destroyed. */
+int  sgp_crafts_attach_particles(sgp_crafts* cs, sgp_particles* particles_or_null);
+/* One update of every craft: flushes pending body edits, makes the query grid valid (as a batched sgp_raycast does), uploads what the host
+ * changed and enqueues the update on the world's stream.  No wait, no copy to the host, no allocation.  The world's next step is never skipped
+ * as idle afterwards.  A craft whose body has gone is skipped and touches nothing.  dt must be finite and >= 0. */
+int  sgp_crafts_update(sgp_crafts* cs, float dt);
+/* Waits for the updates in flight.  Slots that are not live read as zeros with trace_body = SGP_INVALID_ID. */
+int  sgp_crafts_get_states(sgp_crafts* cs, uint32_t first, uint32_t n, sgp_craft_state* out);
+
 /* ---- overlap queries with any convex shape (JPH::NarrowPhaseQuery::CollideShape) --------------------
  * "What is inside this volume?": a box for a parcel or a trigger volume, a sphere for an explosion or an audio radius, the hull of an
  * object for a placement test before it is added -- thousands of them per call if need be.  Every query reports the contacts of its shape

@@ -282,6 +282,35 @@ class ParticleEvent(C.Structure):
     _fields_ = [("tag", u64), ("kind", u32), ("pos", f32 * 3), ("width", f32), ("foam_width", f32)]
 
 
+CRAFT_HOVERCAR, CRAFT_BOAT = 0, 1                                         # SGP_CRAFT_*
+CRAFT_MAX_SPLASH_POINTS, CRAFT_MAX_EMIT, CRAFTS_MAX_CAPACITY = 8, 22, 1 << 16
+CRAFT_IN_DRIVER, CRAFT_IN_BOOST = 1, 2                                    # SGP_CRAFT_IN_*
+CRAFT_ST_BODY_GONE = 1                                                    # SGP_CRAFT_ST_*
+CRAFT_BR = {"HOVER": 1 << 0, "UNFLIP": 1 << 1, "DRAG": 1 << 2, "LIFT_TOP": 1 << 3, "LIFT_BOTTOM": 1 << 4, "LIFT_RIGHT": 1 << 5, "LIFT_LEFT": 1 << 6,
+            "THRUST": 1 << 7, "RUDDER": 1 << 8, "RIGHTING": 1 << 9, "RAY_BODY": 1 << 10, "RAY_WATER": 1 << 11, "ACTIVATE": 1 << 12, "SPLASH0": 1 << 16}      # SGP_CRAFT_BR_*
+CRAFT_PK_SPRAY, CRAFT_PK_DUST, CRAFT_PK_JET, CRAFT_PK_SPLASH = 0, 1, 2, 3   # SGP_CRAFT_PK_*
+
+
+class CraftDesc(C.Structure):
+    """sgp_craft_desc: one hover car (HoverCarPhysicsSettings) or boat (BoatPhysicsSettings / BoatScriptSettings) of a batch."""
+    _fields_ = [("kind", u32), ("body", u32), ("mass", f32), ("model_to_y_forwards_rot_1", f32 * 4), ("model_to_y_forwards_rot_2", f32 * 4),
+                ("seed", u32), ("tag", u64), ("trace_origin_os", f32 * 3), ("thrust_force", f32), ("propellor_point_os", f32 * 3),
+                ("propellor_sideways_offset", f32), ("rudder_deflection_force_factor", f32), ("thrust_vector_lateral_amount", f32),
+                ("jet_particle_initial_width", f32), ("front_cross_sectional_area", f32), ("side_cross_sectional_area", f32),
+                ("top_cross_sectional_area", f32), ("n_splash_points", u32), ("splash_points", f32 * 32), ("shape_volume", f32)]
+
+
+class CraftInput(C.Structure):
+    _fields_ = [("forward", f32), ("right", f32), ("up", f32), ("hand_brake", f32), ("flags", u32)]
+
+
+class CraftState(C.Structure):
+    """sgp_craft_state: what the last update of a craft did."""
+    _fields_ = [("force", f32 * 3), ("torque", f32 * 3), ("branches", u32), ("unflip_time_remaining", f32), ("righting_time_remaining", f32),
+                ("trace_origin", f32 * 3), ("trace_t", f32), ("trace_body", u32), ("n_emitted", u32), ("status", u32), ("update_index", u32),
+                ("reserved_", u32)]
+
+
 class CompoundChild(C.Structure):
     _fields_ = [("shape_type", i32), ("shape", f32 * 4), ("pos", f32 * 3), ("rot", f32 * 4)]
 
@@ -312,7 +341,8 @@ ABI_SIZEOF_ORDER = ["sgp_settings", "sgp_world_desc", "sgp_body_desc", "sgp_body
 # (likewise 24, which the bindings that know 24 structs probe)
 ABI_SIZEOF_APPENDED = ["sgp_shape_query", None, "sgp_shape_cast", "sgp_cast_hit",
                        None, "sgp_character_desc", "sgp_character_input", "sgp_character_state", "sgp_character_contact",
-                       None, "sgp_particle", "sgp_particle_state", "sgp_particle_event"]      # (29 likewise)
+                       None, "sgp_particle", "sgp_particle_state", "sgp_particle_event",      # (29 likewise)
+                       None, "sgp_craft_desc", "sgp_craft_input", "sgp_craft_state"]           # (33 likewise)
 ABI_SIZEOF_ALL = ABI_SIZEOF_ORDER + ABI_SIZEOF_APPENDED
 
 STRUCTS = {"sgp_settings": Settings, "sgp_world_desc": WorldDesc, "sgp_body_desc": BodyDesc,
@@ -324,7 +354,8 @@ STRUCTS = {"sgp_settings": Settings, "sgp_world_desc": WorldDesc, "sgp_body_desc
            "sgp_checkpoint_info": CheckpointInfo, "sgp_shape_query": ShapeQuery, "sgp_shape_cast": ShapeCast,
            "sgp_cast_hit": CastHit, "sgp_character_desc": CharacterDesc, "sgp_character_input": CharacterInput,
            "sgp_character_state": CharacterState, "sgp_character_contact": CharacterContact,
-           "sgp_particle": Particle, "sgp_particle_state": ParticleState, "sgp_particle_event": ParticleEvent}
+           "sgp_particle": Particle, "sgp_particle_state": ParticleState, "sgp_particle_event": ParticleEvent,
+           "sgp_craft_desc": CraftDesc, "sgp_craft_input": CraftInput, "sgp_craft_state": CraftState}
 
 body_desc_dtype = np.dtype(BodyDesc)
 body_state_dtype = np.dtype(BodyState)
@@ -349,6 +380,9 @@ character_contact_dtype = np.dtype(CharacterContact)
 particle_dtype = np.dtype(Particle)
 particle_state_dtype = np.dtype(ParticleState)
 particle_event_dtype = np.dtype(ParticleEvent)
+craft_desc_dtype = np.dtype(CraftDesc)
+craft_input_dtype = np.dtype(CraftInput)
+craft_state_dtype = np.dtype(CraftState)
 compound_child_dtype = np.dtype(CompoundChild)
 migration_dtype = np.dtype(Migration)
 
@@ -438,6 +472,17 @@ PROTOTYPES = {
     "particles_read": (C.c_int, [vp, vp, u32, P(u32)]),
     "particles_drain_events": (C.c_int, [vp, vp, u32, P(u32), P(u32)]),
     "particles_clear": (C.c_int, [vp]),
+    # batched hover cars and boats (handle: void*)
+    "default_craft_desc": (None, [u32, P(CraftDesc)]),
+    "crafts_create": (C.c_int, [vp, u32, P(vp)]),
+    "crafts_destroy": (C.c_int, [vp]),
+    "craft_add": (C.c_int, [vp, P(CraftDesc), P(u32)]),
+    "craft_remove": (C.c_int, [vp, u32]),
+    "crafts_set_inputs": (C.c_int, [vp, u32, u32, vp]),
+    "crafts_start_righting": (C.c_int, [vp, vp, u32]),
+    "crafts_attach_particles": (C.c_int, [vp, vp]),
+    "crafts_update": (C.c_int, [vp, f32]),
+    "crafts_get_states": (C.c_int, [vp, u32, u32, vp]),
     "world_export_boundary": (C.c_int, [vp, P(f32), P(f32), f32, vp, u32, P(u32)]),
     "world_import_ghosts": (C.c_int, [vp, vp, u32]),
     "tiles_route": (C.c_int, [vp, u32, u32, vp, u32, f32, vp, u32, vp, vp, u32, P(u32)]),

@@ -136,6 +136,43 @@ __global__ void k_particles_append_commit(PsBufs b, uint32_t n)
 	b.st->n_events = ne + min(m, 0xFFFFFFFFu - ne);
 }
 
+// The same append for records the device made (sgp_crafts_update): their count comes from device memory, the grid covers the host's upper bound of it.  Lane for
+// lane what k_particles_append / k_particles_append_commit do with that count.
+__global__ void __launch_bounds__(256) k_particles_append_device(PsBufs b, uint32_t cur, const sgp_particle* recs, const uint32_t* n_dev)
+{
+	const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+	const uint32_t cap = b.cap, n = min(*n_dev, cap);
+	if (k >= n) return;
+	const uint32_t n_old = min(b.st->n_live, cap), cursor = b.st->cursor % cap;
+	const uint32_t fit = min(n, cap - n_old), m = n - fit;
+	if (k < fit) {
+		const uint32_t slot = n_old + k;
+		const uint32_t rel = slot >= cursor ? slot - cursor : slot + (cap - cursor);
+		if (rel < m) return;
+		particle_store(b, cur, slot, recs[k]);
+		return;
+	}
+	const uint32_t j = k - fit, slot = (cursor + j) % cap;
+	sgp_particle_event e;
+	if (slot >= n_old) {
+		const sgp_particle& o = recs[slot - n_old];
+		e.tag = o.tag; e.pos[0] = o.pos[0]; e.pos[1] = o.pos[1]; e.pos[2] = o.pos[2]; e.width = o.width;
+		e.kind = SGP_PARTICLE_EV_REPLACED; e.foam_width = 0.0f;
+	}
+	else e = particle_event(b.cold[cur][2 * (size_t)slot + 1], SGP_PARTICLE_EV_REPLACED, b.hot[cur][2 * (size_t)slot], 0.0f);
+	const uint64_t at = (uint64_t)b.st->n_events + j;
+	if (at < b.ev_cap) b.events[at] = e;
+	particle_store(b, cur, slot, recs[k]);
+}
+__global__ void k_particles_append_device_commit(PsBufs b, const uint32_t* n_dev)
+{
+	const uint32_t cap = b.cap, n = min(*n_dev, cap), n_old = min(b.st->n_live, cap), cursor = b.st->cursor % cap;
+	const uint32_t fit = min(n, cap - n_old), m = n - fit, ne = b.st->n_events;
+	b.st->n_live = n_old + fit;
+	b.st->cursor = (cursor + m) % cap;
+	b.st->n_events = ne + min(m, 0xFFFFFFFFu - ne);
+}
+
 __global__ void __launch_bounds__(256) k_particles_pack(PsBufs b, uint32_t cur, uint32_t upper, sgp_particle_state* out)
 {
 	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -162,6 +199,12 @@ void launch_particles_append(const PsBufs& b, uint32_t cur, const sgp_particle* 
 	if (!n) return;
 	hipLaunchKernelGGL(k_particles_append, dim3((n + 255u) / 256u), dim3(256), 0, s, b, cur, recs, n);
 	hipLaunchKernelGGL(k_particles_append_commit, dim3(1), dim3(1), 0, s, b, n);
+}
+void launch_particles_append_device(const PsBufs& b, uint32_t cur, const sgp_particle* recs, const uint32_t* n_dev, uint32_t bound, hipStream_t s)
+{
+	if (!bound) return;
+	hipLaunchKernelGGL(k_particles_append_device, dim3((bound + 255u) / 256u), dim3(256), 0, s, b, cur, recs, n_dev);
+	hipLaunchKernelGGL(k_particles_append_device_commit, dim3(1), dim3(1), 0, s, b, n_dev);
 }
 void launch_particles_pack(const PsBufs& b, uint32_t cur, uint32_t upper, sgp_particle_state* out, hipStream_t s)
 {

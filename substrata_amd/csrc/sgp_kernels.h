@@ -16,6 +16,7 @@
 //   sgp_k_shapecast.hip    A7     k_sc_candidates + k_sc_pairs_prim / k_sc_pairs_hull / k_sc_mesh (sgp_cast_shapes)
 //   sgp_k_characters.hip   A7     k_characters_update (a wave per character: the whole Update / ExtendedUpdate), k_characters_push, k_characters_sync (sgp_characters_*)
 //   sgp_k_particles.hip    A7     k_particles_update (a lane per particle: raycast_one + ParticleManager::think), k_particles_scan, k_particles_scatter (stable compaction + events), k_particles_append (sgp_particles_*)
+//   sgp_k_crafts.hip       A7     k_crafts_update (a lane per craft: HoverCarPhysics::update / BoatPhysics::update, forces into the accumulators), k_crafts_scan, k_crafts_compact (particle hand-over) (sgp_crafts_*)
 //   sgp_k_edits.hip        A5/A6  k_apply_cmds, k_ghost_refresh, read-back
 //   sgp_k_tiles.hip        (e)    tile export / routing, re-tiling histograms
 //   sgp_k_checkpoint.hip          k_ckpt_copy: the segmented copy of sgp_world_checkpoint / sgp_world_rollback
@@ -543,6 +544,32 @@ struct PsBufs {
 void launch_particles_update(const DV& d, const PsBufs& b, uint32_t cur, uint32_t upper, float dt, int water_enabled, float water_z, hipStream_t s);
 void launch_particles_append(const PsBufs& b, uint32_t cur, const sgp_particle* recs, uint32_t n, hipStream_t s);
 void launch_particles_pack(const PsBufs& b, uint32_t cur, uint32_t upper, sgp_particle_state* out, hipStream_t s);      // out[i], i < min(live count, upper)
+// the same append with the records and their count in device memory (sgp_crafts_update hands its particles over without the host); bound >= the count, <= b.cap
+void launch_particles_append_device(const PsBufs& b, uint32_t cur, const sgp_particle* recs, const uint32_t* n_dev, uint32_t bound, hipStream_t s);
+// ---- batched hover cars and boats (sgp_k_crafts.hip, sgp_dev_crafts.h) -----------------------------------------------------------------------------------
+// The host owns the descriptions and inputs (CraftRec, CraftIn: uploaded when they change); the device owns the timers, the update index and the particle
+// counter (CraftDyn) and reaches the host's wishes through serial numbers, as the characters do.
+struct CraftRec {
+	uint32_t alive, gone, reset_serial, cmd_serial;      // gone: the body is no longer the one the craft was added on (the host knows: it hands out the slots)
+	float cmd_value;                                      // what the righting timer becomes when cmd_serial moves (2: startRightingVehicle, -1: a driver sat down)
+	uint32_t kind, body, seed;
+	float mass, q1[4], q2[4], trace_os[3], thrust, prop_os[3], prop_off, rudder, lateral, jet_w, a_front, a_side, a_top, volume;
+	uint32_t n_splash; float splash[4 * SGP_CRAFT_MAX_SPLASH_POINTS];
+};
+struct CraftIn { float forward, right, up, hand_brake; uint32_t flags; };
+struct CraftDyn { float unflip, righting; uint32_t update_index, counter, reset_serial, cmd_serial, pad_[2]; };
+struct CraftBufs {
+	const CraftRec* rec; const CraftIn* in; CraftDyn* dyn; sgp_craft_state* st;
+	sgp_particle* emit;        // [craft][SGP_CRAFT_MAX_EMIT]: what the running update made
+	uint32_t* n_emit;          // [craft]
+	uint32_t* emit_off;        // [craft]: exclusive scan of n_emit; [n]: the total (k_crafts_scan)
+	sgp_particle* dense;       // the records in hand-over order (k_crafts_compact)
+	uint32_t n;                // slots in use (high-water mark)
+};
+#define CRAFT_SCAN_THREADS 1024
+void launch_crafts_update(const DV& d, const CraftBufs& b, float dt, int water_enabled, float water_z, hipStream_t s);
+void launch_crafts_gather(const CraftBufs& b, hipStream_t s);      // scan + compact: b.dense[0 .. b.emit_off[b.n]) in ascending craft, then emission order
+void launch_crafts_sync(const CraftBufs& b, hipStream_t s);        // get_states with host edits pending and no update to carry them
 void launch_export_boundary(const DV& d, uint32_t nb, float3 lo, float3 hi, float margin, sgp_ghost_record* out, uint32_t cap, uint32_t* count, hipStream_t s);
 
 // ---- tile exchange with the routing on the device (sgp_tiles_*) ----------------------------------------------------

@@ -14,9 +14,6 @@ struct sgp_characters : WorldBatch {
 	size_t up_rec = 0, up_in = 0;      // the pinned staging of the uploads (WorldBatch::h_up): [DV][records at up_rec][inputs at up_in]
 };
 
-// a tile's world: ghosts imported, or queued for import
-static bool world_holds_ghosts(const sgp_world* w) { return !w->ghost_map.empty() || !w->ghost_seq.empty() || !w->ghost_refresh.empty() || !w->rec_creates.empty(); }
-
 static CharBufs chars_bufs(const sgp_characters* cs)
 {
 	CharBufs b;

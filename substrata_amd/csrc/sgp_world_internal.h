@@ -6,6 +6,7 @@
 //   sgp_world_queries.hip    rays, capsule queries, sphere casts, shape queries (sgp_collide_shapes), shape casts (sgp_cast_shapes); the query prologue
 //   sgp_world_characters.hip the batched character controller (sgp_characters_*)
 //   sgp_world_particles.hip  the batched point particles (sgp_particles_*)
+//   sgp_world_crafts.hip     the batched hover cars and boats (sgp_crafts_*)
 //                            (what the two batches share -- owner, zeroed device arrays, the upload fence: WorldBatch, below)
 //   sgp_stage_carve.h        the regions of one call in the stage buffer (host only, no HIP types)
 //   sgp_world_tiles.hip      ghost import / export, the tile exchange over RCCL, re-tiling
@@ -92,6 +93,7 @@ struct sgp_world {
 	std::vector<HostBody> hb;
 	std::vector<uint32_t> free_list;
 	uint32_t high = 0, n_alive = 0;
+	std::vector<uint32_t> body_born; uint32_t births = 0;      // [slot]: the birth number of the body that lives there (set_body_flags); not part of a checkpoint
 	std::vector<uint32_t> large_ids; bool large_dirty = false;      // every large body (host order; may hold ids that have gone: rebuild_large_grid compacts it)
 	// round 4: the grid of the static large bodies is rebuilt in full only now and then -- a newcomer waits on the linear list every body walks (lg_pending
 	// of them at most), a removed one stays behind as a dead entry (lg_tombs; a query skips what is not alive): streaming one parcel object in or out is
@@ -271,6 +273,8 @@ struct WorldBatch {
 	}
 };
 static inline bool batch_usable(const WorldBatch* b) { return b && b->usable(); }
+// a tile's world: ghosts imported, or queued for import (the characters and the crafts refuse it)
+static inline bool world_holds_ghosts(const sgp_world* w) { return !w->ghost_map.empty() || !w->ghost_seq.empty() || !w->ghost_refresh.empty() || !w->rec_creates.empty(); }
 
 
 // ---- helpers used by several files -----------------------------------------------------------------------------------------------------------
@@ -285,6 +289,11 @@ static inline void set_body_flags(sgp_world* w, HostBody& b, uint32_t f)
 {
 	if (counts_in_layer(b.flags)) w->layer_counts[(b.flags & BF_LAYER_MASK) >> BF_LAYER_SHIFT]--;
 	if (counts_in_layer(f)) w->layer_counts[(f & BF_LAYER_MASK) >> BF_LAYER_SHIFT]++;
+	if (!(b.flags & BF_ALIVE) && (f & BF_ALIVE)) {      // a slot is given to a new body: it gets a birth number no body of this world had before (sgp_crafts: "is this still my body?")
+		const size_t id = (size_t)(&b - w->hb.data());
+		if (w->body_born.size() < w->hb.size()) w->body_born.resize(w->hb.size(), 0u);
+		if (id < w->body_born.size()) w->body_born[id] = ++w->births;
+	}
 	b.flags = f;
 }
 // ... and after the mirror was replaced wholesale (a rollback)
@@ -320,6 +329,11 @@ int shapes_upload_all(sgp_world* w);                           // the host mirro
 // defined in sgp_world_queries.hip
 int query_prelude(sgp_world* w);          // flush_cmds (edits applied, the resident ray server told to leave) + ensure_query_grid: what precedes the launch of every query, characters' and particles' update
 int ensure_query_grid(sgp_world* w);      // re-bins the bodies when poses changed since the broad-phase grid was built (every query's first step after flush_cmds)
+// defined in sgp_world_particles.hip (struct sgp_particles is private to it): what sgp_world_crafts.hip needs of a particle batch
+struct sgp_particles;
+uint32_t particles_capacity(const sgp_particles* ps);
+bool particles_of_world(const sgp_particles* ps, const sgp_world* w);      // usable, and of this world
+int particles_append_device(sgp_particles* ps, const sgp_particle* d_recs, const uint32_t* d_count, uint32_t bound);
 // defined in sgp_world_bodies.hip
 int add_one(sgp_world* w, const sgp_body_desc* d, uint32_t* id_out, bool ghost);
 int book_record_body(sgp_world* w, uint32_t* flags_io, uint64_t userdata, float radius, float volume, bool ghost, uint32_t* id_out);      // (the host's share of add_one for a body created on the device from a record)

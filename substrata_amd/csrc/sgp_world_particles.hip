@@ -100,6 +100,21 @@ SGP_API int sgp_particles_add(sgp_particles* ps, const sgp_particle* recs, uint3
 	return SGP_OK;
 }
 
+// Internal (sgp_world_crafts.hip): newcomers the device made -- `d_recs` and their count `d_count` are device memory of the same stream, bound >= the count.
+// Enqueues the append and raises the host's upper bound of the live count by `bound`; no wait, no copy, no allocation.
+uint32_t particles_capacity(const sgp_particles* ps) { return ps->cap; }
+bool particles_of_world(const sgp_particles* ps, const sgp_world* w) { return batch_usable(ps) && ps->w == w; }
+int particles_append_device(sgp_particles* ps, const sgp_particle* d_recs, const uint32_t* d_count, uint32_t bound)
+{
+	if (!batch_usable(ps) || bound > ps->cap) return fail(SGP_ERR_INVALID, "particles_append_device: the batch's world is gone, or more records than its capacity");
+	if (!bound) return SGP_OK;
+	launch_particles_append_device(ps->b, ps->cur, d_recs, d_count, bound, ps->w->stream);
+	ps->upper = (uint32_t)std::min<uint64_t>(ps->cap, (uint64_t)ps->upper + bound);
+	ps->st_known = false;
+	HIP_TRY(hipGetLastError());
+	return SGP_OK;
+}
+
 SGP_API int sgp_particles_update(sgp_particles* ps, float dt)
 {
 	if (!batch_usable(ps)) return fail(SGP_ERR_INVALID, "sgp_particles_update: NULL, or the batch's world is gone");

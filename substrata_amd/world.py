@@ -117,6 +117,64 @@ class Characters:
             pass
 
 
+class Crafts:
+    """A batch of hover cars and boats of one world (sgp_crafts): update() enqueues and returns; states() waits."""
+
+    def __init__(self, world, capacity):
+        self._w, self._h = world, C.c_void_p()
+        world._check(world._fn("crafts_create")(world._h, int(capacity), C.byref(self._h)), "crafts_create")
+        self.capacity = int(capacity)
+
+    def default_desc(self, kind, body=None):
+        d = abi.CraftDesc()
+        self._w._fn("default_craft_desc")(int(kind), C.byref(d))
+        if body is not None:
+            d.body = int(body)
+        return d
+
+    def add(self, desc):
+        i = C.c_uint32(0)
+        self._w._check(self._w._fn("craft_add")(self._h, C.byref(desc), C.byref(i)), "craft_add")
+        return int(i.value)
+
+    def remove(self, i):
+        self._w._check(self._w._fn("craft_remove")(self._h, int(i)), "craft_remove")
+
+    def set_inputs(self, first, inputs):
+        """inputs: array of abi.craft_input_dtype (forward, right, up, hand_brake, flags) for crafts first, first + 1, ..."""
+        inputs = np.ascontiguousarray(inputs, dtype=abi.craft_input_dtype).reshape(-1)
+        self._w._check(self._w._fn("crafts_set_inputs")(self._h, int(first), len(inputs), inputs.ctypes.data), "crafts_set_inputs")
+
+    def start_righting(self, ids):
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        self._w._check(self._w._fn("crafts_start_righting")(self._h, ids.ctypes.data, len(ids)), "crafts_start_righting")
+
+    def attach(self, particles=None):
+        """The Particles batch of the same world that receives what the crafts raise (None: detach; emissions are then only counted)."""
+        self._w._check(self._w._fn("crafts_attach_particles")(self._h, particles._h if particles is not None else None), "crafts_attach_particles")
+        self._particles = particles      # (kept alive while attached)
+
+    def update(self, dt=1.0 / 60.0):
+        self._w._check(self._w._fn("crafts_update")(self._h, float(dt)), "crafts_update")
+
+    def states(self, first=0, n=None):
+        n = self.capacity - first if n is None else int(n)
+        out = np.zeros(n, dtype=abi.craft_state_dtype)
+        self._w._check(self._w._fn("crafts_get_states")(self._h, int(first), n, out.ctypes.data), "crafts_get_states")
+        return out
+
+    def close(self):
+        if self._h:
+            self._w._fn("crafts_destroy")(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Particles:
     """A batch of point particles of one world (sgp_particles): numpy in, numpy out.  add(), update() and clear() enqueue and return; read() and
     drain_events() wait."""
@@ -539,6 +597,10 @@ class CWorld:
     def particles(self, capacity, event_capacity=4096):
         """A batch of up to `capacity` point particles that belongs to this world."""
         return Particles(self, capacity, event_capacity)
+
+    def crafts(self, capacity):
+        """A batch of up to `capacity` hover cars and boats that belongs to this world (close it before the world)."""
+        return Crafts(self, capacity)
 
     def characters(self, capacity):
         """A batch of up to `capacity` virtual characters that belongs to this world (close it before the world)."""
