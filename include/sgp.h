@@ -881,6 +881,123 @@ int  sgp_crafts_update(sgp_crafts* cs, float dt);
 /* Waits for the updates in flight.  Slots that are not live read as zeros with trace_body = SGP_INVALID_ID. */
 int  sgp_crafts_get_states(sgp_crafts* cs, uint32_t first, uint32_t n, sgp_craft_state* out);
 
+/* ---- batched path and move-to controllers (ObjectPathController, ObjectMoveToController of gui_client) ----
+ * A batch of scripted movers that belongs to one world and lives on the device: trains, trams and lifts on a closed waypoint loop with
+ * carriages that follow a leader at a distance (SGP_MOVER_PATH), and doors and platforms with an eased position track and an eased rotation
+ * track (SGP_MOVER_MOVETO).  Each is bound to one kinematic body.  sgp_movers_update runs ObjectPathController::update
+ * (ObjectPathController.cpp:441-526) or ObjectMoveToController::update (ObjectMoveToController.cpp:58-114) for every mover, a lane per mover,
+ * on the world's stream and gives the body the velocities of sgp_body_move_kinematic -- for a mesh body also its two alias slots --; nothing is
+ * read back, nothing waits.  Call it before each sgp_world_step, where the reference runs its controllers (GUIClient.cpp:6394-6418).
+ * The fp32 expressions and their order: docs/CONTRACT.md 4j.  Departures from the reference (docs/GAPS.md): an update passes at most
+ * SGP_MOVER_MAX_SEGMENTS_PER_UPDATE segment ends forwards or segment starts backwards; a follower's leader is a walker on the same path (no
+ * chains); a path has at most SGP_MOVER_MAX_WAYPOINTS waypoints; rotations are held as quaternions; no checkpoint state; tiled worlds are
+ * refused; sgp_world_step_n advances n steps on one update. */
+typedef struct sgp_movers sgp_movers;
+#define SGP_MOVER_PATH   0u
+#define SGP_MOVER_MOVETO 1u
+#define SGP_WAYPOINT_CURVE_IN  0u     /* PathWaypointIn::CurveIn: start of a circular arc                                      */
+#define SGP_WAYPOINT_CURVE_OUT 1u     /* CurveOut: end of a curve                                                              */
+#define SGP_WAYPOINT_STATION   2u     /* Station: the object pauses here for pause_time seconds                                */
+#define SGP_MOVER_EASE_LINEAR     0u  /* Protocol::MoveTo_EasingLinear                                                         */
+#define SGP_MOVER_EASE_SMOOTHSTEP 1u  /* Protocol::MoveTo_EasingSmoothstep                                                     */
+#define SGP_MOVER_ORIENT_ALONG_PATH 1u
+#define SGP_MOVER_MAX_WAYPOINTS 128
+#define SGP_MOVER_MAX_SEGMENTS_PER_UPDATE 64
+#define SGP_MOVERS_MAX_CAPACITY (1u << 16)
+#define SGP_MOVERS_MAX_PATHS    (1u << 12)
+#define SGP_MOVER_ST_BODY_GONE   1u   /* the body is no longer the live kinematic body the mover was added on: the mover is skipped */
+#define SGP_MOVER_ST_LEADER_GONE 2u   /* a follower whose leader was removed or lost its body: waypoint 0, direction (1,0,0)   */
+#define SGP_MOVER_ST_OVERRUN     4u   /* the last update stopped at the cap of SGP_MOVER_MAX_SEGMENTS_PER_UPDATE               */
+#define SGP_MOVER_ST_POS_ACTIVE  8u   /* pos_active after the last update                                                      */
+#define SGP_MOVER_ST_ROT_ACTIVE  16u  /* rot_active after the last update                                                      */
+typedef struct sgp_path_waypoint {
+	float    pos[3];
+	uint32_t type;                 /* SGP_WAYPOINT_*                                                                    */
+	float    pause_time;           /* Station: seconds; finite, >= 0                                                    */
+	float    speed;                /* to the next waypoint; finite, > 0                                                 */
+} sgp_path_waypoint;
+/* ObjectPathController::PathWaypoint.  The fields behind speed are derived by sgp_path_prepare; those of a curve are 0 on other waypoints. */
+typedef struct sgp_path_segment {
+	float    pos[3];
+	uint32_t type;
+	float    pause_time;
+	float    speed;
+	float    segment_len;          /* length along the segment to the next waypoint                                     */
+	float    just_curve_len;       /* length along just the arc                                                         */
+	float    entry_segment_len;    /* length of the straight part before the arc                                        */
+	float    curve_angle;
+	float    curve_r;
+	float    exit_segment_unit_dir[3];
+} sgp_path_segment;
+typedef struct sgp_path_progress {
+	uint32_t waypoint_index;       /* cur_waypoint_index: the waypoint we are at or have just passed                    */
+	float    dist_along_segment;   /* m_dist_along_segment                                                              */
+	float    time_along_segment;   /* m_time_along_segment (a station's pause counts)                                   */
+} sgp_path_progress;
+typedef struct sgp_mover_desc {
+	uint32_t kind;                 /* SGP_MOVER_PATH | SGP_MOVER_MOVETO                                                 */
+	uint32_t body;                 /* a live kinematic body: no compound, ghost or alias slot, no other mover of the batch on it */
+	uint32_t flags;                /* SGP_MOVER_ORIENT_ALONG_PATH                                                       */
+	uint32_t path;                 /* path movers: a path of sgp_movers_path_add                                        */
+	double   initial_time;         /* path walkers: the global time; taken modulo the path's traversal time             */
+	uint64_t tag;                  /* the caller's (its WorldObject*); not interpreted                                  */
+	uint32_t leader;               /* path movers: the mover to follow -- a walker of this batch on the same path --, or SGP_INVALID_ID */
+	float    follow_dist;          /* followers: distance behind the leader; finite, >= 0                               */
+	float    base_rot[4];          /* path movers: the object's own rotation (fromAxisAndAngle(normalise(axis), angle)) */
+	float    hold_pos[3];          /* move-to movers: what an inactive position track holds before any track has run    */
+	float    hold_rot[4];          /* ... and an inactive rotation track                                                */
+	uint32_t reserved_;
+} sgp_mover_desc;
+typedef struct sgp_mover_state {
+	uint32_t status;               /* SGP_MOVER_ST_*                                                                    */
+	uint32_t waypoint_index;       /* walkers: the state after the last update; followers: the segment they were placed on */
+	float    dist_along_segment;
+	float    time_along_segment;   /* walkers                                                                           */
+	float    pos[3];               /* the target the last update moved the body towards                                 */
+	float    rot[4];
+	float    dir[3];               /* path movers: the direction along the path                                         */
+	float    pos_elapsed;          /* move-to movers                                                                    */
+	float    rot_elapsed;
+	uint32_t update_index;         /* updates this mover has run (skipped ones do not count)                            */
+} sgp_mover_state;
+/* The constructor's segment loop (ObjectPathController.cpp:60-124) on the host, no world needed: out[0..n) and the traversal time of the loop.
+ * SGP_ERR_INVALID for a NULL, n < 2 or > SGP_MOVER_MAX_WAYPOINTS, a segment shorter than 1e-5 or not finite (where the reference throws), and
+ * for a speed not finite or not > 0, a pause_time negative or not finite, an unknown type (where the reference runs into undefined behaviour). */
+int  sgp_path_prepare(const sgp_path_waypoint* in, uint32_t n, sgp_path_segment* out, double* total_time_out);
+/* The state change of walkAlongPathForTime (:233-393) for dt, the arithmetic the device runs: bit-equal to it.  At most
+ * SGP_MOVER_MAX_SEGMENTS_PER_UPDATE segment ends are passed: at the cap it stops at the start of the segment reached (dist = time = 0) and
+ * ORs SGP_MOVER_ST_OVERRUN into *status_io.  dt <= 0 changes nothing.  SGP_ERR_INVALID for a NULL, n < 2, an index >= n, a dt that is not finite. */
+int  sgp_path_advance(const sgp_path_segment* segs, uint32_t n, sgp_path_progress* io, float dt, uint32_t* status_io);
+/* capacity in 1 .. SGP_MOVERS_MAX_CAPACITY movers, path_capacity in 1 .. SGP_MOVERS_MAX_PATHS paths of SGP_MOVER_MAX_WAYPOINTS segments each.
+ * A world that holds ghost bodies (a tile) is refused, as by sgp_crafts_create. */
+int  sgp_movers_create(sgp_world* w, uint32_t capacity, uint32_t path_capacity, sgp_movers** out);
+/* After sgp_world_destroy of its world this still frees the batch and returns SGP_OK; every other call on such a batch is SGP_ERR_INVALID. */
+int  sgp_movers_destroy(sgp_movers* ms);
+/* Paths are shared by movers and counted by reference: sgp_movers_path_remove of a path in use answers SGP_ERR_INVALID and removes nothing. */
+int  sgp_movers_path_add(sgp_movers* ms, const sgp_path_waypoint* waypoints, uint32_t n, uint32_t* path_id_out);
+int  sgp_movers_path_remove(sgp_movers* ms, uint32_t path_id);
+/* Copies the prepared segments of a path (for drawing, evalSegmentCurvePos): up to cap of them; *n_out their number. */
+int  sgp_movers_path_get(sgp_movers* ms, uint32_t path_id, sgp_path_segment* out, uint32_t cap, uint32_t* n_out);
+/* A walker (leader == SGP_INVALID_ID) starts where walkAlongPathForTime((float) doubleMod(initial_time, traversal time)) leaves it from
+ * (0, 0, 0), as the constructor does; the body is not moved by the add.  SGP_ERR_INVALID, with nothing added, for a NULL, an unknown kind or
+ * flag, a non-finite value, a body that does not qualify or carries a mover already, a path that is not live, a leader that is not a live
+ * walker of this batch on the same path, follow_dist < 0; SGP_ERR_CAPACITY for a full batch. */
+int  sgp_mover_add(sgp_movers* ms, const sgp_mover_desc* desc, uint32_t* id_out);
+/* The followers of a removed walker take the reference's fallback for a missing leader (SGP_MOVER_ST_LEADER_GONE). */
+int  sgp_mover_remove(sgp_movers* ms, uint32_t id);
+/* ObjectMoveToController::setPositionTrack / setRotationTrack for a move-to mover: duration is clamped to >= 1e-4 and cur_elapsed to >= 0, the
+ * track is active from the next update on and replaces the one that runs.  easing: SGP_MOVER_EASE_*. */
+int  sgp_movers_set_position_track(sgp_movers* ms, uint32_t id, const float start[3], const float target[3], float duration, uint32_t easing, float cur_elapsed);
+int  sgp_movers_set_rotation_track(sgp_movers* ms, uint32_t id, const float start[4], const float target[4], float duration, uint32_t easing, float cur_elapsed);
+/* One update of every mover: flushes pending body edits, uploads what the host changed and enqueues the update on the world's stream -- a
+ * second launch for the followers, which see where their leaders went in this update.  No wait, no copy to the host, no allocation.  The
+ * world's next step is never skipped as idle afterwards.  A mover whose body has gone, and a move-to mover with both tracks inactive, touch
+ * nothing.  dt must be finite and >= 0; dt == 0 returns without a launch. */
+int  sgp_movers_update(sgp_movers* ms, float dt);
+/* Waits for the updates in flight.  A mover that has not been updated since it was added reads as its initial state; slots that are not live
+ * read as zeros. */
+int  sgp_movers_get_states(sgp_movers* ms, uint32_t first, uint32_t n, sgp_mover_state* out);
+
 /* ---- overlap queries with any convex shape (JPH::NarrowPhaseQuery::CollideShape) --------------------
  * "What is inside this volume?": a box for a parcel or a trigger volume, a sphere for an explosion or an audio radius, the hull of an
  * object for a placement test before it is added -- thousands of them per call if need be.  Every query reports the contacts of its shape

@@ -311,6 +311,41 @@ class CraftState(C.Structure):
                 ("reserved_", u32)]
 
 
+MOVER_PATH, MOVER_MOVETO = 0, 1                                           # SGP_MOVER_*
+WAYPOINT_CURVE_IN, WAYPOINT_CURVE_OUT, WAYPOINT_STATION = 0, 1, 2         # SGP_WAYPOINT_*
+MOVER_EASE_LINEAR, MOVER_EASE_SMOOTHSTEP = 0, 1                           # SGP_MOVER_EASE_*
+MOVER_ORIENT_ALONG_PATH = 1
+MOVER_MAX_WAYPOINTS, MOVER_MAX_SEGMENTS_PER_UPDATE, MOVERS_MAX_CAPACITY, MOVERS_MAX_PATHS = 128, 64, 1 << 16, 1 << 12
+MOVER_ST = {"BODY_GONE": 1, "LEADER_GONE": 2, "OVERRUN": 4, "POS_ACTIVE": 8, "ROT_ACTIVE": 16}      # SGP_MOVER_ST_*
+
+
+class PathWaypoint(C.Structure):
+    """sgp_path_waypoint: PathWaypointIn of ObjectPathController."""
+    _fields_ = [("pos", f32 * 3), ("type", u32), ("pause_time", f32), ("speed", f32)]
+
+
+class PathSegment(C.Structure):
+    """sgp_path_segment: ObjectPathController::PathWaypoint, the derived values filled by sgp_path_prepare."""
+    _fields_ = [("pos", f32 * 3), ("type", u32), ("pause_time", f32), ("speed", f32), ("segment_len", f32), ("just_curve_len", f32),
+                ("entry_segment_len", f32), ("curve_angle", f32), ("curve_r", f32), ("exit_segment_unit_dir", f32 * 3)]
+
+
+class PathProgress(C.Structure):
+    _fields_ = [("waypoint_index", u32), ("dist_along_segment", f32), ("time_along_segment", f32)]
+
+
+class MoverDesc(C.Structure):
+    """sgp_mover_desc: one path mover (ObjectPathController) or move-to mover (ObjectMoveToController) of a batch."""
+    _fields_ = [("kind", u32), ("body", u32), ("flags", u32), ("path", u32), ("initial_time", C.c_double), ("tag", u64), ("leader", u32),
+                ("follow_dist", f32), ("base_rot", f32 * 4), ("hold_pos", f32 * 3), ("hold_rot", f32 * 4), ("reserved_", u32)]
+
+
+class MoverState(C.Structure):
+    """sgp_mover_state: what the last update of a mover did."""
+    _fields_ = [("status", u32), ("waypoint_index", u32), ("dist_along_segment", f32), ("time_along_segment", f32), ("pos", f32 * 3),
+                ("rot", f32 * 4), ("dir", f32 * 3), ("pos_elapsed", f32), ("rot_elapsed", f32), ("update_index", u32)]
+
+
 class CompoundChild(C.Structure):
     _fields_ = [("shape_type", i32), ("shape", f32 * 4), ("pos", f32 * 3), ("rot", f32 * 4)]
 
@@ -342,7 +377,8 @@ ABI_SIZEOF_ORDER = ["sgp_settings", "sgp_world_desc", "sgp_body_desc", "sgp_body
 ABI_SIZEOF_APPENDED = ["sgp_shape_query", None, "sgp_shape_cast", "sgp_cast_hit",
                        None, "sgp_character_desc", "sgp_character_input", "sgp_character_state", "sgp_character_contact",
                        None, "sgp_particle", "sgp_particle_state", "sgp_particle_event",      # (29 likewise)
-                       None, "sgp_craft_desc", "sgp_craft_input", "sgp_craft_state"]           # (33 likewise)
+                       None, "sgp_craft_desc", "sgp_craft_input", "sgp_craft_state",          # (33 likewise)
+                       None, "sgp_path_waypoint", "sgp_path_segment", "sgp_path_progress", "sgp_mover_desc", "sgp_mover_state"]      # (37 likewise)
 ABI_SIZEOF_ALL = ABI_SIZEOF_ORDER + ABI_SIZEOF_APPENDED
 
 STRUCTS = {"sgp_settings": Settings, "sgp_world_desc": WorldDesc, "sgp_body_desc": BodyDesc,
@@ -355,7 +391,9 @@ STRUCTS = {"sgp_settings": Settings, "sgp_world_desc": WorldDesc, "sgp_body_desc
            "sgp_cast_hit": CastHit, "sgp_character_desc": CharacterDesc, "sgp_character_input": CharacterInput,
            "sgp_character_state": CharacterState, "sgp_character_contact": CharacterContact,
            "sgp_particle": Particle, "sgp_particle_state": ParticleState, "sgp_particle_event": ParticleEvent,
-           "sgp_craft_desc": CraftDesc, "sgp_craft_input": CraftInput, "sgp_craft_state": CraftState}
+           "sgp_craft_desc": CraftDesc, "sgp_craft_input": CraftInput, "sgp_craft_state": CraftState,
+           "sgp_path_waypoint": PathWaypoint, "sgp_path_segment": PathSegment, "sgp_path_progress": PathProgress,
+           "sgp_mover_desc": MoverDesc, "sgp_mover_state": MoverState}
 
 body_desc_dtype = np.dtype(BodyDesc)
 body_state_dtype = np.dtype(BodyState)
@@ -383,6 +421,9 @@ particle_event_dtype = np.dtype(ParticleEvent)
 craft_desc_dtype = np.dtype(CraftDesc)
 craft_input_dtype = np.dtype(CraftInput)
 craft_state_dtype = np.dtype(CraftState)
+path_waypoint_dtype = np.dtype(PathWaypoint)
+path_segment_dtype = np.dtype(PathSegment)
+mover_state_dtype = np.dtype(MoverState)
 compound_child_dtype = np.dtype(CompoundChild)
 migration_dtype = np.dtype(Migration)
 
@@ -483,6 +524,19 @@ PROTOTYPES = {
     "crafts_attach_particles": (C.c_int, [vp, vp]),
     "crafts_update": (C.c_int, [vp, f32]),
     "crafts_get_states": (C.c_int, [vp, u32, u32, vp]),
+    "path_prepare": (C.c_int, [vp, u32, vp, P(C.c_double)]),
+    "path_advance": (C.c_int, [vp, u32, P(PathProgress), f32, P(u32)]),
+    "movers_create": (C.c_int, [vp, u32, u32, P(vp)]),
+    "movers_destroy": (C.c_int, [vp]),
+    "movers_path_add": (C.c_int, [vp, vp, u32, P(u32)]),
+    "movers_path_remove": (C.c_int, [vp, u32]),
+    "movers_path_get": (C.c_int, [vp, u32, vp, u32, P(u32)]),
+    "mover_add": (C.c_int, [vp, P(MoverDesc), P(u32)]),
+    "mover_remove": (C.c_int, [vp, u32]),
+    "movers_set_position_track": (C.c_int, [vp, u32, P(f32), P(f32), f32, u32, f32]),
+    "movers_set_rotation_track": (C.c_int, [vp, u32, P(f32), P(f32), f32, u32, f32]),
+    "movers_update": (C.c_int, [vp, f32]),
+    "movers_get_states": (C.c_int, [vp, u32, u32, vp]),
     "world_export_boundary": (C.c_int, [vp, P(f32), P(f32), f32, vp, u32, P(u32)]),
     "world_import_ghosts": (C.c_int, [vp, vp, u32]),
     "tiles_route": (C.c_int, [vp, u32, u32, vp, u32, f32, vp, u32, vp, vp, u32, P(u32)]),

@@ -57,18 +57,10 @@ __global__ void __launch_bounds__(TPB) k_apply_cmds(DV d, const BodyCmd* cmds, c
 		if (c.ops & CMD_MOVE_KINEMATIC) {
 			// MotionProperties::MoveKinematic: velocities that reach the target in dt
 			if (f_motion(f) == SGP_MOTION_KINEMATIC && c.dt > 0.0f) {
-				const v3 pos = V3(d.pose[POSE_F4 * (size_t)i]);
-				const quat q = Q4(d.pose[POSE_F4 * (size_t)i + 1]);
-				const v3 lv = v3_scale(v3_sub(V3(c.pos[0], c.pos[1], c.pos[2]), pos), 1.0f / c.dt);
 				quat t; t.x = c.rot[0]; t.y = c.rot[1]; t.z = c.rot[2]; t.w = c.rot[3];
-				quat cj; cj.x = -q.x; cj.y = -q.y; cj.z = -q.z; cj.w = q.w;
-				quat dq = quat_mul(t, cj);
-				if (dq.w < 0.0f) { dq.x = -dq.x; dq.y = -dq.y; dq.z = -dq.z; dq.w = -dq.w; }
-				const float sl = sqrtf(dq.x * dq.x + dq.y * dq.y + dq.z * dq.z);
-				v3 av = V3(0.0f, 0.0f, 0.0f);
-				if (sl > 1.0e-12f) { const float angle = sgd_quat_angle(sl, dq.w); av = v3_scale(V3(dq.x / sl, dq.y / sl, dq.z / sl), angle / c.dt); }
-				d.vel[VEL_F4 * (size_t)i] = F4(lv, d.vel[VEL_F4 * (size_t)i].w);
-				d.vel[VEL_F4 * (size_t)i + 1] = F4(av, d.vel[VEL_F4 * (size_t)i + 1].w);
+				v3 lv, av;
+				move_kinematic_velocities(d, i, V3(c.pos[0], c.pos[1], c.pos[2]), t, c.dt, lv, av);      // (sgp_dev_edits.h: the movers call the same function)
+				store_velocities(d, i, lv, av);
 				if (!(f & BF_ALIAS)) f = activate_body(d, i, f);      // (a mesh body's alias slots follow its pose and velocities, they are never awake themselves)
 			}
 			continue;

@@ -17,6 +17,7 @@
 //   sgp_k_characters.hip   A7     k_characters_update (a wave per character: the whole Update / ExtendedUpdate), k_characters_push, k_characters_sync (sgp_characters_*)
 //   sgp_k_particles.hip    A7     k_particles_update (a lane per particle: raycast_one + ParticleManager::think), k_particles_scan, k_particles_scatter (stable compaction + events), k_particles_append (sgp_particles_*)
 //   sgp_k_crafts.hip       A7     k_crafts_update (a lane per craft: HoverCarPhysics::update / BoatPhysics::update, forces into the accumulators), k_crafts_scan, k_crafts_compact (particle hand-over) (sgp_crafts_*)
+//   sgp_k_movers.hip       A5     k_movers_update (a lane per mover: ObjectPathController::update / ObjectMoveToController::update, MoveKinematic on the body), k_movers_follow (the carriages) (sgp_movers_*)
 //   sgp_k_edits.hip        A5/A6  k_apply_cmds, k_ghost_refresh, read-back
 //   sgp_k_tiles.hip        (e)    tile export / routing, re-tiling histograms
 //   sgp_k_checkpoint.hip          k_ckpt_copy: the segmented copy of sgp_world_checkpoint / sgp_world_rollback
@@ -570,6 +571,33 @@ struct CraftBufs {
 void launch_crafts_update(const DV& d, const CraftBufs& b, float dt, int water_enabled, float water_z, hipStream_t s);
 void launch_crafts_gather(const CraftBufs& b, hipStream_t s);      // scan + compact: b.dense[0 .. b.emit_off[b.n]) in ascending craft, then emission order
 void launch_crafts_sync(const CraftBufs& b, hipStream_t s);        // get_states with host edits pending and no update to carry them
+// ---- batched path and move-to controllers (sgp_k_movers.hip, sgp_dev_movers.h, sgp_mover_path.h) -----------------------------------------------------------
+// The host owns the descriptions, the track commands and the prepared paths (MoverRec, sgp_path_segment: uploaded when they change); the device owns the
+// walkers' progress, the tracks' clocks and the held pose (MoverDyn) and reaches the host's wishes through serial numbers, as the crafts do.
+struct MoverRec {
+	uint32_t alive, gone, reset_serial, kind;             // gone: the body is no longer the one the mover was added on
+	uint32_t body, flags, path, leader;                   // leader: a slot of the batch, or SGP_INVALID_ID (a walker, or a move-to mover)
+	uint32_t leader_gone, pos_serial, rot_serial, init_index;
+	float init_dist, init_time, follow_dist;              // a walker's state when it was added (mp_advance on the host)
+	float base_rot[4], hold_pos[3], hold_rot[4];
+	float pos_start[3], pos_target[3], pos_duration, pos_elapsed; uint32_t pos_easing;      // the track pos_serial announces
+	float rot_start[4], rot_target[4], rot_duration, rot_elapsed; uint32_t rot_easing;
+};
+struct MoverDyn {
+	uint32_t reset_serial, pos_serial, rot_serial, update_index;
+	uint32_t index; float dist, time;                     // a walker's progress
+	uint32_t pos_active, rot_active; float pos_elapsed, rot_elapsed;
+	float last_pos[3], last_rot[4];                       // what an inactive track holds
+};
+struct MoverBufs {
+	const MoverRec* rec; MoverDyn* dyn; sgp_mover_state* st;
+	uint2* pub;                                           // [mover]: (waypoint_index, dist_along_segment) a walker published in the running update
+	const sgp_path_segment* segs;                         // [path][SGP_MOVER_MAX_WAYPOINTS]
+	const uint32_t* path_n;                               // [path]: waypoints of the path (0: no such path)
+	uint32_t n, n_paths;                                  // slots in use (high-water marks)
+};
+void launch_movers_update(const DV& d, const MoverBufs& b, float dt, hipStream_t s);      // walkers and move-to movers
+void launch_movers_follow(const DV& d, const MoverBufs& b, float dt, hipStream_t s);      // followers, behind launch_movers_update
 void launch_export_boundary(const DV& d, uint32_t nb, float3 lo, float3 hi, float margin, sgp_ghost_record* out, uint32_t cap, uint32_t* count, hipStream_t s);
 
 // ---- tile exchange with the routing on the device (sgp_tiles_*) ----------------------------------------------------

@@ -16,6 +16,7 @@
 #include "sgp_k_shapecast.hip"
 #include "sgp_k_particles.hip"
 #include "sgp_k_crafts.hip"
+#include "sgp_k_movers.hip"
 #include "sgp_k_vehicle.hip"
 #include "sgp_k_tiles.hip"
 #include "sgp_k_checkpoint.hip"

@@ -84,6 +84,8 @@ SGP_API int sgp_abi_sizeof(int which)
 	case 28: return (int)sizeof(sgp_character_contact);      // (24 stays -1, as 21 does: bindings that know 24 structs probe it for the end of the list)
 	case 30: return (int)sizeof(sgp_particle); case 31: return (int)sizeof(sgp_particle_state); case 32: return (int)sizeof(sgp_particle_event);      // (29 stays -1 likewise)
 	case 34: return (int)sizeof(sgp_craft_desc); case 35: return (int)sizeof(sgp_craft_input); case 36: return (int)sizeof(sgp_craft_state);      // (33 stays -1 likewise)
+	case 38: return (int)sizeof(sgp_path_waypoint); case 39: return (int)sizeof(sgp_path_segment); case 40: return (int)sizeof(sgp_path_progress);      // (37 stays -1 likewise)
+	case 41: return (int)sizeof(sgp_mover_desc); case 42: return (int)sizeof(sgp_mover_state);
 	default: return -1;
 	}
 }

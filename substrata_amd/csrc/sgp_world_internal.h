@@ -7,6 +7,7 @@
 //   sgp_world_characters.hip the batched character controller (sgp_characters_*)
 //   sgp_world_particles.hip  the batched point particles (sgp_particles_*)
 //   sgp_world_crafts.hip     the batched hover cars and boats (sgp_crafts_*)
+//   sgp_world_movers.hip     the batched path and move-to controllers (sgp_movers_*), sgp_path_prepare / sgp_path_advance
 //                            (what the two batches share -- owner, zeroed device arrays, the upload fence: WorldBatch, below)
 //   sgp_stage_carve.h        the regions of one call in the stage buffer (host only, no HIP types)
 //   sgp_world_tiles.hip      ghost import / export, the tile exchange over RCCL, re-tiling

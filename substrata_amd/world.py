@@ -117,6 +117,81 @@ class Characters:
             pass
 
 
+class Movers:
+    """A batch of path and move-to controllers of one world (sgp_movers): update() enqueues and returns; states() waits."""
+
+    def __init__(self, world, capacity, path_capacity):
+        self._w, self._h = world, C.c_void_p()
+        world._check(world._fn("movers_create")(world._h, int(capacity), int(path_capacity), C.byref(self._h)), "movers_create")
+        self.capacity = int(capacity)
+
+    def add_path(self, waypoints):
+        """waypoints: array of abi.path_waypoint_dtype (pos, type, pause_time, speed); returns the path id."""
+        wp = np.ascontiguousarray(waypoints, dtype=abi.path_waypoint_dtype).reshape(-1)
+        p = C.c_uint32(0)
+        self._w._check(self._w._fn("movers_path_add")(self._h, wp.ctypes.data, len(wp), C.byref(p)), "movers_path_add")
+        return int(p.value)
+
+    def remove_path(self, path):
+        self._w._check(self._w._fn("movers_path_remove")(self._h, int(path)), "movers_path_remove")
+
+    def path_segments(self, path):
+        out = np.zeros(abi.MOVER_MAX_WAYPOINTS, dtype=abi.path_segment_dtype)
+        n = C.c_uint32(0)
+        self._w._check(self._w._fn("movers_path_get")(self._h, int(path), out.ctypes.data, len(out), C.byref(n)), "movers_path_get")
+        return out[:n.value].copy()
+
+    def add_path_mover(self, body, path, initial_time=0.0, leader=None, follow_dist=0.0, base_rot=(0.0, 0.0, 0.0, 1.0), orient_along_path=False, tag=0):
+        d = abi.MoverDesc(kind=abi.MOVER_PATH, body=int(body), flags=abi.MOVER_ORIENT_ALONG_PATH if orient_along_path else 0, path=int(path),
+                          initial_time=float(initial_time), tag=int(tag), leader=abi.INVALID_ID if leader is None else int(leader), follow_dist=float(follow_dist))
+        d.base_rot[:] = [float(x) for x in base_rot]
+        d.hold_rot[3] = 1.0
+        return self.add(d)
+
+    def add_moveto_mover(self, body, hold_pos, hold_rot=(0.0, 0.0, 0.0, 1.0), tag=0):
+        d = abi.MoverDesc(kind=abi.MOVER_MOVETO, body=int(body), leader=abi.INVALID_ID, tag=int(tag))
+        d.base_rot[3] = 1.0
+        d.hold_pos[:] = [float(x) for x in hold_pos]
+        d.hold_rot[:] = [float(x) for x in hold_rot]
+        return self.add(d)
+
+    def add(self, desc):
+        i = C.c_uint32(0)
+        self._w._check(self._w._fn("mover_add")(self._h, C.byref(desc), C.byref(i)), "mover_add")
+        return int(i.value)
+
+    def remove(self, i):
+        self._w._check(self._w._fn("mover_remove")(self._h, int(i)), "mover_remove")
+
+    def set_position_track(self, i, start, target, duration, easing=abi.MOVER_EASE_LINEAR, cur_elapsed=0.0):
+        a, b = (C.c_float * 3)(*[float(x) for x in start]), (C.c_float * 3)(*[float(x) for x in target])
+        self._w._check(self._w._fn("movers_set_position_track")(self._h, int(i), a, b, float(duration), int(easing), float(cur_elapsed)), "movers_set_position_track")
+
+    def set_rotation_track(self, i, start, target, duration, easing=abi.MOVER_EASE_LINEAR, cur_elapsed=0.0):
+        a, b = (C.c_float * 4)(*[float(x) for x in start]), (C.c_float * 4)(*[float(x) for x in target])
+        self._w._check(self._w._fn("movers_set_rotation_track")(self._h, int(i), a, b, float(duration), int(easing), float(cur_elapsed)), "movers_set_rotation_track")
+
+    def update(self, dt=1.0 / 60.0):
+        self._w._check(self._w._fn("movers_update")(self._h, float(dt)), "movers_update")
+
+    def states(self, first=0, n=None):
+        n = self.capacity - first if n is None else int(n)
+        out = np.zeros(n, dtype=abi.mover_state_dtype)
+        self._w._check(self._w._fn("movers_get_states")(self._h, int(first), n, out.ctypes.data), "movers_get_states")
+        return out
+
+    def close(self):
+        if self._h:
+            self._w._fn("movers_destroy")(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Crafts:
     """A batch of hover cars and boats of one world (sgp_crafts): update() enqueues and returns; states() waits."""
 
@@ -601,6 +676,10 @@ class CWorld:
     def crafts(self, capacity):
         """A batch of up to `capacity` hover cars and boats that belongs to this world (close it before the world)."""
         return Crafts(self, capacity)
+
+    def movers(self, capacity, path_capacity=16):
+        """A batch of up to `capacity` path and move-to controllers over `path_capacity` shared paths that belongs to this world (close it before the world)."""
+        return Movers(self, capacity, path_capacity)
 
     def characters(self, capacity):
         """A batch of up to `capacity` virtual characters that belongs to this world (close it before the world)."""
