@@ -5,6 +5,17 @@ linked; an object is rebuilt only when its source, a header or this script is ne
 
 -ffp-contract=off: fp32 expressions round exactly as written (no FMA contraction), the contract that lets the parity
 tests compare the device path with the CPU oracle to rounding.  Correctly rounded fp32 divide/sqrt is hipcc's default.
+
+SOURCE_FLAGS: extra flags per source file.  Four stage files of the world step (sgp_k_solve, sgp_k_narrowphase, sgp_k_sweep,
+sgp_k_vehicle) are built with -fno-slp-vectorize: under plain -O3 the SLP vectorizer pairs neighbouring scalar f32 multiplies and adds
+of the v3 arithmetic into v_pk_mul_f32 / v_pk_add_f32 and pays for the aligned register pairs with v_mov_b32 and registers
+(docs/KERNELS.md, "f32 pairing"; tools/kernel_resources.py prints the table).  Each packed instruction becomes the two IEEE
+operations it stood for: results do not change.  The load/store vectorizer is another pass and is not touched.  A file has the
+flag only where its kernels measured no slower without the pairing (profiles/scalar_f32_step_kernels.md): sgp_k_constraints.hip
+(k_setup) and sgp_k_solve_hc.hip (k_solve_hc, a stage file of its own for this reason) measured slower and keep the pairing.  The
+query, character, particle, craft, mover, cast, mesh, tile, checkpoint and edit files have not been measured and stay as they were.
+The unity translation unit of --experiments contains every stage file and takes the flag as a whole, so in such a build k_setup,
+k_solve_hc and the query, character, particle, ... kernels are compiled without the pairing too.
 """
 import os
 import subprocess
@@ -22,6 +33,19 @@ HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.joi
 EXPERIMENT_FILES = [os.path.join("experiments", f) for f in sorted(os.listdir(os.path.join(CSRC, "experiments")))]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC",
          "-fvisibility=hidden", "-mllvm", "-amdgpu-kernarg-preload-count=16", "-Wall", "-Wno-unused-function", "-Wno-unused-result", "-Wno-unused-value"]
+NO_F32_PAIRING = ["-fno-slp-vectorize"]
+SOURCE_FLAGS = {
+    "sgp_k_solve.hip": NO_F32_PAIRING,
+    "sgp_k_narrowphase.hip": NO_F32_PAIRING,
+    "sgp_k_sweep.hip": NO_F32_PAIRING,
+    "sgp_k_vehicle.hip": NO_F32_PAIRING,
+    UNITY: NO_F32_PAIRING,
+}
+
+
+def source_flags(src):
+    """The whole flag list build() compiles `src` (a file name in csrc/) with, without the -c / -o part."""
+    return FLAGS + list(SOURCE_FLAGS.get(src, ()))
 
 
 def hipcc():
@@ -73,7 +97,7 @@ def build(force=False, verbose=False, extra=()):
     todo = [s for s in _sources(experiments) if force or _newer(common + [os.path.join(CSRC, s)], _obj(s, experiments))]
 
     def compile_one(src):
-        cmd = [hipcc()] + FLAGS + list(extra) + ["-c", os.path.join(CSRC, src), "-o", _obj(src, experiments)]
+        cmd = [hipcc()] + source_flags(src) + list(extra) + ["-c", os.path.join(CSRC, src), "-o", _obj(src, experiments)]
         if verbose:
             print(" ".join(cmd), flush=True)
         return src, subprocess.run(cmd, capture_output=True, text=True)

@@ -385,3 +385,25 @@ SGP_DEV void solve_position_pair_at(const DV& d, const ConstraintArrays& ca, uin
 // a component of more than 128 constraints and the overflow colour go through the serial catch-all at the end of the same launch.
 SGP_DEV uint32_t uf_prio(uint32_t x);
 SGP_DEV uint32_t uf_find(const uint32_t* parent, uint32_t x);
+// (shared by the build kernels, sgp_k_solve.hip, and the component launch, sgp_k_solve_hc.hip)
+#define HC_CLASSES 9                  // component size classes: 1 << class constraints
+#define HC_WG_PAIRS 256               // lane pairs (= constraints) per workgroup (8 waves: 2 per SIMD, a constraint half keeps its ~150 registers)
+#define HC_TPB (2 * HC_WG_PAIRS)
+#define HC_BIG 0xFFFFFFFFu
+#define HC_NONE 0xFFFFFFFFu
+#define NPCOL_CATCH_ALL (1 << 17)     // np_col: the constraint's component is too large for a workgroup
+#define HC_BIG_LIST (4 * HC_WG_PAIRS)  // the catch-all's own list of such constraints (up to four per lane pair; more: it searches the colours for the flag)
+
+// the overflow colour (a body with > 63 contacts; Jolt's non-parallel split) is solved serially in ascending priority
+SGP_DEV uint32_t overflow_next(const ConstraintArrays& ca, uint32_t first, uint32_t count, uint64_t& last, bool& have_last)
+{
+	// the overflow constraint with the lowest priority above `last` (selection by scanning: the overflow colour is rare and short)
+	uint64_t best = ~0ull; uint32_t bslot = first;
+	for (uint32_t k = 0; k < count; ++k) {
+		const uint2 okab = con_ab(ca, first + k); const uint64_t pr = sgp_mix64(((uint64_t)okab.x << 32) | okab.y);
+		if ((!have_last || pr > last) && pr <= best) { best = pr; bslot = first + k; }
+	}
+	last = best; have_last = true;
+	return bslot;
+}
+SGP_DEV uint32_t overflow_next(const DV& d, uint32_t first, uint32_t count, uint64_t& last, bool& have_last) { return overflow_next(CUR(d), first, count, last, have_last); }

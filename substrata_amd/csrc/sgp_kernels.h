@@ -8,7 +8,8 @@
 //   sgp_k_narrowphase.hip  K4     k_narrowphase (sphere / box / capsule manifolds, sgp_device_collide.h), k_wake_pairs (in-step activation), k_narrowphase_hull*
 //   sgp_k_mesh.hip         K4     k_narrowphase_mesh<8|64, kinds>: (body, static mesh) pairs by lanes
 //   sgp_k_constraints.hip  K5/K6  k_colour_* (deterministic colouring), k_setup (contact-cache match, constraint rows), k_cache_build, k_contact_events
-//   sgp_k_solve.hip        K7     k_warm_bodies, k_solve_colour<0|1|2>, k_hc_* + k_solve_hc (high colours by connected component), k_solve_tail*, k_solve_small*
+//   sgp_k_solve.hip        K7     k_warm_bodies, k_solve_colour<0|1|2>, k_hc_* (high colours by connected component: the layout), k_solve_tail*, k_solve_small*
+//   sgp_k_solve_hc.hip     K7     k_solve_hc (high colours by connected component: the launch that solves them)
 //   sgp_k_sweep.hip        K8/K1/K9/A3  the body-array sweep k_pre_solve + k_integrate_pose + k_finalize, k_island_*, k_sleep_apply, k_buoyancy (PhysicsWorld.cpp:1367-1442)
 //   sgp_k_vehicle.hip      (f)1   k_vehicle_cast / controller, the vehicle rows inside the solver passes (k_solve_colour_veh)
 //   sgp_k_queries.hip      A7     k_raycast, k_collide_capsules, k_spherecast

@@ -9,6 +9,7 @@
 #include "sgp_k_mesh.hip"
 #include "sgp_k_constraints.hip"
 #include "sgp_k_solve.hip"
+#include "sgp_k_solve_hc.hip"
 #include "sgp_k_sweep.hip"
 #include "sgp_k_edits.hip"
 #include "sgp_k_queries.hip"
