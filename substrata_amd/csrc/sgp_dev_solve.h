@@ -167,8 +167,10 @@ SGP_DEV float half_jv(v3 lv, v3 av, v3 axis, v3 c, int side)
 SGP_DEV void half_apply(v3& lv, v3& av, float im, v3 axis, v3 iv, float lambda, int side)
 {
 	if (!(im > 0.0f)) return;
-	if (side) { lv = v3_add(lv, v3_scale(axis, lambda * im)); av = v3_add(av, v3_scale(iv, lambda)); }
-	else      { lv = v3_sub(lv, v3_scale(axis, lambda * im)); av = v3_sub(av, v3_scale(iv, lambda)); }
+	// ONE path for both lanes: `side` alternates lane by lane, so a branch on it runs both ways in every wave.  The sign goes into the operand:
+	// x * (-l) = -(x * l) and a - b = a + (-b) bit for bit in IEEE arithmetic (signed zeros included), body 1 subtracts what body 2 adds.
+	const float sl = side ? lambda : -lambda;
+	lv = v3_add(lv, v3_scale(axis, sl * im)); av = v3_add(av, v3_scale(iv, sl));
 }
 
 // One contact manifold, one velocity iteration (ContactConstraintManager::SolveVelocityConstraints): friction rows of every point first (they
@@ -335,8 +337,9 @@ SGP_DEV void pos_half_solve_rec(const DV& d, const PosHalf& ph, int side, float4
 			if (eff <= 0.0f) continue;
 			const float lambda = -eff * d.st.baumgarte * sep;
 			if (im > 0.0f) {
-				if (side) { pos = v3_add(pos, v3_scale(nrm, lambda * im)); q = quat_add_rotation_step(q, v3_scale(Ic, lambda)); }
-				else      { pos = v3_sub(pos, v3_scale(nrm, lambda * im)); q = quat_add_rotation_step(q, v3_scale(Ic, -lambda)); }
+				const float sl = side ? lambda : -lambda;      // (one path, one inlined rotation step for both lanes: see half_apply)
+				pos = v3_add(pos, v3_scale(nrm, sl * im));
+				q = quat_add_rotation_step(q, v3_scale(Ic, sl));
 				R = quat_to_m33(q);
 			}
 			moved = true;

@@ -130,13 +130,14 @@ SGP_DEV quat quat_add_rotation_step(quat q, v3 w)
 
 SGP_DEV v3 v3_normalized_perpendicular(v3 n)
 {
-	if (fabsf(n.x) > fabsf(n.y)) {
-		const float len = sqrtf(n.x * n.x + n.z * n.z);
-		return V3(n.z / len, 0.0f, -n.x / len);
-	} else {
-		const float len = sqrtf(n.y * n.y + n.z * n.z);
-		return V3(0.0f, n.z / len, -n.y / len);
-	}
+	// (x, 0, z) form when |n.x| > |n.y|, (0, y, z) form otherwise (a tie too).  Contact normals split about evenly between the two, so a branch
+	// here runs both ways in practically every wave: the operand is selected first, then ONE root and two divisions -- the same operations on the same
+	// operands as either form written out.
+	const bool xz = fabsf(n.x) > fabsf(n.y);
+	const float a = xz ? n.x : n.y;
+	const float len = sqrtf(a * a + n.z * n.z);
+	const float u = n.z / len, v = -a / len;
+	return V3(xz ? u : 0.0f, xz ? 0.0f : u, v);
 }
 
 SGP_DEV uint64_t sgp_mix64(uint64_t z)
