@@ -4,21 +4,20 @@
 #include "sgp_world_internal.h"
 
 struct sgp_characters : WorldBatch {
-	uint32_t cap = 0, high = 0, n_alive = 0;
-	std::vector<CharRec> rec; std::vector<CharIn> in; std::vector<uint32_t> free_list;
-	bool rec_dirty = false, in_dirty = false;
+	BatchSlots slots;
+	// the copy of the world's DV the update kernel reads through a pointer: a mirror of `one` record, brought up to date by every update (dv_valid: it has been the world's once)
+	Mirror<DV> dv; bool dv_valid = false; const uint32_t one = 1;
+	Mirror<CharRec> rec; Mirror<CharIn> in;
 	// device
-	DV* d_dv = nullptr; DV dv_uploaded; bool dv_valid = false;
-	CharRec* d_rec = nullptr; CharIn* d_in = nullptr; CharState* d_st = nullptr; CharContact* d_active = nullptr; uint32_t* d_seen = nullptr;
+	CharState* d_st = nullptr; CharContact* d_active = nullptr; uint32_t* d_seen = nullptr;
 	CharPush* d_push = nullptr; uint32_t* d_n_push = nullptr; CharAdded* d_added = nullptr; uint32_t* d_n_added = nullptr;
-	size_t up_rec = 0, up_in = 0;      // the pinned staging of the uploads (WorldBatch::h_up): [DV][records at up_rec][inputs at up_in]
 };
 
 static CharBufs chars_bufs(const sgp_characters* cs)
 {
 	CharBufs b;
-	b.rec = cs->d_rec; b.in = cs->d_in; b.st = cs->d_st; b.active = cs->d_active; b.seen = cs->d_seen;
-	b.push = cs->d_push; b.n_push = cs->d_n_push; b.push_any = cs->d_n_push + cs->cap; b.added = cs->d_added; b.n_added = cs->d_n_added; b.n = cs->high;
+	b.rec = cs->rec.d(); b.in = cs->in.d(); b.st = cs->d_st; b.active = cs->d_active; b.seen = cs->d_seen;
+	b.push = cs->d_push; b.n_push = cs->d_n_push; b.push_any = cs->d_n_push + cs->slots.cap; b.added = cs->d_added; b.n_added = cs->d_n_added; b.n = cs->slots.high;
 	return b;
 }
 
@@ -40,35 +39,23 @@ SGP_API void sgp_default_character_desc(sgp_character_desc* d)
 	d->walk_stairs_min_step_forward = 0.02f; d->walk_stairs_step_forward_test = 0.15f; d->walk_stairs_cos_angle_forward_contact = 0.2588f;
 }
 
-SGP_API int sgp_characters_destroy(sgp_characters* cs)
-{
-	if (!cs) return fail(SGP_ERR_INVALID, "sgp_characters_destroy: NULL");
-	cs->release();
-	delete cs;
-	return SGP_OK;
-}
+SGP_API int sgp_characters_destroy(sgp_characters* cs) { return batch_destroy(cs, "sgp_characters_destroy"); }
 
 SGP_API int sgp_characters_create(sgp_world* w, uint32_t capacity, sgp_characters** out)
 {
 	if (!w || !out || capacity == 0 || capacity > (1u << 20)) return fail(SGP_ERR_INVALID, "sgp_characters_create: NULL world or out, or a capacity of 0 or beyond 2^20");
-	if (world_holds_ghosts(w)) return fail(SGP_ERR_INVALID, "sgp_characters_create: the world holds ghost bodies (characters of tiled worlds are not supported)");
+	if (world_holds_ghosts(w)) return fail_ghosts("sgp_characters_create", "characters");
 	hipSetDevice(w->device);
 	sgp_characters* cs = new sgp_characters();
-	cs->cap = capacity;
-	cs->rec.resize(capacity); cs->in.resize(capacity);
-	memset(cs->rec.data(), 0, sizeof(CharRec) * capacity); memset(cs->in.data(), 0, sizeof(CharIn) * capacity);
-	for (uint32_t i = 0; i < capacity; ++i) cs->in[i].ignore = SGP_INVALID_ID;
 	const size_t n = capacity;
-	StageCarve up;
-	up.add(sizeof(DV)); cs->up_rec = up.add(sizeof(CharRec) * n); cs->up_in = up.add(sizeof(CharIn) * n);
-	bool ok = cs->adopt(w);
-	ok = ok && cs->alloc(cs->d_dv, 1) && cs->alloc(cs->d_rec, n) && cs->alloc(cs->d_in, n) && cs->alloc(cs->d_st, n)
+	cs->slots.cap = capacity;
+	cs->dv.shape(1, &cs->one); cs->rec.shape(n, &cs->slots.high); cs->in.shape(n, &cs->slots.high);
+	for (uint32_t i = 0; i < capacity; ++i) cs->in[i].ignore = SGP_INVALID_ID;
+	bool ok = cs->adopt(w) && cs->create_mirrors({ &cs->dv, &cs->rec, &cs->in });
+	ok = ok && cs->alloc(cs->d_st, n)
 	        && cs->alloc(cs->d_active, n * SGP_CHAR_MAX_CONTACTS) && cs->alloc(cs->d_seen, n * SGP_CHAR_MAX_CONTACTS)
 	        && cs->alloc(cs->d_push, n * SGP_CHAR_MAX_PUSHES) && cs->alloc(cs->d_n_push, n + 1) && cs->alloc(cs->d_added, n * SGP_CHAR_MAX_ADDED) && cs->alloc(cs->d_n_added, n);
-	ok = ok && cs->pin(up.total);
-	if (!ok) { (void)hipGetLastError(); sgp_characters_destroy(cs); return fail(SGP_ERR_HIP, "sgp_characters_create: allocation"); }
-	*out = cs;
-	return SGP_OK;
+	return batch_created(cs, ok, out, "sgp_characters_create");
 }
 
 static const char* character_desc_fault(const sgp_character_desc& d)
@@ -92,10 +79,8 @@ SGP_API int sgp_character_add(sgp_characters* cs, const sgp_character_desc* desc
 	if (!batch_usable(cs) || !desc || !pos || !id_out) return fail(SGP_ERR_INVALID, "sgp_character_add: NULL, or the batch's world is gone");
 	if (!finite3(pos)) return fail(SGP_ERR_INVALID, "sgp_character_add: non-finite position");
 	if (const char* what = character_desc_fault(*desc)) { char msg[160]; snprintf(msg, sizeof(msg), "sgp_character_add: %s", what); return fail(SGP_ERR_INVALID, msg); }
-	uint32_t id;
-	if (!cs->free_list.empty()) { id = cs->free_list.back(); cs->free_list.pop_back(); }
-	else if (cs->high < cs->cap) id = cs->high++;
-	else return fail(SGP_ERR_CAPACITY, "sgp_character_add: the batch is full");
+	const uint32_t id = cs->slots.take();
+	if (id == BatchSlots::none) return fail(SGP_ERR_CAPACITY, "sgp_character_add: the batch is full");
 	CharRec& r = cs->rec[id];
 	const uint32_t reset = r.reset_serial + 1u, pose = r.pose_serial + 1u;
 	memset(&r, 0, sizeof(r));
@@ -113,21 +98,20 @@ SGP_API int sgp_character_add(sgp_characters* cs, const sgp_character_desc* desc
 	CharIn& in = cs->in[id];
 	const uint32_t in_serial = in.serial + 1u;
 	memset(&in, 0, sizeof(in)); in.ignore = SGP_INVALID_ID; in.serial = in_serial;
-	cs->rec_dirty = cs->in_dirty = true;
-	cs->n_alive++;
+	cs->rec.dirty = cs->in.dirty = true;
 	*id_out = id;
 	return SGP_OK;
 }
 
-static bool char_live(const sgp_characters* cs, uint32_t id) { return id < cs->high && cs->rec[id].alive; }
+static bool char_live(const sgp_characters* cs, uint32_t id) { return id < cs->slots.high && cs->rec[id].alive; }
 
 SGP_API int sgp_character_remove(sgp_characters* cs, uint32_t id)
 {
 	if (!batch_usable(cs) || !char_live(cs, id)) return fail(SGP_ERR_INVALID, "sgp_character_remove: no such character");
 	hipSetDevice(cs->w->device);
 	HIP_TRY(hipMemsetAsync(cs->d_n_added + id, 0, sizeof(uint32_t), cs->w->stream));      // (its pending contact records go with it: the slot's next character starts with none)
-	cs->rec[id].alive = 0; cs->rec_dirty = true;
-	cs->free_list.push_back(id); cs->n_alive--;
+	cs->rec[id].alive = 0; cs->rec.dirty = true;
+	cs->slots.give_back(id);
 	return SGP_OK;
 }
 
@@ -136,7 +120,7 @@ SGP_API int sgp_characters_set_pose(sgp_characters* cs, const uint32_t* ids, con
 	if (!batch_usable(cs) || (n && (!ids || !pos))) return fail(SGP_ERR_INVALID, "sgp_characters_set_pose: NULL");
 	for (uint32_t i = 0; i < n; ++i) if (!char_live(cs, ids[i]) || !finite3(pos + 3 * i)) return fail(SGP_ERR_INVALID, "sgp_characters_set_pose: no such character, or a non-finite position");      // (all or nothing)
 	for (uint32_t i = 0; i < n; ++i) { CharRec& r = cs->rec[ids[i]]; memcpy(r.pose, pos + 3 * i, 12); r.pose_serial++; }
-	if (n) cs->rec_dirty = true;
+	if (n) cs->rec.dirty = true;
 	return SGP_OK;
 }
 
@@ -146,14 +130,14 @@ SGP_API int sgp_characters_set_shape(sgp_characters* cs, uint32_t id, float radi
 	if (!std::isfinite(radius) || !std::isfinite(half_height) || !finite3(offset) || !(radius > 0.0f) || !(half_height >= 0.0f)) return fail(SGP_ERR_INVALID, "sgp_characters_set_shape: a non-finite or non-positive capsule size");
 	CharRec& r = cs->rec[id];
 	r.radius = radius; r.half_height = half_height; memcpy(r.offset, offset, 12);
-	cs->rec_dirty = true;
+	cs->rec.dirty = true;
 	return SGP_OK;
 }
 
 SGP_API int sgp_characters_set_inputs(sgp_characters* cs, uint32_t first, uint32_t n, const sgp_character_input* inputs)
 {
 	if (!batch_usable(cs) || (n && !inputs)) return fail(SGP_ERR_INVALID, "sgp_characters_set_inputs: NULL");
-	if ((uint64_t)first + n > cs->high) return fail(SGP_ERR_INVALID, "sgp_characters_set_inputs: range beyond the last character");
+	if ((uint64_t)first + n > cs->slots.high) return fail(SGP_ERR_INVALID, "sgp_characters_set_inputs: range beyond the last character");
 	for (uint32_t i = 0; i < n; ++i) {
 		if (!finite3(inputs[i].velocity)) return fail(SGP_ERR_INVALID, "sgp_characters_set_inputs: non-finite velocity");
 		if (inputs[i].flags & ~(SGP_CHAR_EXTENDED | SGP_CHAR_NO_SLIDE | SGP_CHAR_DISABLED)) return fail(SGP_ERR_INVALID, "sgp_characters_set_inputs: unknown flag");
@@ -162,69 +146,35 @@ SGP_API int sgp_characters_set_inputs(sgp_characters* cs, uint32_t first, uint32
 		CharIn& in = cs->in[first + i];
 		memcpy(in.vel, inputs[i].velocity, 12); in.ignore = inputs[i].ignore_id; in.flags = inputs[i].flags; in.serial++;
 	}
-	if (n) cs->in_dirty = true;
+	if (n) cs->in.dirty = true;
 	return SGP_OK;
-}
-
-// what changed on the host -> the device, behind whatever the stream holds (no wait for the stream; only for the previous upload to have left the staging buffer)
-static int chars_upload(sgp_characters* cs, bool with_dv)
-{
-	sgp_world* w = cs->w;
-	const bool dv_dirty = with_dv && (!cs->dv_valid || memcmp(&cs->dv_uploaded, &w->dv, sizeof(DV)) != 0);
-	if (!dv_dirty && !cs->rec_dirty && !cs->in_dirty) return SGP_OK;
-	{ int r = cs->upload_begin(); if (r != SGP_OK) return r; }
-	if (dv_dirty) {
-		memcpy(cs->h_up, &w->dv, sizeof(DV));
-		HIP_TRY(hipMemcpyAsync(cs->d_dv, cs->h_up, sizeof(DV), hipMemcpyHostToDevice, w->stream));
-		memcpy(&cs->dv_uploaded, &w->dv, sizeof(DV)); cs->dv_valid = true;
-	}
-	if (cs->rec_dirty && cs->high) {
-		memcpy(cs->h_up + cs->up_rec, cs->rec.data(), sizeof(CharRec) * cs->high);
-		HIP_TRY(hipMemcpyAsync(cs->d_rec, cs->h_up + cs->up_rec, sizeof(CharRec) * cs->high, hipMemcpyHostToDevice, w->stream));
-	}
-	if (cs->in_dirty && cs->high) {
-		memcpy(cs->h_up + cs->up_in, cs->in.data(), sizeof(CharIn) * cs->high);
-		HIP_TRY(hipMemcpyAsync(cs->d_in, cs->h_up + cs->up_in, sizeof(CharIn) * cs->high, hipMemcpyHostToDevice, w->stream));
-	}
-	cs->rec_dirty = cs->in_dirty = false;
-	return cs->upload_end();
 }
 
 SGP_API int sgp_characters_update(sgp_characters* cs, float dt)
 {
-	if (!batch_usable(cs)) return fail(SGP_ERR_INVALID, "sgp_characters_update: NULL, or the batch's world is gone");
-	if (!std::isfinite(dt) || !(dt > 0.0f)) return fail(SGP_ERR_INVALID, "sgp_characters_update: dt must be finite and positive");
+	{ int r = batch_update_admit(cs, "sgp_characters_update", "characters", std::isfinite(dt) && dt > 0.0f, "positive"); if (r != SGP_OK) return r; }
 	sgp_world* w = cs->w;
-	if (world_holds_ghosts(w)) return fail(SGP_ERR_INVALID, "sgp_characters_update: the world holds ghost bodies (characters of tiled worlds are not supported)");
-	{ int r = (cs->high && cs->n_alive) ? query_prelude(w) : flush_cmds(w); if (r != SGP_OK) return r; }
-	if (!cs->high || !cs->n_alive) return SGP_OK;
-	{ int r = chars_upload(cs, true); if (r != SGP_OK) return r; }
-	{ int r = flush_event_reset(w); if (r != SGP_OK) return r; }      // (a push may wake a body: an activation event)
+	{ int r = cs->slots.empty() ? flush_cmds(w) : query_prelude(w); if (r != SGP_OK) return r; }      // (an empty batch applies the edits and leaves the grid alone)
+	if (cs->slots.empty()) return SGP_OK;
+	if (!cs->dv_valid || memcmp(&cs->dv[0], &w->dv, sizeof(DV)) != 0) { memcpy(&cs->dv[0], &w->dv, sizeof(DV)); cs->dv.dirty = cs->dv_valid = true; }
+	{ int r = cs->update_stage(); if (r != SGP_OK) return r; }
 	const CharBufs b = chars_bufs(cs);
-	launch_characters_update(cs->d_dv, b, dt, w->stream);
+	launch_characters_update(cs->dv.d(), b, dt, w->stream);
 	launch_characters_push(w->dv, b, w->stream);
-	// a push leaves a force on a body, and may have woken it, without the host hearing of it: the next step is not skipped as idle, and the event lists may hold something
-	w->dirty_since_step = true; w->events_on_device = true;
-	HIP_TRY(hipGetLastError());
-	return SGP_OK;
+	return cs->update_end();
 }
 
 SGP_API int sgp_characters_get_states(sgp_characters* cs, uint32_t first, uint32_t n, sgp_character_state* out)
 {
-	if (!batch_usable(cs) || (n && !out)) return fail(SGP_ERR_INVALID, "sgp_characters_get_states: NULL, or the batch's world is gone");
-	if ((uint64_t)first + n > cs->cap) return fail(SGP_ERR_INVALID, "sgp_characters_get_states: range beyond the batch's capacity");
-	if (!n) return SGP_OK;
-	sgp_world* w = cs->w;
-	hipSetDevice(w->device);
-	ray_server_stop(w);
-	if (cs->rec_dirty || cs->in_dirty) {
-		{ int r = chars_upload(cs, false); if (r != SGP_OK) return r; }
-		launch_characters_sync(chars_bufs(cs), w->stream);
-	}
-	{ int r = ensure_stage(w, sizeof(CharState) * n); if (r != SGP_OK) return r; }
-	HIP_TRY(hipMemcpyAsync(w->stage_host, cs->d_st + first, sizeof(CharState) * n, hipMemcpyDeviceToHost, w->stream));
-	HIP_TRY(hipStreamSynchronize(w->stream));
-	const CharState* hs = (const CharState*)w->stage_host;
+	const CharState* hs;
+	const int rc = batch_read_states(cs, "sgp_characters_get_states", &sgp_characters::d_st, first, n, out, &hs, [cs] {
+		if (!cs->rec.dirty && !cs->in.dirty) return (int)SGP_OK;
+		{ int r = cs->upload(); if (r != SGP_OK) return r; }      // (host edits pending and no update to carry them)
+		launch_characters_sync(chars_bufs(cs), cs->w->stream);
+		return (int)SGP_OK;
+	});
+	if (rc != SGP_OK || !hs) return rc;
+	const sgp_world* w = cs->w;
 	for (uint32_t i = 0; i < n; ++i) {
 		sgp_character_state& o = out[i];
 		memset(&o, 0, sizeof(o));
@@ -247,20 +197,20 @@ SGP_API int sgp_characters_drain_contacts(sgp_characters* cs, sgp_character_cont
 {
 	if (!batch_usable(cs) || (cap && !out) || !n_out) return fail(SGP_ERR_INVALID, "sgp_characters_drain_contacts: NULL, or the batch's world is gone");
 	*n_out = 0;
-	if (!cs->high) return SGP_OK;
+	if (!cs->slots.high) return SGP_OK;
 	sgp_world* w = cs->w;
 	hipSetDevice(w->device);
 	ray_server_stop(w);
-	const size_t cb = (sizeof(uint32_t) * cs->high + 15) & ~size_t(15);
-	{ int r = ensure_stage(w, cb + sizeof(CharAdded) * SGP_CHAR_MAX_ADDED * (size_t)cs->high); if (r != SGP_OK) return r; }
-	HIP_TRY(hipMemcpyAsync(w->stage_host, cs->d_n_added, sizeof(uint32_t) * cs->high, hipMemcpyDeviceToHost, w->stream));
+	const size_t cb = (sizeof(uint32_t) * cs->slots.high + 15) & ~size_t(15);
+	{ int r = ensure_stage(w, cb + sizeof(CharAdded) * SGP_CHAR_MAX_ADDED * (size_t)cs->slots.high); if (r != SGP_OK) return r; }
+	HIP_TRY(hipMemcpyAsync(w->stage_host, cs->d_n_added, sizeof(uint32_t) * cs->slots.high, hipMemcpyDeviceToHost, w->stream));
 	HIP_TRY(hipStreamSynchronize(w->stream));
 	const uint32_t* counts = (const uint32_t*)w->stage_host;
 	uint32_t last = 0, total = 0;
-	for (uint32_t k = 0; k < cs->high; ++k) if (counts[k]) { last = k + 1; total += std::min(counts[k], (uint32_t)SGP_CHAR_MAX_ADDED); }
+	for (uint32_t k = 0; k < cs->slots.high; ++k) if (counts[k]) { last = k + 1; total += std::min(counts[k], (uint32_t)SGP_CHAR_MAX_ADDED); }
 	if (!total) return SGP_OK;
 	HIP_TRY(hipMemcpyAsync((char*)w->stage_host + cb, cs->d_added, sizeof(CharAdded) * SGP_CHAR_MAX_ADDED * (size_t)last, hipMemcpyDeviceToHost, w->stream));
-	HIP_TRY(hipMemsetAsync(cs->d_n_added, 0, sizeof(uint32_t) * cs->high, w->stream));
+	HIP_TRY(hipMemsetAsync(cs->d_n_added, 0, sizeof(uint32_t) * cs->slots.high, w->stream));
 	HIP_TRY(hipStreamSynchronize(w->stream));
 	const CharAdded* recs = (const CharAdded*)((char*)w->stage_host + cb);
 	uint32_t m = 0;

@@ -8,8 +8,10 @@
 //   sgp_world_particles.hip  the batched point particles (sgp_particles_*)
 //   sgp_world_crafts.hip     the batched hover cars and boats (sgp_crafts_*)
 //   sgp_world_movers.hip     the batched path and move-to controllers (sgp_movers_*), sgp_path_prepare / sgp_path_advance
-//                            (what the two batches share -- owner, zeroed device arrays, the upload fence: WorldBatch, below)
+//                            (what the four batches share on the host -- owner, device arrays, uploaded mirrors, the skeletons of create, destroy, update
+//                            and get_states: WorldBatch, below; their slots and body links: sgp_batch_slots.h)
 //   sgp_stage_carve.h        the regions of one call in the stage buffer (host only, no HIP types)
+//   sgp_batch_slots.h        a batch's slot table and the bodies its slots are attached to (host only, no HIP types)
 //   sgp_world_tiles.hip      ghost import / export, the tile exchange over RCCL, re-tiling
 //   sgp_world_snapshots.hip  the network snapshot codec and the de-jitter queue (host only)
 //   sgp_world_checkpoint.hip capture, rollback, the checkpoint blob and restore
@@ -32,6 +34,7 @@
 #include "sgp_device_vehicle.h"
 #include "sgp_hull_build.h"
 #include "sgp_stage_carve.h"
+#include "sgp_batch_slots.h"
 
 #define SGP_API extern "C" __attribute__((visibility("default")))
 
@@ -236,44 +239,6 @@ inline uint32_t next_pow2(uint32_t v) { uint32_t p = 1; while (p < v) p <<= 1; r
 
 bool world_alive(uint64_t serial);      // (defined in sgp_world.hip)
 
-// What the device-resident batches of a world (sgp_characters, sgp_particles) share: who owns the batch; device arrays zeroed on the world's stream; a pinned
-// upload buffer with its fence -- `uploaded` is recorded behind the copy that reads the buffer and waited for before the buffer is written again, so that add,
-// update and clear never wait for the stream --; the destroy sequence.
-struct WorldBatch {
-	sgp_world* w = nullptr; uint64_t world_serial = 0; int device = 0;
-	std::vector<void*> dev;      // the device arrays of alloc(), freed by release()
-	char* h_up = nullptr; hipEvent_t uploaded = nullptr; bool upload_in_flight = false;
-
-	bool usable() const { return w && world_alive(world_serial); }
-	bool adopt(sgp_world* world)
-	{
-		w = world; world_serial = world->serial; device = world->device;
-		return hipEventCreateWithFlags(&uploaded, hipEventDisableTiming) == hipSuccess;
-	}
-	template <typename T> bool alloc(T*& p, size_t n)
-	{
-		const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-		if (hipMalloc((void**)&p, bytes) != hipSuccess) { p = nullptr; return false; }
-		dev.push_back(p);
-		return hipMemsetAsync(p, 0, bytes, w->stream) == hipSuccess;
-	}
-	bool pin(size_t bytes)      // a new upload buffer (the caller has seen to it that nothing reads the old one)
-	{
-		if (h_up) { hipHostFree(h_up); h_up = nullptr; }
-		return hipHostMalloc((void**)&h_up, bytes, hipHostMallocDefault) == hipSuccess;
-	}
-	int upload_begin() { if (upload_in_flight) { HIP_TRY(hipEventSynchronize(uploaded)); upload_in_flight = false; } return SGP_OK; }      // before h_up is written
-	int upload_end() { HIP_TRY(hipEventRecord(uploaded, w->stream)); upload_in_flight = true; return SGP_OK; }                              // behind the copies that read it
-	void release()
-	{
-		hipSetDevice(device);
-		if (usable()) hipStreamSynchronize(w->stream);      // (a destroyed world has waited for its stream already)
-		for (void* p : dev) hipFree(p);
-		if (h_up) hipHostFree(h_up);
-		if (uploaded) hipEventDestroy(uploaded);
-	}
-};
-static inline bool batch_usable(const WorldBatch* b) { return b && b->usable(); }
 // a tile's world: ghosts imported, or queued for import (the characters and the crafts refuse it)
 static inline bool world_holds_ghosts(const sgp_world* w) { return !w->ghost_map.empty() || !w->ghost_seq.empty() || !w->ghost_refresh.empty() || !w->rec_creates.empty(); }
 
@@ -338,3 +303,158 @@ int particles_append_device(sgp_particles* ps, const sgp_particle* d_recs, const
 // defined in sgp_world_bodies.hip
 int add_one(sgp_world* w, const sgp_body_desc* d, uint32_t* id_out, bool ghost);
 int book_record_body(sgp_world* w, uint32_t* flags_io, uint64_t userdata, float radius, float volume, bool ghost, uint32_t* id_out);      // (the host's share of add_one for a body created on the device from a record)
+
+// ---- the host side the device-resident batches of a world share (sgp_characters, sgp_particles, sgp_crafts, sgp_movers) ---------------------------------------
+static inline int fail_in(int code, const char* fn, const char* what) { char msg[256]; snprintf(msg, sizeof(msg), "%s: %s", fn, what); return fail(code, msg); }
+static inline int fail_ghosts(const char* fn, const char* whose)
+{
+	char msg[256]; snprintf(msg, sizeof(msg), "%s: the world holds ghost bodies (%s of tiled worlds are not supported)", fn, whose);
+	return fail(SGP_ERR_INVALID, msg);
+}
+// the bodies a batch attaches its slots to (BodyLinks): a live body of the given motion type that is no compound child, ghost or alias slot, and the birth number it has
+static inline bool body_carries(const sgp_world* w, uint32_t body, uint32_t motion)
+{
+	if (!live(w, body)) return false;
+	const HostBody& b = w->hb[body];
+	return (b.flags & BF_MOTION_MASK) == motion && !(b.flags & BF_ALIAS) && b.comp_root == SGP_INVALID_ID && !b.ghost;
+}
+static inline uint32_t body_born_of(const sgp_world* w, uint32_t body) { return body < w->body_born.size() ? w->body_born[body] : 0u; }
+
+// One array the host keeps and the device gets when it changed: the host's copy, the device's, where the copy is staged in WorldBatch::h_up, and whether the
+// two differ.  An upload moves the first *count units of `stride` bytes (the records up to the batch's high-water mark, the segments of the paths up to theirs).
+struct BatchMirror { const void* host = nullptr; void* dev = nullptr; size_t stride = 0, bytes = 0, off = 0; const uint32_t* count = nullptr; bool dirty = false; };
+template <class T> struct Mirror : BatchMirror {
+	std::vector<T> h;
+	void shape(size_t units, const uint32_t* count_, size_t per = 1)      // `units` zeroed units of `per` records each
+	{
+		h.resize(units * per); memset((void*)h.data(), 0, sizeof(T) * h.size());
+		host = h.data(); stride = sizeof(T) * per; bytes = stride * units; count = count_;
+	}
+	T* d() const { return (T*)dev; }
+	T& operator[](size_t i) { return h[i]; }
+	const T& operator[](size_t i) const { return h[i]; }
+};
+
+// Who owns the batch; device arrays zeroed on the world's stream; the uploaded mirrors and their pinned upload buffer with its fence -- `uploaded` is recorded
+// behind the copies that read the buffer and waited for before the buffer is written again, so that add, update and clear never wait for the stream --; the
+// two ends of an update; the release sequence.  (batch_created, batch_destroy, batch_update_admit and batch_read_states, below, are the rest of the skeletons.)
+struct WorldBatch {
+	sgp_world* w = nullptr; uint64_t world_serial = 0; int device = 0;
+	std::vector<void*> dev;      // the device arrays of alloc(), freed by release()
+	std::vector<BatchMirror*> mirrors;      // in the order they are uploaded
+	char* h_up = nullptr; hipEvent_t uploaded = nullptr; bool upload_in_flight = false;
+
+	bool usable() const { return w && world_alive(world_serial); }
+	bool adopt(sgp_world* world)
+	{
+		w = world; world_serial = world->serial; device = world->device;
+		return hipEventCreateWithFlags(&uploaded, hipEventDisableTiming) == hipSuccess;
+	}
+	bool alloc_bytes(void** p, size_t bytes)
+	{
+		if (hipMalloc(p, bytes) != hipSuccess) { *p = nullptr; return false; }
+		dev.push_back(*p);
+		return hipMemsetAsync(*p, 0, bytes, w->stream) == hipSuccess;
+	}
+	template <typename T> bool alloc(T*& p, size_t n) { return alloc_bytes((void**)&p, std::max<size_t>(n, 1) * sizeof(T)); }
+	bool pin(size_t bytes)      // a new upload buffer (the caller has seen to it that nothing reads the old one)
+	{
+		if (h_up) { hipHostFree(h_up); h_up = nullptr; }
+		return hipHostMalloc((void**)&h_up, bytes, hipHostMallocDefault) == hipSuccess;
+	}
+	// the mirrors of the batch (shaped already), in upload order: their device arrays, their regions of the upload buffer, the buffer
+	bool create_mirrors(std::initializer_list<BatchMirror*> list)
+	{
+		StageCarve up;
+		for (BatchMirror* m : list) {
+			m->off = up.add(m->bytes);
+			if (!alloc_bytes(&m->dev, std::max<size_t>(m->bytes, 1))) return false;
+			mirrors.push_back(m);
+		}
+		return pin(up.total);
+	}
+	int upload_begin() { if (upload_in_flight) { HIP_TRY(hipEventSynchronize(uploaded)); upload_in_flight = false; } return SGP_OK; }      // before h_up is written
+	int upload_end() { HIP_TRY(hipEventRecord(uploaded, w->stream)); upload_in_flight = true; return SGP_OK; }                              // behind the copies that read it
+	// what changed on the host -> the device, behind whatever the stream holds (no wait for the stream; only for the previous upload to have left the staging buffer)
+	int upload()
+	{
+		bool any = false;
+		for (const BatchMirror* m : mirrors) any = any || m->dirty;
+		if (!any) return SGP_OK;
+		{ int r = upload_begin(); if (r != SGP_OK) return r; }
+		for (const BatchMirror* m : mirrors) {
+			const size_t n = m->stride * *m->count;
+			if (!m->dirty || !n) continue;
+			memcpy(h_up + m->off, m->host, n);
+			HIP_TRY(hipMemcpyAsync(m->dev, h_up + m->off, n, hipMemcpyHostToDevice, w->stream));
+		}
+		for (BatchMirror* m : mirrors) m->dirty = false;
+		return upload_end();
+	}
+	// an update of characters, crafts or movers that has something to launch: the mirrors go up, and the event counters are emptied if the host has pulled the
+	// lists (a push, a force or a move may wake a body: an activation event) ...
+	int update_stage()
+	{
+		{ int r = upload(); if (r != SGP_OK) return r; }
+		return flush_event_reset(w);
+	}
+	// ... and behind its launches: the update has left forces or velocities on bodies, and may have woken them, without the host hearing of it -- the next step is
+	// not skipped as idle, and the event lists may hold something
+	int update_end()
+	{
+		w->dirty_since_step = true; w->events_on_device = true;
+		HIP_TRY(hipGetLastError());
+		return SGP_OK;
+	}
+	void release()
+	{
+		hipSetDevice(device);
+		if (usable()) hipStreamSynchronize(w->stream);      // (a destroyed world has waited for its stream already)
+		for (void* p : dev) hipFree(p);
+		if (h_up) hipHostFree(h_up);
+		if (uploaded) hipEventDestroy(uploaded);
+	}
+};
+static inline bool batch_usable(const WorldBatch* b) { return b && b->usable(); }
+
+// the end of every *_create (`ok`: adopt, the allocations and the pinning all succeeded) and the whole of every *_destroy
+template <class B> inline int batch_created(B* b, bool ok, B** out, const char* fn)
+{
+	if (!ok) { (void)hipGetLastError(); b->release(); delete b; return fail_in(SGP_ERR_HIP, fn, "allocation"); }
+	*out = b;
+	return SGP_OK;
+}
+template <class B> inline int batch_destroy(B* b, const char* fn)
+{
+	if (!b) return fail_in(SGP_ERR_INVALID, fn, "NULL");
+	b->release();
+	delete b;
+	return SGP_OK;
+}
+// what an update of characters, crafts or movers refuses (`whose`: "crafts"; `dt_rule`: what `dt_ok` asked of a finite dt -- "positive", "not negative")
+static inline int batch_update_admit(const WorldBatch* b, const char* fn, const char* whose, bool dt_ok, const char* dt_rule)
+{
+	if (!batch_usable(b)) return fail_in(SGP_ERR_INVALID, fn, "NULL, or the batch's world is gone");
+	if (!dt_ok) { char msg[256]; snprintf(msg, sizeof(msg), "%s: dt must be finite and %s", fn, dt_rule); return fail(SGP_ERR_INVALID, msg); }
+	if (world_holds_ghosts(b->w)) return fail_ghosts(fn, whose);
+	return SGP_OK;
+}
+// The opening of every *_get_states: the argument checks, the resident ray server told to leave, `before_copy()` (what the batch has to bring up to date on the
+// device first), then `n` records of the device's states from `first` on copied to the stage buffer and waited for.  *staged: the records, or NULL where n == 0
+// (nothing to fill).  The fill loop is the batch's own.
+template <class B, class S, class F> inline int batch_read_states(B* b, const char* fn, S* B::* d_st, uint32_t first, uint32_t n, const void* out, const S** staged, F&& before_copy)
+{
+	*staged = nullptr;
+	if (!batch_usable(b) || (n && !out)) return fail_in(SGP_ERR_INVALID, fn, "NULL, or the batch's world is gone");
+	if ((uint64_t)first + n > b->slots.cap) return fail_in(SGP_ERR_INVALID, fn, "range beyond the batch's capacity");
+	if (!n) return SGP_OK;
+	sgp_world* w = b->w;
+	hipSetDevice(w->device);
+	ray_server_stop(w);
+	{ int r = before_copy(); if (r != SGP_OK) return r; }
+	{ int r = ensure_stage(w, sizeof(S) * (size_t)n); if (r != SGP_OK) return r; }
+	HIP_TRY(hipMemcpyAsync(w->stage_host, b->*d_st + first, sizeof(S) * (size_t)n, hipMemcpyDeviceToHost, w->stream));
+	HIP_TRY(hipStreamSynchronize(w->stream));
+	*staged = (const S*)w->stage_host;
+	return SGP_OK;
+}

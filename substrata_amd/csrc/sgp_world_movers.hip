@@ -7,20 +7,18 @@
 
 struct MoverPath { uint32_t n = 0, refs = 0; bool alive = false; double total_time = 0.0; };
 struct sgp_movers : WorldBatch {
-	uint32_t cap = 0, high = 0, n_alive = 0, n_followers = 0, path_cap = 0, path_high = 0;
-	std::vector<MoverRec> rec; std::vector<uint32_t> born, leader_serial; std::vector<uint64_t> tag; std::vector<uint8_t> fresh; std::vector<uint32_t> free_list;
-	std::vector<MoverPath> paths; std::vector<sgp_path_segment> segs; std::vector<uint32_t> path_n; std::vector<uint32_t> path_free;
-	std::unordered_map<uint32_t, uint32_t> mover_of_body;      // body -> the live mover on it (a body carries one mover)
-	bool rec_dirty = false, path_dirty = false;
+	BatchSlots slots, path_slots; BodyLinks links;      // (a body carries one mover)
+	uint32_t n_followers = 0;
+	Mirror<MoverRec> rec; std::vector<uint32_t> leader_serial; std::vector<uint64_t> tag; std::vector<uint8_t> fresh;
+	std::vector<MoverPath> paths; Mirror<sgp_path_segment> segs; Mirror<uint32_t> path_n;      // (segs and path_n change together)
 	// device
-	MoverRec* d_rec = nullptr; MoverDyn* d_dyn = nullptr; sgp_mover_state* d_st = nullptr; uint2* d_pub = nullptr; sgp_path_segment* d_segs = nullptr; uint32_t* d_path_n = nullptr;
-	size_t up_rec = 0, up_segs = 0, up_path_n = 0;      // the pinned staging of the uploads (WorldBatch::h_up)
+	MoverDyn* d_dyn = nullptr; sgp_mover_state* d_st = nullptr; uint2* d_pub = nullptr;
 };
 
 static MoverBufs movers_bufs(const sgp_movers* ms)
 {
 	MoverBufs b;
-	b.rec = ms->d_rec; b.dyn = ms->d_dyn; b.st = ms->d_st; b.pub = ms->d_pub; b.segs = ms->d_segs; b.path_n = ms->d_path_n; b.n = ms->high; b.n_paths = ms->path_high;
+	b.rec = ms->rec.d(); b.dyn = ms->d_dyn; b.st = ms->d_st; b.pub = ms->d_pub; b.segs = ms->segs.d(); b.path_n = ms->path_n.d(); b.n = ms->slots.high; b.n_paths = ms->path_slots.high;
 	return b;
 }
 
@@ -41,37 +39,24 @@ SGP_API int sgp_path_advance(const sgp_path_segment* segs, uint32_t n, sgp_path_
 	return SGP_OK;
 }
 
-SGP_API int sgp_movers_destroy(sgp_movers* ms)
-{
-	if (!ms) return fail(SGP_ERR_INVALID, "sgp_movers_destroy: NULL");
-	ms->release();
-	delete ms;
-	return SGP_OK;
-}
+SGP_API int sgp_movers_destroy(sgp_movers* ms) { return batch_destroy(ms, "sgp_movers_destroy"); }
 
 SGP_API int sgp_movers_create(sgp_world* w, uint32_t capacity, uint32_t path_capacity, sgp_movers** out)
 {
 	if (!w || !out || capacity == 0 || capacity > SGP_MOVERS_MAX_CAPACITY || path_capacity == 0 || path_capacity > SGP_MOVERS_MAX_PATHS) return fail(SGP_ERR_INVALID, "sgp_movers_create: NULL world or out, a capacity of 0 or beyond 2^16, or a path capacity of 0 or beyond 2^12");
-	if (world_holds_ghosts(w)) return fail(SGP_ERR_INVALID, "sgp_movers_create: the world holds ghost bodies (movers of tiled worlds are not supported)");
+	if (world_holds_ghosts(w)) return fail_ghosts("sgp_movers_create", "movers");
 	hipSetDevice(w->device);
 	sgp_movers* ms = new sgp_movers();
-	ms->cap = capacity; ms->path_cap = path_capacity;
-	const size_t n = capacity, ns = (size_t)path_capacity * SGP_MOVER_MAX_WAYPOINTS;
-	ms->rec.resize(n); ms->born.assign(n, 0u); ms->leader_serial.assign(n, 0u); ms->tag.assign(n, 0ull); ms->fresh.assign(n, 0);
-	memset(ms->rec.data(), 0, sizeof(MoverRec) * n);
-	ms->paths.resize(path_capacity); ms->segs.resize(ns); ms->path_n.assign(path_capacity, 0u);
-	memset(ms->segs.data(), 0, sizeof(sgp_path_segment) * ns);
-	StageCarve up;
-	ms->up_rec = up.add(sizeof(MoverRec) * n); ms->up_segs = up.add(sizeof(sgp_path_segment) * ns); ms->up_path_n = up.add(sizeof(uint32_t) * path_capacity);
-	bool ok = ms->adopt(w);
-	ok = ok && ms->alloc(ms->d_rec, n) && ms->alloc(ms->d_dyn, n) && ms->alloc(ms->d_st, n) && ms->alloc(ms->d_pub, n) && ms->alloc(ms->d_segs, ns) && ms->alloc(ms->d_path_n, path_capacity);
-	ok = ok && ms->pin(up.total);
-	if (!ok) { (void)hipGetLastError(); sgp_movers_destroy(ms); return fail(SGP_ERR_HIP, "sgp_movers_create: allocation"); }
-	*out = ms;
-	return SGP_OK;
+	const size_t n = capacity;
+	ms->slots.cap = capacity; ms->path_slots.cap = path_capacity; ms->links.resize(capacity);
+	ms->leader_serial.assign(n, 0u); ms->tag.assign(n, 0ull); ms->fresh.assign(n, 0); ms->paths.resize(path_capacity);
+	ms->segs.shape(path_capacity, &ms->path_slots.high, SGP_MOVER_MAX_WAYPOINTS); ms->path_n.shape(path_capacity, &ms->path_slots.high); ms->rec.shape(n, &ms->slots.high);
+	bool ok = ms->adopt(w) && ms->create_mirrors({ &ms->segs, &ms->path_n, &ms->rec });      // (the paths go up before the records that name them)
+	ok = ok && ms->alloc(ms->d_dyn, n) && ms->alloc(ms->d_st, n) && ms->alloc(ms->d_pub, n);
+	return batch_created(ms, ok, out, "sgp_movers_create");
 }
 
-static bool path_live(const sgp_movers* ms, uint32_t p) { return p < ms->path_high && ms->paths[p].alive; }
+static bool path_live(const sgp_movers* ms, uint32_t p) { return p < ms->path_slots.high && ms->paths[p].alive; }
 
 SGP_API int sgp_movers_path_add(sgp_movers* ms, const sgp_path_waypoint* waypoints, uint32_t n, uint32_t* path_id_out)
 {
@@ -80,14 +65,12 @@ SGP_API int sgp_movers_path_add(sgp_movers* ms, const sgp_path_waypoint* waypoin
 	double total = 0.0;
 	if (sgp_path_prepare(waypoints, n, prepared, &total) != SGP_OK) return SGP_ERR_INVALID;      // (the message is sgp_path_prepare's)
 	if (!(total > 0.0) || !std::isfinite(total)) return fail(SGP_ERR_INVALID, "sgp_movers_path_add: the path's traversal time is not finite and > 0");
-	uint32_t p;
-	if (!ms->path_free.empty()) { p = ms->path_free.back(); ms->path_free.pop_back(); }
-	else if (ms->path_high < ms->path_cap) p = ms->path_high++;
-	else return fail(SGP_ERR_CAPACITY, "sgp_movers_path_add: no free path slot");
+	const uint32_t p = ms->path_slots.take();
+	if (p == BatchSlots::none) return fail(SGP_ERR_CAPACITY, "sgp_movers_path_add: no free path slot");
 	memcpy(&ms->segs[(size_t)p * SGP_MOVER_MAX_WAYPOINTS], prepared, sizeof(sgp_path_segment) * n);
 	ms->path_n[p] = n;
 	MoverPath& mp = ms->paths[p]; mp.n = n; mp.refs = 0; mp.alive = true; mp.total_time = total;
-	ms->path_dirty = true;
+	ms->segs.dirty = ms->path_n.dirty = true;
 	*path_id_out = p;
 	return SGP_OK;
 }
@@ -96,8 +79,8 @@ SGP_API int sgp_movers_path_remove(sgp_movers* ms, uint32_t p)
 {
 	if (!batch_usable(ms) || !path_live(ms, p)) return fail(SGP_ERR_INVALID, "sgp_movers_path_remove: no such path");
 	if (ms->paths[p].refs) return fail(SGP_ERR_INVALID, "sgp_movers_path_remove: the path is in use");
-	ms->paths[p].alive = false; ms->path_n[p] = 0u; ms->path_free.push_back(p);
-	ms->path_dirty = true;
+	ms->paths[p].alive = false; ms->path_n[p] = 0u; ms->path_slots.give_back(p);
+	ms->segs.dirty = ms->path_n.dirty = true;
 	return SGP_OK;
 }
 
@@ -109,35 +92,22 @@ SGP_API int sgp_movers_path_get(sgp_movers* ms, uint32_t p, sgp_path_segment* ou
 	return SGP_OK;
 }
 
-static bool mover_live(const sgp_movers* ms, uint32_t id) { return id < ms->high && ms->rec[id].alive; }
+static bool mover_live(const sgp_movers* ms, uint32_t id) { return id < ms->slots.high && ms->rec[id].alive; }
 static bool is_follower(const MoverRec& r) { return r.kind == SGP_MOVER_PATH && r.leader != SGP_INVALID_ID; }
-static bool body_carries_mover(const sgp_world* w, uint32_t body)
-{
-	if (!live(w, body)) return false;
-	const HostBody& b = w->hb[body];
-	return (b.flags & BF_MOTION_MASK) == SGP_MOTION_KINEMATIC && !(b.flags & BF_ALIAS) && b.comp_root == SGP_INVALID_ID && !b.ghost;
-}
-static uint32_t mover_born_of(const sgp_world* w, uint32_t body) { return body < w->body_born.size() ? w->body_born[body] : 0u; }
 // the bodies that have gone since the last look (the host hands out the slots, so it knows): their movers are marked, the body is free for another mover, and the
 // followers of a walker that lost its body lose their leader
 static void movers_mark_gone(sgp_movers* ms)
 {
 	const sgp_world* w = ms->w;
-	for (uint32_t k = 0; k < ms->high; ++k) {
-		MoverRec& r = ms->rec[k];
-		if (!r.alive || r.gone) continue;
-		if (body_carries_mover(w, r.body) && mover_born_of(w, r.body) == ms->born[k]) continue;
-		r.gone = 1u; ms->rec_dirty = true;
-		const auto it = ms->mover_of_body.find(r.body);
-		if (it != ms->mover_of_body.end() && it->second == k) ms->mover_of_body.erase(it);
-	}
+	ms->links.mark_gone(ms->slots.high, [w](uint32_t body) { return body_carries(w, body, SGP_MOTION_KINEMATIC); }, [w](uint32_t body) { return body_born_of(w, body); },
+	                    [ms](uint32_t k) { ms->rec[k].gone = 1u; ms->rec.dirty = true; });
 	if (!ms->n_followers) return;
-	for (uint32_t k = 0; k < ms->high; ++k) {
+	for (uint32_t k = 0; k < ms->slots.high; ++k) {
 		MoverRec& r = ms->rec[k];
 		if (!r.alive || !is_follower(r) || r.leader_gone) continue;
 		const MoverRec& l = ms->rec[r.leader];
 		if (l.alive && !l.gone && l.reset_serial == ms->leader_serial[k]) continue;
-		r.leader_gone = 1u; ms->rec_dirty = true;
+		r.leader_gone = 1u; ms->rec.dirty = true;
 	}
 }
 
@@ -160,13 +130,11 @@ SGP_API int sgp_mover_add(sgp_movers* ms, const sgp_mover_desc* desc, uint32_t* 
 	if (!batch_usable(ms) || !desc || !id_out) return fail(SGP_ERR_INVALID, "sgp_mover_add: NULL, or the batch's world is gone");
 	if (const char* what = mover_desc_fault(ms, *desc)) { char msg[160]; snprintf(msg, sizeof(msg), "sgp_mover_add: %s", what); return fail(SGP_ERR_INVALID, msg); }
 	sgp_world* w = ms->w;
-	if (!body_carries_mover(w, desc->body)) return fail(SGP_ERR_INVALID, "sgp_mover_add: the body is not a live kinematic body (no compound, ghost or alias slot)");
+	if (!body_carries(w, desc->body, SGP_MOTION_KINEMATIC)) return fail(SGP_ERR_INVALID, "sgp_mover_add: the body is not a live kinematic body (no compound, ghost or alias slot)");
 	movers_mark_gone(ms);
-	if (ms->mover_of_body.count(desc->body)) return fail(SGP_ERR_INVALID, "sgp_mover_add: the body already carries a mover of this batch");
-	uint32_t id;
-	if (!ms->free_list.empty()) { id = ms->free_list.back(); ms->free_list.pop_back(); }
-	else if (ms->high < ms->cap) id = ms->high++;
-	else return fail(SGP_ERR_CAPACITY, "sgp_mover_add: the batch is full");
+	if (ms->links.carried(desc->body)) return fail(SGP_ERR_INVALID, "sgp_mover_add: the body already carries a mover of this batch");
+	const uint32_t id = ms->slots.take();
+	if (id == BatchSlots::none) return fail(SGP_ERR_CAPACITY, "sgp_mover_add: the batch is full");
 	MoverRec& r = ms->rec[id];
 	const uint32_t reset = r.reset_serial + 1u;
 	memset(&r, 0, sizeof(r));
@@ -188,10 +156,8 @@ SGP_API int sgp_mover_add(sgp_movers* ms, const sgp_mover_desc* desc, uint32_t* 
 			r.follow_dist = desc->follow_dist; ms->leader_serial[id] = ms->rec[desc->leader].reset_serial; ms->n_followers++;
 		}
 	} else { memcpy(r.hold_pos, desc->hold_pos, 12); memcpy(r.hold_rot, desc->hold_rot, 16); }
-	ms->born[id] = mover_born_of(w, desc->body); ms->tag[id] = desc->tag; ms->fresh[id] = 1;
-	ms->mover_of_body[desc->body] = id;
-	ms->rec_dirty = true;
-	ms->n_alive++;
+	ms->links.attach(id, desc->body, body_born_of(w, desc->body)); ms->tag[id] = desc->tag; ms->fresh[id] = 1;
+	ms->rec.dirty = true;
 	*id_out = id;
 	return SGP_OK;
 }
@@ -200,12 +166,11 @@ SGP_API int sgp_mover_remove(sgp_movers* ms, uint32_t id)
 {
 	if (!batch_usable(ms) || !mover_live(ms, id)) return fail(SGP_ERR_INVALID, "sgp_mover_remove: no such mover");
 	MoverRec& r = ms->rec[id];
-	const auto it = ms->mover_of_body.find(r.body);
-	if (it != ms->mover_of_body.end() && it->second == id) ms->mover_of_body.erase(it);
+	ms->links.detach(id);
 	if (r.kind == SGP_MOVER_PATH) { ms->paths[r.path].refs--; if (is_follower(r)) ms->n_followers--; }
-	r.alive = 0u; ms->rec_dirty = true;
-	ms->free_list.push_back(id); ms->n_alive--;
-	if (ms->n_followers) for (uint32_t k = 0; k < ms->high; ++k) if (ms->rec[k].alive && is_follower(ms->rec[k]) && ms->rec[k].leader == id) ms->rec[k].leader_gone = 1u;
+	r.alive = 0u; ms->rec.dirty = true;
+	ms->slots.give_back(id);
+	if (ms->n_followers) for (uint32_t k = 0; k < ms->slots.high; ++k) if (ms->rec[k].alive && is_follower(ms->rec[k]) && ms->rec[k].leader == id) ms->rec[k].leader_gone = 1u;
 	return SGP_OK;
 }
 
@@ -222,7 +187,7 @@ static int set_track(sgp_movers* ms, uint32_t id, const float* start, const floa
 	// ObjectMoveToController.cpp:36-55
 	if (rotation) { memcpy(r.rot_start, start, 16); memcpy(r.rot_target, target, 16); r.rot_duration = std::max(duration, 1.0e-4f); r.rot_easing = easing; r.rot_elapsed = std::max(cur_elapsed, 0.0f); r.rot_serial++; }
 	else { memcpy(r.pos_start, start, 12); memcpy(r.pos_target, target, 12); r.pos_duration = std::max(duration, 1.0e-4f); r.pos_easing = easing; r.pos_elapsed = std::max(cur_elapsed, 0.0f); r.pos_serial++; }
-	ms->rec_dirty = true;
+	ms->rec.dirty = true;
 	return SGP_OK;
 }
 SGP_API int sgp_movers_set_position_track(sgp_movers* ms, uint32_t id, const float start[3], const float target[3], float duration, uint32_t easing, float cur_elapsed)
@@ -234,61 +199,27 @@ SGP_API int sgp_movers_set_rotation_track(sgp_movers* ms, uint32_t id, const flo
 	return set_track(ms, id, start, target, duration, easing, cur_elapsed, true, "sgp_movers_set_rotation_track");
 }
 
-// what changed on the host -> the device, behind whatever the stream holds (no wait for the stream; only for the previous upload to have left the staging buffer)
-static int movers_upload(sgp_movers* ms)
-{
-	sgp_world* w = ms->w;
-	if (!ms->rec_dirty && !ms->path_dirty) return SGP_OK;
-	{ int r = ms->upload_begin(); if (r != SGP_OK) return r; }
-	if (ms->path_dirty && ms->path_high) {
-		const size_t ns = (size_t)ms->path_high * SGP_MOVER_MAX_WAYPOINTS;
-		memcpy(ms->h_up + ms->up_segs, ms->segs.data(), sizeof(sgp_path_segment) * ns);
-		memcpy(ms->h_up + ms->up_path_n, ms->path_n.data(), sizeof(uint32_t) * ms->path_high);
-		HIP_TRY(hipMemcpyAsync(ms->d_segs, ms->h_up + ms->up_segs, sizeof(sgp_path_segment) * ns, hipMemcpyHostToDevice, w->stream));
-		HIP_TRY(hipMemcpyAsync(ms->d_path_n, ms->h_up + ms->up_path_n, sizeof(uint32_t) * ms->path_high, hipMemcpyHostToDevice, w->stream));
-	}
-	if (ms->rec_dirty && ms->high) {
-		memcpy(ms->h_up + ms->up_rec, ms->rec.data(), sizeof(MoverRec) * ms->high);
-		HIP_TRY(hipMemcpyAsync(ms->d_rec, ms->h_up + ms->up_rec, sizeof(MoverRec) * ms->high, hipMemcpyHostToDevice, w->stream));
-	}
-	ms->rec_dirty = ms->path_dirty = false;
-	return ms->upload_end();
-}
-
 SGP_API int sgp_movers_update(sgp_movers* ms, float dt)
 {
-	if (!batch_usable(ms)) return fail(SGP_ERR_INVALID, "sgp_movers_update: NULL, or the batch's world is gone");
-	if (!std::isfinite(dt) || !(dt >= 0.0f)) return fail(SGP_ERR_INVALID, "sgp_movers_update: dt must be finite and not negative");
+	{ int r = batch_update_admit(ms, "sgp_movers_update", "movers", std::isfinite(dt) && dt >= 0.0f, "not negative"); if (r != SGP_OK) return r; }
 	sgp_world* w = ms->w;
-	if (world_holds_ghosts(w)) return fail(SGP_ERR_INVALID, "sgp_movers_update: the world holds ghost bodies (movers of tiled worlds are not supported)");
 	if (dt == 0.0f) return SGP_OK;      // (the reference would move nothing and leave its target unset)
 	{ int r = query_prelude(w); if (r != SGP_OK) return r; }
-	if (!ms->high || !ms->n_alive) return SGP_OK;
+	if (ms->slots.empty()) return SGP_OK;
 	movers_mark_gone(ms);
-	{ int r = movers_upload(ms); if (r != SGP_OK) return r; }
-	{ int r = flush_event_reset(w); if (r != SGP_OK) return r; }      // (a moved body is activated: an activation event)
+	{ int r = ms->update_stage(); if (r != SGP_OK) return r; }
 	const MoverBufs b = movers_bufs(ms);
 	launch_movers_update(w->dv, b, dt, w->stream);
 	if (ms->n_followers) launch_movers_follow(w->dv, b, dt, w->stream);
-	std::fill(ms->fresh.begin(), ms->fresh.begin() + ms->high, (uint8_t)0);
-	// an update leaves velocities on bodies, and may have woken them, without the host hearing of it: the next step is not skipped as idle, and the event lists may hold something
-	w->dirty_since_step = true; w->events_on_device = true;
-	HIP_TRY(hipGetLastError());
-	return SGP_OK;
+	std::fill(ms->fresh.begin(), ms->fresh.begin() + ms->slots.high, (uint8_t)0);
+	return ms->update_end();
 }
 
 SGP_API int sgp_movers_get_states(sgp_movers* ms, uint32_t first, uint32_t n, sgp_mover_state* out)
 {
-	if (!batch_usable(ms) || (n && !out)) return fail(SGP_ERR_INVALID, "sgp_movers_get_states: NULL, or the batch's world is gone");
-	if ((uint64_t)first + n > ms->cap) return fail(SGP_ERR_INVALID, "sgp_movers_get_states: range beyond the batch's capacity");
-	if (!n) return SGP_OK;
-	sgp_world* w = ms->w;
-	hipSetDevice(w->device);
-	ray_server_stop(w);
-	{ int r = ensure_stage(w, sizeof(sgp_mover_state) * (size_t)n); if (r != SGP_OK) return r; }
-	HIP_TRY(hipMemcpyAsync(w->stage_host, ms->d_st + first, sizeof(sgp_mover_state) * (size_t)n, hipMemcpyDeviceToHost, w->stream));
-	HIP_TRY(hipStreamSynchronize(w->stream));
-	const sgp_mover_state* hs = (const sgp_mover_state*)w->stage_host;
+	const sgp_mover_state* hs;
+	const int rc = batch_read_states(ms, "sgp_movers_get_states", &sgp_movers::d_st, first, n, out, &hs, [] { return (int)SGP_OK; });      // (nothing to bring up to date: see `fresh`)
+	if (rc != SGP_OK || !hs) return rc;
 	for (uint32_t i = 0; i < n; ++i) {
 		const uint32_t k = first + i;
 		if (mover_live(ms, k) && !ms->fresh[k]) { out[i] = hs[i]; continue; }

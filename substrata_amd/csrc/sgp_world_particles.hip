@@ -13,6 +13,7 @@ struct sgp_particles : WorldBatch {
 	PsState* h_st = nullptr;      // pinned
 	// the device copy of the newcomers' pinned staging (WorldBatch::h_up): up_cap records each, both grown by add
 	sgp_particle* d_up = nullptr; uint32_t up_cap = 0;
+	~sgp_particles() { if (d_up) hipFree(d_up); if (h_st) hipHostFree(h_st); }      // (behind WorldBatch::release, which has waited for the stream)
 };
 
 SGP_API void sgp_default_particle(sgp_particle* p)
@@ -23,15 +24,7 @@ SGP_API void sgp_default_particle(sgp_particle* p)
 	p->restitution = 0.5f; p->width = 1.0f; p->dwidth_dt = 0.5f; p->opacity = 1.0f; p->dopacity_dt = -0.3f; p->mass = 1.0e-6f; p->area = 1.0e-6f;
 }
 
-SGP_API int sgp_particles_destroy(sgp_particles* ps)
-{
-	if (!ps) return fail(SGP_ERR_INVALID, "sgp_particles_destroy: NULL");
-	ps->release();
-	if (ps->d_up) hipFree(ps->d_up);
-	if (ps->h_st) hipHostFree(ps->h_st);
-	delete ps;
-	return SGP_OK;
-}
+SGP_API int sgp_particles_destroy(sgp_particles* ps) { return batch_destroy(ps, "sgp_particles_destroy"); }
 
 SGP_API int sgp_particles_create(sgp_world* w, uint32_t capacity, uint32_t event_capacity, sgp_particles** out)
 {
@@ -47,9 +40,7 @@ SGP_API int sgp_particles_create(sgp_world* w, uint32_t capacity, uint32_t event
 	        && ps->alloc(ps->b.evw, n) && ps->alloc(ps->b.wg_counts, blocks) && ps->alloc(ps->b.wg_off, blocks) && ps->alloc(ps->b.st, 1)
 	        && ps->alloc(ps->b.events, event_capacity);
 	ok = ok && hipHostMalloc((void**)&ps->h_st, sizeof(PsState), hipHostMallocDefault) == hipSuccess;
-	if (!ok) { (void)hipGetLastError(); sgp_particles_destroy(ps); return fail(SGP_ERR_HIP, "sgp_particles_create: allocation"); }
-	*out = ps;
-	return SGP_OK;
+	return batch_created(ps, ok, out, "sgp_particles_create");
 }
 
 static const char* particle_fault(const sgp_particle& p)

@@ -25,11 +25,48 @@ def _f4(v):
     return np.ascontiguousarray(v, dtype=np.float32).reshape(4)
 
 
-class Checkpoint:
-    """A captured world state (sgp_checkpoint): owns device and host memory, belongs to the world that made it."""
+class _Owned:
+    """A handle of the C ABI that belongs to a world and is destroyed by sgp_<_stem>_destroy: close() is idempotent, and runs when the object goes."""
+    _stem = None
 
     def __init__(self, world, handle):
         self._w, self._h = world, handle
+
+    def close(self):
+        if self._h:
+            self._w._fn(self._stem + "_destroy")(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _Batch(_Owned):
+    """A device-resident batch of one world: sgp_<_stem>_create with the capacities, update(); states() where the batch has a _state_dtype."""
+    _state_dtype = None
+
+    def __init__(self, world, *capacities):
+        super().__init__(world, C.c_void_p())
+        world._check(world._fn(self._stem + "_create")(world._h, *[int(c) for c in capacities], C.byref(self._h)), self._stem + "_create")
+        self.capacity = int(capacities[0])
+        self._update = world._fn(self._stem + "_update")
+
+    def update(self, dt=1.0 / 60.0):
+        self._w._check(self._update(self._h, float(dt)), self._stem + "_update")
+
+    def states(self, first=0, n=None):
+        n = self.capacity - first if n is None else int(n)
+        out = np.zeros(n, dtype=self._state_dtype)
+        self._w._check(self._w._fn(self._stem + "_get_states")(self._h, int(first), n, out.ctypes.data), self._stem + "_get_states")
+        return out
+
+
+class Checkpoint(_Owned):
+    """A captured world state (sgp_checkpoint): owns device and host memory, belongs to the world that made it."""
+    _stem = "checkpoint"
 
     def info(self):
         i = abi.CheckpointInfo()
@@ -44,25 +81,13 @@ class Checkpoint:
         self._w._check(self._w._fn("checkpoint_write")(self._h, buf.ctypes.data, buf.nbytes, C.byref(n)), "checkpoint_write")
         return buf.tobytes()
 
-    def close(self):
-        if self._h:
-            self._w._fn("checkpoint_destroy")(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Characters:
+class Characters(_Batch):
     """A batch of virtual characters of one world (sgp_characters): numpy in, numpy out.  update() enqueues and returns; states() waits."""
+    _stem, _state_dtype = "characters", abi.character_state_dtype
 
     def __init__(self, world, capacity):
-        self._w, self._h = world, C.c_void_p()
-        world._check(world._fn("characters_create")(world._h, int(capacity), C.byref(self._h)), "characters_create")
-        self.capacity = int(capacity)
+        super().__init__(world, capacity)
 
     def default_desc(self):
         d = abi.CharacterDesc()
@@ -90,40 +115,19 @@ class Characters:
         inputs = np.ascontiguousarray(inputs, dtype=abi.character_input_dtype).reshape(-1)
         self._w._check(self._w._fn("characters_set_inputs")(self._h, int(first), len(inputs), inputs.ctypes.data), "characters_set_inputs")
 
-    def update(self, dt=1.0 / 60.0):
-        self._w._check(self._w._fn("characters_update")(self._h, float(dt)), "characters_update")
-
-    def states(self, first=0, n=None):
-        n = self.capacity - first if n is None else int(n)
-        out = np.zeros(n, dtype=abi.character_state_dtype)
-        self._w._check(self._w._fn("characters_get_states")(self._h, int(first), n, out.ctypes.data), "characters_get_states")
-        return out
-
     def drain_contacts(self, cap=4096):
         out = np.zeros(cap, dtype=abi.character_contact_dtype)
         n = C.c_uint32(0)
         self._w._check(self._w._fn("characters_drain_contacts")(self._h, out.ctypes.data, cap, C.byref(n)), "characters_drain_contacts")
         return out[:min(n.value, cap)].copy()
 
-    def close(self):
-        if self._h:
-            self._w._fn("characters_destroy")(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Movers:
+class Movers(_Batch):
     """A batch of path and move-to controllers of one world (sgp_movers): update() enqueues and returns; states() waits."""
+    _stem, _state_dtype = "movers", abi.mover_state_dtype
 
     def __init__(self, world, capacity, path_capacity):
-        self._w, self._h = world, C.c_void_p()
-        world._check(world._fn("movers_create")(world._h, int(capacity), int(path_capacity), C.byref(self._h)), "movers_create")
-        self.capacity = int(capacity)
+        super().__init__(world, capacity, path_capacity)
 
     def add_path(self, waypoints):
         """waypoints: array of abi.path_waypoint_dtype (pos, type, pause_time, speed); returns the path id."""
@@ -171,34 +175,13 @@ class Movers:
         a, b = (C.c_float * 4)(*[float(x) for x in start]), (C.c_float * 4)(*[float(x) for x in target])
         self._w._check(self._w._fn("movers_set_rotation_track")(self._h, int(i), a, b, float(duration), int(easing), float(cur_elapsed)), "movers_set_rotation_track")
 
-    def update(self, dt=1.0 / 60.0):
-        self._w._check(self._w._fn("movers_update")(self._h, float(dt)), "movers_update")
 
-    def states(self, first=0, n=None):
-        n = self.capacity - first if n is None else int(n)
-        out = np.zeros(n, dtype=abi.mover_state_dtype)
-        self._w._check(self._w._fn("movers_get_states")(self._h, int(first), n, out.ctypes.data), "movers_get_states")
-        return out
-
-    def close(self):
-        if self._h:
-            self._w._fn("movers_destroy")(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Crafts:
+class Crafts(_Batch):
     """A batch of hover cars and boats of one world (sgp_crafts): update() enqueues and returns; states() waits."""
+    _stem, _state_dtype = "crafts", abi.craft_state_dtype
 
     def __init__(self, world, capacity):
-        self._w, self._h = world, C.c_void_p()
-        world._check(world._fn("crafts_create")(world._h, int(capacity), C.byref(self._h)), "crafts_create")
-        self.capacity = int(capacity)
+        super().__init__(world, capacity)
 
     def default_desc(self, kind, body=None):
         d = abi.CraftDesc()
@@ -229,35 +212,15 @@ class Crafts:
         self._w._check(self._w._fn("crafts_attach_particles")(self._h, particles._h if particles is not None else None), "crafts_attach_particles")
         self._particles = particles      # (kept alive while attached)
 
-    def update(self, dt=1.0 / 60.0):
-        self._w._check(self._w._fn("crafts_update")(self._h, float(dt)), "crafts_update")
 
-    def states(self, first=0, n=None):
-        n = self.capacity - first if n is None else int(n)
-        out = np.zeros(n, dtype=abi.craft_state_dtype)
-        self._w._check(self._w._fn("crafts_get_states")(self._h, int(first), n, out.ctypes.data), "crafts_get_states")
-        return out
-
-    def close(self):
-        if self._h:
-            self._w._fn("crafts_destroy")(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Particles:
+class Particles(_Batch):
     """A batch of point particles of one world (sgp_particles): numpy in, numpy out.  add(), update() and clear() enqueue and return; read() and
-    drain_events() wait."""
+    drain_events() wait.  (No states(): read() returns the live particles.)"""
+    _stem = "particles"
 
     def __init__(self, world, capacity, event_capacity=4096):
-        self._w, self._h = world, C.c_void_p()
-        world._check(world._fn("particles_create")(world._h, int(capacity), int(event_capacity), C.byref(self._h)), "particles_create")
-        self.capacity, self.event_capacity = int(capacity), int(event_capacity)
+        super().__init__(world, capacity, event_capacity)
+        self.event_capacity = int(event_capacity)
 
     def defaults(self, n=1):
         """n records of abi.particle_dtype filled by sgp_default_particle (the defaults of the reference's Particle())."""
@@ -270,9 +233,6 @@ class Particles:
     def add(self, particles):
         particles = np.ascontiguousarray(particles, dtype=abi.particle_dtype).reshape(-1)
         self._w._check(self._w._fn("particles_add")(self._h, particles.ctypes.data, len(particles)), "particles_add")
-
-    def update(self, dt=1.0 / 60.0):
-        self._w._check(self._w._fn("particles_update")(self._h, float(dt)), "particles_update")
 
     def clear(self):
         self._w._check(self._w._fn("particles_clear")(self._h), "particles_clear")
@@ -292,17 +252,6 @@ class Particles:
         n, dropped = C.c_uint32(0), C.c_uint32(0)
         self._w._check(self._w._fn("particles_drain_events")(self._h, out.ctypes.data, cap, C.byref(n), C.byref(dropped)), "particles_drain_events")
         return out[:min(n.value, cap)].copy(), int(dropped.value)
-
-    def close(self):
-        if self._h:
-            self._w._fn("particles_destroy")(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class CWorld:
