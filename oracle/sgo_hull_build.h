@@ -387,6 +387,11 @@ static inline int sgo_hull_build_pts(const sgo_d3* pts, int n, double eps, doubl
 	h->aabb_min = V3(bmin[0], bmin[1], bmin[2]); h->aabb_max = V3(bmax[0], bmax[1], bmax[2]);
 	h->bound_radius = br; h->volume = (float)vol;
 	h->unit_inertia = V3((float)I[0][0], (float)I[1][1], (float)I[2][2]);
+	if (com_offset) {
+		/* the hull's own centroid lies at -o from the body origin: into the body frame (+ 0.0: an offset of zero gives +0, not -0) */
+		const sgo_d3 r = { -(double)com_offset[0], -(double)com_offset[1], -(double)com_offset[2] };
+		h->centroid = V3((float)(V[0][0] * r.x + V[1][0] * r.y + V[2][0] * r.z + 0.0), (float)(V[0][1] * r.x + V[1][1] * r.y + V[2][1] * r.z + 0.0), (float)(V[0][2] * r.x + V[1][2] * r.y + V[2][2] * r.z + 0.0));
+	}
 	com_out[0] = (float)cm.x; com_out[1] = (float)cm.y; com_out[2] = (float)cm.z;
 	/* rotation matrix (columns = principal axes) -> quaternion */
 	{

@@ -1607,7 +1607,12 @@ static void hull_submerged(const sgo_hull* hl, m33 R, float posz, float wz, floa
 	float lo = 3.4e38f, hi = -3.4e38f;
 	for (int i = 0; i < hl->nv; ++i) { const float t = v3_dot(n, hl->verts[i]); lo = fminf(lo, t); hi = fmaxf(hi, t); }
 	if (lo >= d) { *vol_out = 0.0f; *centroid_out = V3(0, 0, 0); return; }
-	if (hi <= d) { *vol_out = hl->volume; *centroid_out = V3(0, 0, 0); return; }
+	if (hi <= d) {
+		/* wholly under water: the hull's own centroid, which a centre-of-mass offset moves away from the origin (without one: +0, as before there was one) */
+		const v3 c = hl->centroid;
+		*vol_out = hl->volume; *centroid_out = (c.x != 0.0f || c.y != 0.0f || c.z != 0.0f) ? m33_mul(R, c) : V3(0, 0, 0);
+		return;
+	}
 	const v3 apex = v3_scale(n, d);
 	float vol = 0.0f; v3 cen = V3(0, 0, 0);
 	for (int f = 0; f < hl->nf; ++f) {

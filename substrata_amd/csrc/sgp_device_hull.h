@@ -28,6 +28,7 @@ struct sgd_hull_s {
 	v3 aabb_min, aabb_max;
 	float bound_radius, volume;
 	v3 unit_inertia;                   // principal moments for density 1
+	v3 centroid;                       // the hull's own centroid in the body frame: (0, 0, 0) unless a centre-of-mass offset moved the origin away from it (centre of buoyancy of the sunk hull)
 };
 typedef struct sgd_hull_s sgd_hull;
 

@@ -16,7 +16,7 @@
 #include "sgp_world_internal.h"
 
 #define CKPT_MAGIC "SGPCKPT"      // 7 characters + NUL
-#define CKPT_FORMAT_VERSION 1u
+#define CKPT_FORMAT_VERSION 2u      // 2: sgd_hull carries the hull's own centroid
 #define CKPT_MAX_VEHICLES (1u << 20)
 
 // ---- host state -----------------------------------------------------------------------------------------------------------------------------------------

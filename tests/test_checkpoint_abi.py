@@ -64,7 +64,10 @@ def _blob_info(lib, data):
     return lib.sgp_checkpoint_blob_info(buf, len(data), C.byref(info))
 
 
-def _header(total, host=0, shape=0, table=0, data=0, abi_version=abi.ABI_VERSION, fmt=1, header_bytes=None):
+FORMAT_VERSION = 2      # CKPT_FORMAT_VERSION of sgp_world_checkpoint.hip
+
+
+def _header(total, host=0, shape=0, table=0, data=0, abi_version=abi.ABI_VERSION, fmt=FORMAT_VERSION, header_bytes=None):
     """The fixed part of a blob's header as include/sgp.h's implementation lays it out: magic, four u32, five u64; the rest zero."""
     desc_bytes = C.sizeof(abi.WorldDesc)
     size = 8 + 16 + 40 + 32 + C.sizeof(abi.CheckpointInfo) + desc_bytes
@@ -83,7 +86,7 @@ def test_blob_info_rejects_what_is_not_a_blob(lib):
     # a correct magic with a wrong version (format, then ABI)
     h = _header(0)
     good_len = len(h)
-    assert _blob_info(lib, _header(good_len, fmt=2)) == abi.ERR_INVALID
+    assert _blob_info(lib, _header(good_len, fmt=FORMAT_VERSION + 1)) == abi.ERR_INVALID
     assert b"version" in lib.sgp_last_error()
     assert _blob_info(lib, _header(good_len, abi_version=abi.ABI_VERSION + 1)) == abi.ERR_INVALID
     assert b"version" in lib.sgp_last_error()

@@ -180,6 +180,41 @@ def test_submerged_volume_of_hulls_and_capsules(oracle):
     w.close()
 
 
+def test_centre_of_buoyancy_of_an_offset_hull_does_not_jump_when_it_goes_under(oracle):
+    """A hull created with a centre-of-mass offset (OffsetCenterOfMassShape: cars, bikes, dynamic meshes) has its own centroid an offset away from the body
+    origin.  With its highest corner half a millimetre above the surface and then half a millimetre below, the centre of buoyancy -- read off the torque of
+    the buoyancy impulse on the body at rest -- moves by less than a millimetre, and sits at the hull's centroid, not at the centre of mass."""
+    from buoyancy_reference import quat_to_mat
+    w = oracle.OracleWorld(max_bodies=16, gravity=(0.0, 0.0, 0.0))
+    w.set_water(True, 0.0)
+    rng = np.random.default_rng(11)
+    pts = (rng.uniform(-1.0, 1.0, size=(16, 3)) * (0.35, 0.3, 0.25)).astype(np.float32)
+    offset = np.array([0.1, -0.05, 0.2])
+    info = w.hull_create(pts, com_offset=tuple(offset))
+    verts, _ = oracle.hull_dump(w, info.hull_id)
+    rot = quat_axis_angle((1.0, 0.2, 0.0), 1.4)
+    R = quat_to_mat(np.asarray(rot, np.float32))
+    top = float((verts.astype(np.float64) @ R[2]).max())
+    mass = 300.0
+    ids = [dyn(w, shape_type=abi.SHAPE_HULL, shape=(float(info.hull_id), 0, 0, 0), pos=(5.0 * k, 0, -top + dz), rot=rot, mass=mass, allow_sleeping=0)
+           for k, dz in enumerate((0.0005, -0.0005))]
+    w.step(DT)
+    centroid = -(R @ quat_to_mat(info.rot[:]).T @ offset)         # the hull's own centroid relative to the body origin, world axes
+    assert np.hypot(centroid[0], centroid[1]) > 0.05
+    cob = []
+    for i in ids:
+        s = w.get_state([i])[0]
+        assert s["underwater"] == 1 and abs(s["submerged_volume"] - info.volume) < 1e-6
+        jz = float(s["lin_vel"][2]) * mass                         # the impulse, straight up; its angular impulse = cob x impulse = (cob_y jz, -cob_x jz, 0)
+        inertia = np.array(info.unit_inertia[:], np.float64) * mass / info.volume
+        ang_imp = R @ (inertia * (R.T @ s["ang_vel"].astype(np.float64)))
+        cob.append(np.array([-ang_imp[1] / jz, ang_imp[0] / jz]))
+        assert abs(ang_imp[2]) < 1e-5 * abs(jz)
+    assert np.linalg.norm(cob[0] - cob[1]) < 1e-3, (cob, centroid)
+    assert np.linalg.norm(cob[1] - centroid[:2]) < 1e-4, (cob, centroid)
+    w.close()
+
+
 def test_layer_matrix(oracle):
     """(viii) MyObjectLayerPairFilter truth table, PhysicsWorld.cpp:151-189."""
     NM, M, NMNC, MNC = 0, 1, 2, 3
