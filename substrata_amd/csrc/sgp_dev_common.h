@@ -57,6 +57,60 @@ template <int WHAT> SGP_DEV void keep_head(const DV& d, uint32_t parity, uint32_
 	keep_buffer<WHAT>(d.ca[0]);
 	keep_buffer<WHAT>(d.ca[1]);
 }
+// STORE POLICY of a record a LATER launch reads and the storing launch itself never does (docs/KERNELS.md, "Write-through stores": the rule and the audit).
+// A plain store leaves the line dirty in the XCD's L2 and the kernel boundary writes it back before the next launch may start; a write-through store (sc1)
+// sends the same bytes on while the launch's other waves are still working.  ST_WT is for such records only: the line does not stay in L2, so a lane
+// of the same launch that read it again would fetch it from memory.  Kernels that walk several colours in one workgroup keep ST_PLAIN; a device function
+// shared between both kinds takes the policy from its caller (template flag, one body for both).
+// store_rec<ST>(base, index, v) is base[index] = v.  ST_WT: ONE buffer store of the record's own width (16, 8 or 4 bytes, a vector store) through the compiler's
+// raw buffer builtin with the sc1 cache-policy bit -- compiler-visible, so counters and hazards stay the compiler's business, no inline assembly.  `base` must be
+// uniform over the wave (an array's base out of the kernel arguments or cur_arrays: it becomes the descriptor in scalar registers; a per-lane pointer would be
+// looped over lane by lane) and the record's byte offset must fit 32 bits: every record array does (sgp_world_create: max_bodies < 2^25 records of 64 bytes,
+// max_manifolds < 2^28 - 1 records of 16 bytes).  The descriptor is the plain one (stride 0, 2^32 - 1 bytes, raw dword format): its range check never drops a store.
+enum { ST_PLAIN = 0, ST_WT = 1 };
+// What the solver launches whose stores qualify AND gain run with: the velocity and position instances of k_solve_colour, the pass of k_solve_hc.
+// Measured on config 3 (profiles/write_through_stores.md): +2.8 %, a velocity colour launch 6.8 -> 6.4 us -- with a record's two halves in ONE store instruction
+// (store_rec2 below); as two stores of one lane the same policy LOST 1.6 %.  -DSGP_SOLVER_STORES=0 builds the plain twin for another measurement
+// (tests/test_store_policy_codegen.py holds both).
+#ifndef SGP_SOLVER_STORES
+#define SGP_SOLVER_STORES ST_WT
+#endif
+#define SGP_AUX_SC1 16      // cache-policy operand of the buffer builtins: bit 4 = sc1
+template <int ST, class T> SGP_DEV void store_rec(T* base, size_t index, const T& v)
+{
+	static_assert(sizeof(T) == 16 || sizeof(T) == 8 || sizeof(T) == 4, "store_rec: one store instruction per record");
+	if constexpr (ST == ST_WT) {
+		typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+		typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+		const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, 0xFFFFFFFF, 0x00020000);
+		const uint32_t off = (uint32_t)(index * sizeof(T));
+		if constexpr (sizeof(T) == 16) { u32x4 x; __builtin_memcpy(&x, &v, 16); __builtin_amdgcn_raw_buffer_store_b128(x, rsrc, off, 0, SGP_AUX_SC1); }
+		else if constexpr (sizeof(T) == 8) { u32x2 x; __builtin_memcpy(&x, &v, 8); __builtin_amdgcn_raw_buffer_store_b64(x, rsrc, off, 0, SGP_AUX_SC1); }
+		else { uint32_t x; __builtin_memcpy(&x, &v, 4); __builtin_amdgcn_raw_buffer_store_b32(x, rsrc, off, 0, SGP_AUX_SC1); }
+	} else base[index] = v;
+}
+// A record of TWO float4 (base[at], base[at + 1]: 32 contiguous bytes; the velocity half of a solver record, position + rotation of a pose record), stored by a
+// lane PAIR (lanes 2k and 2k + 1, each with a record of its own and whether it is to be stored; BOTH lanes must be at the call).  Written through as two 16-byte
+// stores of one lane, the halves leave the L2 as two partial writes of 32 bytes each -- WRITE_SIZE per launch doubled (profiles/write_through_stores.md) --, so the
+// pair shares the work the other way round: first the even lane's record, its first half by the even lane and its second by the odd lane, then the odd lane's
+// record likewise.  One store instruction then carries the 32 contiguous bytes of a record in two neighbouring lanes.  ST_PLAIN: each lane stores its own.
+SGP_DEV uint32_t lane_swap1_u(uint32_t x) { return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0xB1, 0xF, 0xF, true); }      // (the value lane ^ 1 holds: lane_swap1, sgp_dev_solve.h)
+SGP_DEV float4 lane_swap1_f4(float4 v)
+{
+	return make_float4(__uint_as_float(lane_swap1_u(__float_as_uint(v.x))), __uint_as_float(lane_swap1_u(__float_as_uint(v.y))),
+	                   __uint_as_float(lane_swap1_u(__float_as_uint(v.z))), __uint_as_float(lane_swap1_u(__float_as_uint(v.w))));
+}
+template <int ST> SGP_DEV void store_rec2(float4* base, size_t at, float4 a, float4 b, bool store)
+{
+	if constexpr (ST == ST_WT) {
+		const bool odd = (threadIdx.x & 1u) != 0u;
+		const uint32_t mine = (uint32_t)at, other = lane_swap1_u(mine);
+		const bool ostore = lane_swap1_u(store ? 1u : 0u) != 0u;
+		const float4 oa = lane_swap1_f4(a), ob = lane_swap1_f4(b);
+		if (odd ? ostore : store) store_rec<ST_WT>(base, odd ? other + 1u : mine, odd ? ob : a);
+		if (odd ? store : ostore) store_rec<ST_WT>(base, odd ? mine + 1u : other, odd ? b : oa);
+	} else if (store) { base[at] = a; base[at + 1] = b; }
+}
 // a constraint's header: the two body ids (8 bytes), np_col, or all of it in one 16-byte load
 SGP_DEV uint2 con_ab(const ConstraintArrays& c, size_t k) { return *(const uint2*)(c.hdr + k); }
 SGP_DEV int& con_npc(const ConstraintArrays& c, size_t k) { return ((int*)(c.hdr + k))[2]; }

@@ -145,12 +145,14 @@ template <int ROWS = -1> SGP_DEV void half_load(const DV& d, const ConstraintArr
 	half_load_known<ROWS>(d, ca, slot, side, (int)hd.z, side ? hd.y : hd.x, h);
 }
 
-SGP_DEV void half_store(const ConstraintArrays& ca, uint32_t slot, int side, const ConHalf& h)
+// (ST: the store policy, store_rec -- the caller's choice here and in every function below that has it: ST_WT from a launch that solves ONE colour, or from the
+// component launch's pass, whose records nobody reads again before the next launch; ST_PLAIN, the default, wherever a workgroup walks on to the next colour)
+template <int ST = ST_PLAIN> SGP_DEV void half_store(const ConstraintArrays& ca, uint32_t slot, int side, const ConHalf& h)
 {
 	if (side) return;
 	const int np = h.np_col & 0xFF;
 #pragma unroll
-	for (int i = 0; i < 4; ++i) { if (i < np) ca.lam[i][slot] = F4(h.lam[i], 0.0f); }
+	for (int i = 0; i < 4; ++i) { if (i < np) store_rec<ST>(ca.lam[i], slot, F4(h.lam[i], 0.0f)); }
 }
 
 // (the forms that look the buffer up themselves: experiments)
@@ -213,20 +215,22 @@ SGP_DEV bool half_solve_core(ConHalf& h, int side, float4& v4, float4& w4, uint3
 	v4 = F4(lv, im); w4 = F4(av, 0.0f);
 	return im > 0.0f;
 }
-template <int VS> SGP_DEV void half_solve(ConHalf& h, int side, float4* vel, uint32_t dbg = 0)
+template <int VS, int ST = ST_PLAIN> SGP_DEV void half_solve(ConHalf& h, int side, float4* vel, uint32_t dbg = 0)
 {
+	static_assert(ST == ST_PLAIN || VS == VEL_F4, "write-through is for the global records, never a copy in LDS");
 	if ((h.np_col & 0xFF) == 0) return;                    // a sensor pair: kept in the contact list, nothing to solve
 	float4 v4 = vel[VS * (size_t)h.body], w4 = vel[VS * (size_t)h.body + 1];
-	if (half_solve_core(h, side, v4, w4, dbg)) { vel[VS * (size_t)h.body] = v4; vel[VS * (size_t)h.body + 1] = w4; }
+	const bool can_move = half_solve_core(h, side, v4, w4, dbg);
+	store_rec2<ST>(vel, VS * (size_t)h.body, v4, w4, can_move);      // (both lanes of the constraint are here: they share np)
 }
 
 // load + one iteration + store: what a colour launch does per constraint (lanes 2k and 2k + 1 of a wave call it with the same slot)
-template <int VS, int ROWS = -1> SGP_DEV void solve_velocity_pair_t(const DV& d, const ConstraintArrays& ca, uint32_t slot, int side, float4* vel)
+template <int VS, int ROWS = -1, int ST = ST_PLAIN> SGP_DEV void solve_velocity_pair_t(const DV& d, const ConstraintArrays& ca, uint32_t slot, int side, float4* vel)
 {
 	ConHalf h;
 	half_load<ROWS>(d, ca, slot, side, h);
-	half_solve<VS>(h, side, vel, d.dbg_flags);
-	half_store(ca, slot, side, h);
+	half_solve<VS, ST>(h, side, vel, d.dbg_flags);
+	half_store<ST>(ca, slot, side, h);
 }
 
 template <int VS, int ROWS = -1> SGP_DEV void solve_velocity_pair_t(const DV& d, uint32_t slot, int side, float4* vel) { solve_velocity_pair_t<VS, ROWS>(d, CUR(d), slot, side, vel); }
@@ -235,7 +239,7 @@ template <int VS, int ROWS = -1> SGP_DEV void solve_velocity_pair_t(const DV& d,
 // loads a constraint, iterates it ONCE and stores it, so r x axis and I (r x axis) -- 72 registers of a ConHalf -- are built where the row is applied instead of
 // where the constraint is loaded.  The same expressions on the same operands in the same order as half_load_rows<2> + half_solve_core (each value is computed once
 // either way): the same bits.  What it buys is registers: the launch fits four waves per SIMD, and a colour of 300k constraints is nine waves per SIMD.
-template <int VS> SGP_DEV void solve_velocity_pair_norows(const DV& d, const ConstraintArrays& ca, uint32_t slot, int side, float4* vel)
+template <int VS, int ST = ST_PLAIN> SGP_DEV void solve_velocity_pair_norows(const DV& d, const ConstraintArrays& ca, uint32_t slot, int side, float4* vel)
 {
 	const uint4 hd = con_hdr(ca, slot);      // ids + np_col: one 16-byte load
 	const int np = (int)hd.z & 0xFF;
@@ -284,10 +288,11 @@ template <int VS> SGP_DEV void solve_velocity_pair_norows(const DV& d, const Con
 			lam[i].x = nl;
 		}
 	}
-	if (im > 0.0f) { vel[VS * (size_t)body] = F4(lv, im); vel[VS * (size_t)body + 1] = F4(av, 0.0f); }
+	static_assert(ST == ST_PLAIN || VS == VEL_F4, "write-through is for the global records, never a copy in LDS");
+	store_rec2<ST>(vel, VS * (size_t)body, F4(lv, im), F4(av, 0.0f), im > 0.0f);      // (both lanes of the constraint are here: they share np)
 	if (!side) {
 #pragma unroll
-		for (int i = 0; i < 4; ++i) { if (i < np) ca.lam[i][slot] = F4(lam[i], 0.0f); }
+		for (int i = 0; i < 4; ++i) { if (i < np) store_rec<ST>(ca.lam[i], slot, F4(lam[i], 0.0f)); }
 	}
 }
 
@@ -304,8 +309,8 @@ SGP_DEV void pos_half_load(const ConstraintArrays& ca, uint32_t slot, int side, 
 	for_points(ph.np, [&](int i) { ph.loc[i] = V3((side ? ca.loc2[i] : ca.loc1[i])[slot]); });
 }
 // (rec: where this lane's body's pose record lives -- the global one, or a workgroup's copy in LDS; ii: its local inverse inertia diagonal)
-// (p4, q4: the two float4 of the record, already read)
-SGP_DEV void pos_half_solve_rec(const DV& d, const PosHalf& ph, int side, float4* rec, float4 p4, float4 q4, v3 ii)
+// (p4, q4: the two float4 of the record, already read; the record is recs[at], recs[at + 1]: the array's base and the record's place apart, as store_rec wants them)
+template <int ST = ST_PLAIN> SGP_DEV void pos_half_solve_rec(const DV& d, const PosHalf& ph, int side, float4* recs, size_t at, float4 p4, float4 q4, v3 ii)
 {
 	const v3 nrm = V3(ph.nf);
 	const int np = ph.np;
@@ -345,10 +350,10 @@ SGP_DEV void pos_half_solve_rec(const DV& d, const PosHalf& ph, int side, float4
 			moved = true;
 		}
 	}
-	if (moved && im > 0.0f) { rec[0] = F4(pos, im); rec[1] = make_float4(q.x, q.y, q.z, q.w); }
+	store_rec2<ST>(recs, at, F4(pos, im), make_float4(q.x, q.y, q.z, q.w), moved && im > 0.0f);      // (both lanes are here: every branch above is on values the two share)
 }
-SGP_DEV void pos_half_solve(const DV& d, const PosHalf& ph, int side, float4* rec, v3 ii) { pos_half_solve_rec(d, ph, side, rec, rec[0], rec[1], ii); }
-SGP_DEV void solve_position_pair(const DV& d, const ConstraintArrays& ca, uint32_t slot, int side)
+SGP_DEV void pos_half_solve(const DV& d, const PosHalf& ph, int side, float4* rec, v3 ii) { pos_half_solve_rec(d, ph, side, rec, 0, rec[0], rec[1], ii); }
+template <int ST = ST_PLAIN> SGP_DEV void solve_position_pair(const DV& d, const ConstraintArrays& ca, uint32_t slot, int side)
 {
 	const uint4 hd = con_hdr(ca, slot);      // ids + np_col: one 16-byte load
 	const uint32_t body = side ? hd.y : hd.x;
@@ -358,10 +363,10 @@ SGP_DEV void solve_position_pair(const DV& d, const ConstraintArrays& ca, uint32
 	const auto load_point = [&](int i) { ph.loc[i] = V3((side ? ca.loc2[i] : ca.loc1[i])[slot]); };
 	load_point(0);
 	// this lane's body's pose record + its local inverse inertia, requested BESIDE the further points: both wait for the header and for nothing else
-	float4* rec = d.pose + POSE_F4 * (size_t)body;
+	const float4* rec = d.pose + POSE_F4 * (size_t)body;
 	const float4 p4 = rec[0], q4 = rec[1], i4 = rec[2];
 	more_points(ph.np, load_point);
-	pos_half_solve_rec(d, ph, side, rec, p4, q4, V3(i4));
+	pos_half_solve_rec<ST>(d, ph, side, d.pose, POSE_F4 * (size_t)body, p4, q4, V3(i4));
 }
 SGP_DEV void solve_position_pair_at(const DV& d, const ConstraintArrays& ca, uint32_t slot, int side, float4* rec, v3 ii)
 {

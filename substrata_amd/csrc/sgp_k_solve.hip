@@ -43,6 +43,9 @@ template <int VS> SGP_DEV void load_pair(const DV& d, const ConstraintArrays& ca
 
 template <int VS> SGP_DEV void load_pair(const DV& d, uint32_t slot, PairCtx& c, const float4* vel) { load_pair<VS>(d, CUR(d), slot, c, vel); }
 
+// (plain stores, also from k_solve_colour<0>, whose records would qualify for write-through: one lane holds both bodies and its neighbour may be past the colour's
+// end, so there is no lane pair for store_rec2, and a record's halves written through one by one leave the L2 as two partial writes -- docs/KERNELS.md,
+// "Write-through stores")
 template <int VS> SGP_DEV void store_pair_vel(const PairCtx& c, float4* vel)
 {
 	if (c.im1 > 0.0f) { vel[VS * (size_t)c.ab.x] = F4(c.A.lv, c.im1); vel[VS * (size_t)c.ab.x + 1] = F4(c.A.av, 0.0f); }
@@ -107,6 +110,8 @@ SGP_DEV void warm_body_one(const DV& d, uint32_t i)
 #pragma unroll
 		for (int k = 0; k < 4; ++k) if (col[k] >= 0) { lv = v3_add(lv, V3(a[k])); av = v3_add(av, V3(b[k])); }
 	}
+	// (plain stores.  The record qualifies for write-through -- one thread per body, nobody reads it again in this launch but the rare constraints of the overflow
+	// colour -- and did not gain by it: 11.5 - 12.3 us plain, 12.9 us as two write-through stores, 12.5 us through store_rec2; docs/KERNELS.md, "Write-through stores")
 	rec[0] = F4(lv, im);
 	rec[1] = F4(av, 0.0f);
 }
@@ -218,6 +223,13 @@ template <int MODE, int ROWS = -1, int OCC = 1> __global__ void __launch_bounds_
 	// one wait for the parity, the colour's range, both buffers' pointers and the body records' base: nothing of it depends on anything else of it
 	keep_head<MODE == 2 ? CA_LOC : (MODE == 0 || ROWS == 2) ? CA_ARMS : CA_LAM>(d_arg, parity, first, end, MODE == 2 ? d_arg.pose : d_arg.vel, gridDim.x);
 	const ConstraintArrays ca = cur_arrays(d_arg, parity);      // (this step's buffers by value, resolved before any store)
+	// One colour per launch: constraints of a colour share no body that can move, a body that cannot is never stored, and the grid-stride loop takes a lane to
+	// another constraint of the SAME colour -- no lane of this launch reads a record or an impulse another lane stored, so they are written through
+	// (store_rec, store_rec2; docs/KERNELS.md, "Write-through stores").  Not by the warm start by constraint (MODE 0): store_pair_vel.  And not in the instances
+	// for large colours (OCC != 1; launch_solve_colour, SOLVE_WT_MAX and SOLVE_MANY_MIN): a colour that does not fit the L2s evicts its lines by capacity long
+	// before the boundary, and config 4 (colours of 300k constraints and more) measured 1.3 % SLOWER with every colour written through, 0.8 % with those above
+	// SOLVE_MANY_MIN on plain stores, and the parent's speed with plain stores from SOLVE_WT_MAX on (profiles/write_through_stores.md).
+	constexpr int ST = OCC == 1 ? SGP_SOLVER_STORES : ST_PLAIN;
 	if (MODE != 0) {
 		// velocity and position iterations: two neighbouring lanes per constraint
 		const int side = (int)(threadIdx.x & 1u);
@@ -226,8 +238,8 @@ template <int MODE, int ROWS = -1, int OCC = 1> __global__ void __launch_bounds_
 		// cache lines, and the same XCD meets the same rows again in the next pass.  (The grid is a multiple of eight: launch_solve_colour.)
 		const uint32_t bx = (colour_arg & SOLVE_XCD_CHUNKS) ? xcd_block() : blockIdx.x;      // (a colour of 200k constraints -- config 4 -- streams from HBM whatever the order, and lost 17 % with the chunks)
 		for (uint32_t k = first + ((bx * SOLVE_VEL_TPB + threadIdx.x) >> 1); k < end; k += gridDim.x * (SOLVE_VEL_TPB / 2)) {
-			if (MODE == 1) { if constexpr (ROWS == 2) solve_velocity_pair_norows<VEL_F4>(d, ca, k, side, d.vel); else solve_velocity_pair_t<VEL_F4, ROWS>(d, ca, k, side, d.vel); }
-			else solve_position_pair(d, ca, k, side);
+			if (MODE == 1) { if constexpr (ROWS == 2) solve_velocity_pair_norows<VEL_F4, ST>(d, ca, k, side, d.vel); else solve_velocity_pair_t<VEL_F4, ROWS, ST>(d, ca, k, side, d.vel); }
+			else solve_position_pair<ST>(d, ca, k, side);
 		}
 		return;
 	}
@@ -689,6 +701,13 @@ void launch_ts_solve(const DV&, int, int, hipStream_t) {}
 #ifndef SOLVE_MANY_OCC
 #define SOLVE_MANY_OCC 3
 #endif
+// Constraints in a colour up to which its launch writes through (k_solve_colour: the OCC == 1 instances do, the others keep plain stores).  The bound of the
+// XCD-contiguous chunks below, for the same reason: up to here the colour's bodies and rows fit the eight L2s and what the launch leaves dirty waits for the
+// boundary; a larger colour evicts its lines by capacity as it goes.  On the layout without rows and in the position passes the two instances differ in their
+// stores alone (same instructions, registers and waves per SIMD from the compiler), so there the plain one simply takes over from this size on.
+#ifndef SOLVE_WT_MAX
+#define SOLVE_WT_MAX 65536u
+#endif
 void launch_solve_colour(const DV& d, int colour, uint32_t est, int mode, hipStream_t s, int compact_rows)
 {
 	uint32_t blocks = (est + est / 8 + 64 + SOLVE_TPB - 1) / SOLVE_TPB;      // warm start: one thread per constraint, one wave per workgroup
@@ -699,11 +718,14 @@ void launch_solve_colour(const DV& d, int colour, uint32_t est, int mode, hipStr
 	if (mode == 0) hipLaunchKernelGGL(k_solve_colour<0>, dim3(blocks), dim3(SOLVE_TPB), 0, s, (const uint32_t*)d.cstarts, d.sp, colour, d);
 	else if (mode == 1) {
 		const bool many = est > SOLVE_MANY_MIN;
-		if (compact_rows == 2) hipLaunchKernelGGL((k_solve_colour<1, 2>), dim3(blocks), dim3(SOLVE_VEL_TPB), 0, s, (const uint32_t*)d.cstarts, d.sp, colour, d);      // (108 VGPRs: four waves per SIMD as it is, solve_velocity_pair_norows; five spill and lose)
+		if (compact_rows == 2) {      // (108 VGPRs: four waves per SIMD as it is, solve_velocity_pair_norows; five spill and lose -- the instance for large colours differs in its stores alone)
+			if (est > SOLVE_WT_MAX) hipLaunchKernelGGL((k_solve_colour<1, 2, SOLVE_MANY_OCC>), dim3(blocks), dim3(SOLVE_VEL_TPB), 0, s, (const uint32_t*)d.cstarts, d.sp, colour, d);
+			else hipLaunchKernelGGL((k_solve_colour<1, 2>), dim3(blocks), dim3(SOLVE_VEL_TPB), 0, s, (const uint32_t*)d.cstarts, d.sp, colour, d);
+		}
 		else if (compact_rows) { if (many) hipLaunchKernelGGL((k_solve_colour<1, 1, SOLVE_MANY_OCC>), dim3(blocks), dim3(SOLVE_VEL_TPB), 0, s, (const uint32_t*)d.cstarts, d.sp, colour, d); else hipLaunchKernelGGL((k_solve_colour<1, 1>), dim3(blocks), dim3(SOLVE_VEL_TPB), 0, s, (const uint32_t*)d.cstarts, d.sp, colour, d); }
 		else hipLaunchKernelGGL((k_solve_colour<1, 0>), dim3(blocks), dim3(SOLVE_VEL_TPB), 0, s, (const uint32_t*)d.cstarts, d.sp, colour, d);
 	}
-	else if (est > SOLVE_MANY_MIN) hipLaunchKernelGGL((k_solve_colour<2, -1, SOLVE_MANY_OCC>), dim3(blocks), dim3(SOLVE_VEL_TPB), 0, s, (const uint32_t*)d.cstarts, d.sp, colour, d);
+	else if (est > SOLVE_WT_MAX) hipLaunchKernelGGL((k_solve_colour<2, -1, SOLVE_MANY_OCC>), dim3(blocks), dim3(SOLVE_VEL_TPB), 0, s, (const uint32_t*)d.cstarts, d.sp, colour, d);
 	else hipLaunchKernelGGL(k_solve_colour<2>, dim3(blocks), dim3(SOLVE_VEL_TPB), 0, s, (const uint32_t*)d.cstarts, d.sp, colour, d);
 }
 void launch_warm_bodies(const DV& d, uint32_t nb, hipStream_t s) { hipLaunchKernelGGL(k_warm_bodies, dim3(blocks_for(nb)), dim3(TPB), 0, s, d); }

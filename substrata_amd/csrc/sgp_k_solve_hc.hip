@@ -62,11 +62,17 @@ template <int MODE, int ROWS = -1> __global__ void __launch_bounds__(HC_TPB) k_s
 			if (my_col == c) { if (MODE == 1) half_solve<2>(h, side, s_rec, d.dbg_flags); else pos_half_solve(d, ph, side, s_rec + RS * at, V3(s_rec[RS * at + 2])); }
 			__syncthreads();
 		}
-		if (MODE == 1 && mine) half_store(ca(), slot, side, h);
-		if (owner && s_rec[RS * at].w > 0.0f) {
-			float4* g = (MODE == 1 ? d.vel + VEL_F4 * (size_t)body : d.pose + POSE_F4 * (size_t)body);
-			g[0] = s_rec[RS * at]; g[1] = s_rec[RS * at + 1];
-		}
+		// the pass's only global stores: impulses and records were read once, above, and are written once, here, through to memory (store_rec, store_rec2;
+		// SGP_SOLVER_STORES); the catch-all below walks colours through global memory and keeps plain stores (it comes behind two fences, and a component is
+		// solved here or there, never both)
+		constexpr int ST = SGP_SOLVER_STORES;
+		if (MODE == 1 && mine) half_store<ST>(ca(), slot, side, h);
+		float4* const recs = MODE == 1 ? d.vel : d.pose;
+		const size_t g = (MODE == 1 ? VEL_F4 : POSE_F4) * (size_t)body;
+		if constexpr (ST == ST_WT) {
+			const float4 ra = s_rec[RS * at], rb = s_rec[RS * at + 1];      // (every lane comes along, store_rec2: one that owns nothing reads slot 0 and stores nothing)
+			store_rec2<ST>(recs, g, ra, rb, owner && ra.w > 0.0f);
+		} else if (owner && s_rec[RS * at].w > 0.0f) { recs[g] = s_rec[RS * at]; recs[g + 1] = s_rec[RS * at + 1]; }
 	}
 	// catch-all: components too large for a workgroup and the overflow colour, by the last workgroup to finish (nothing to do: no ticket either)
 	const uint32_t n_big = d.ctr->hc_n_big;
