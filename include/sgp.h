@@ -616,7 +616,7 @@ int  sgp_spherecast(sgp_world* w, const sgp_ray* rays, const float* radii, uint3
  * The algorithm, its constants and its fp32 expressions are those of shim/Jolt/JoltCharacterLite.h (the host class that walks one
  * character at a time through sgp_collide_capsules / sgp_spherecast): a character of a batch moves as that class moves it.
  * The capsule's axis is the world z axis (identity rotation, as PlayerPhysics uses it).  Characters do not collide with each other.
- * A batch holds no state that a world checkpoint captures (docs/GAPS.md). */
+ * A world checkpoint holds nothing of a batch; sgp_characters_checkpoint / _rollback do ("batch checkpoints", below). */
 typedef struct sgp_characters sgp_characters;
 #define SGP_CHAR_EXTENDED  1u   /* ExtendedUpdate (stick to floor, stairs); without it the plain Update of PlayerPhysics::updateForInVehicle */
 #define SGP_CHAR_NO_SLIDE  2u   /* PlayerPhysics::OnContactSolve (PlayerPhysics.cpp:536-545): a contact whose velocity is near zero (squared length <= 1e-12)
@@ -700,7 +700,7 @@ int  sgp_characters_drain_contacts(sgp_characters* cs, sgp_character_contact* ou
  * but every body the facade creates carries its object, so the two agree.  Particles never act on bodies or on each other.
  * Departures from the reference (docs/GAPS.md): the dead are removed by a STABLE compaction (survivors keep their order; the reference
  * swaps with the last), and a full batch replaces its particles in round-robin slot order (the reference picks a random victim).
- * A batch holds no state that a world checkpoint captures.  In a tiled world particles see ghost bodies as bodies; nothing is exchanged. */
+ * A world checkpoint holds nothing of a batch; sgp_particles_checkpoint / _rollback do ("batch checkpoints", below).  In a tiled world particles see ghost bodies as bodies; nothing is exchanged. */
 typedef struct sgp_particles sgp_particles;
 #define SGP_PARTICLE_DIE_ON_HIT    1u   /* Particle::die_when_hit_surface (ParticleManager.cpp:189-190,198-206) */
 #define SGP_PARTICLE_EV_DIED       1u   /* cur_opacity <= 0 after the update (ParticleManager.cpp:259-267): the particle is gone          */
@@ -776,7 +776,7 @@ int  sgp_particles_clear(sgp_particles* ps);
  * car with a driver casts its one ray with the function sgp_raycast runs per ray.  The dust, spray and foam an update makes go to an attached
  * sgp_particles batch without leaving the device.  Nothing is read back, nothing waits.
  * Departures from the reference (docs/GAPS.md): the random numbers are a counter-based generator of this library (glare-core's PCG32 is not
- * reproduced); a batch holds no state that a world checkpoint captures; tiled worlds are refused; sgp_world_step_n advances n steps with ONE
+ * reproduced); a world checkpoint holds nothing of a batch (sgp_crafts_checkpoint / _rollback do); tiled worlds are refused; sgp_world_step_n advances n steps with ONE
  * update's forces where the reference updates per sub-step: step one at a time.
  * The caller creates a boat's body with use_zero_linear_drag = 1 (BoatPhysics.cpp:36 sets it on the object: the boat computes its own drag). */
 typedef struct sgp_crafts sgp_crafts;
@@ -890,7 +890,7 @@ int  sgp_crafts_get_states(sgp_crafts* cs, uint32_t first, uint32_t n, sgp_craft
  * read back, nothing waits.  Call it before each sgp_world_step, where the reference runs its controllers (GUIClient.cpp:6394-6418).
  * The fp32 expressions and their order: docs/CONTRACT.md 4j.  Departures from the reference (docs/GAPS.md): an update passes at most
  * SGP_MOVER_MAX_SEGMENTS_PER_UPDATE segment ends forwards or segment starts backwards; a follower's leader is a walker on the same path (no
- * chains); a path has at most SGP_MOVER_MAX_WAYPOINTS waypoints; rotations are held as quaternions; no checkpoint state; tiled worlds are
+ * chains); a path has at most SGP_MOVER_MAX_WAYPOINTS waypoints; rotations are held as quaternions; a world checkpoint holds nothing of a batch (sgp_movers_checkpoint / _rollback do); tiled worlds are
  * refused; sgp_world_step_n advances n steps on one update. */
 typedef struct sgp_movers sgp_movers;
 #define SGP_MOVER_PATH   0u
@@ -1212,6 +1212,48 @@ int  sgp_checkpoint_write(const sgp_checkpoint* cp, void* out, uint64_t cap, uin
 int  sgp_world_restore(sgp_world* fresh, const void* blob, uint64_t bytes);
 /* Validates a blob and reads its counts.  Host only: needs no device. */
 int  sgp_checkpoint_blob_info(const void* blob, uint64_t bytes, sgp_checkpoint_info* out);
+
+/* ---- batch checkpoints: capture and rollback of sgp_characters, sgp_particles, sgp_crafts and sgp_movers ---- */
+/* A world checkpoint holds nothing of the world's batches; these pairs do, by the world's rule (docs/CONTRACT.md, "Batch checkpoints"): after
+ * sgp_world_rollback and one rollback per batch, each to the checkpoint taken at the same moment, in any order and with no update or step in
+ * between, the whole scene continues bit for bit as one that was never interrupted.  The pairing is the caller's: world_steps_taken is there to
+ * check it.  A batch checkpoint is opaque, owns device and host memory, belongs to the batch that made it and may outlive it and its world
+ * (get_info and destroy still work).  There is no blob, and no restoring into a fresh batch.
+ *
+ * Capture: *io == NULL creates a checkpoint, else *io is overwritten in place and its buffers are re-used (device_bytes grows only when the
+ * batch's high-water slot did; for particles, the host's bound of the live count).  Host edits that no update has carried yet go to the device
+ * first; the copy is enqueued on the world's stream and the call returns without waiting for it.  It changes nothing any later call returns.
+ * Rollback: the batch becomes exactly what it was at the capture -- the device's state (for particles: the live ones, their count, the
+ * replacement cursor, undrained events and the dropped count; for characters: undrained contact and push records too), the host's records and
+ * inputs, tags, the movers' paths with their reference counts, and the slot tables with the free list's order, so that the next *_add returns
+ * the id it would have.  Not touched: which particle batch a craft batch is attached to.
+ * A craft or mover that was attached to its body at the capture is attached to the same body id again if that is now a live body the batch
+ * could be added on (whatever happened to it in between -- the world's rollback brings a removed body back), and BODY_GONE from the next
+ * update on otherwise; one that was BODY_GONE at the capture stays so.
+ * SGP_ERR_INVALID, with the batch untouched: NULL, a checkpoint of another batch or kind, a batch whose world is gone, a world that holds ghost
+ * bodies. */
+#define SGP_BATCH_CHARACTERS 1u
+#define SGP_BATCH_PARTICLES  2u
+#define SGP_BATCH_CRAFTS     3u
+#define SGP_BATCH_MOVERS     4u
+typedef struct sgp_batch_checkpoint sgp_batch_checkpoint;
+typedef struct sgp_batch_checkpoint_info {
+	uint64_t device_bytes, host_bytes;   /* what the checkpoint holds                                                             */
+	uint32_t kind;                       /* SGP_BATCH_*                                                                           */
+	uint32_t capacity, high_slot, num_alive;      /* of the batch at the capture (particles: high_slot and num_alive are the host's bound of the live count) */
+	uint32_t world_steps_taken;          /* steps the batch's world had taken at the capture: lets a caller check the pairing     */
+	uint32_t pad_;
+} sgp_batch_checkpoint_info;
+int  sgp_characters_checkpoint(sgp_characters* cs, sgp_batch_checkpoint** io);
+int  sgp_characters_rollback(sgp_characters* cs, const sgp_batch_checkpoint* cp);
+int  sgp_particles_checkpoint(sgp_particles* ps, sgp_batch_checkpoint** io);
+int  sgp_particles_rollback(sgp_particles* ps, const sgp_batch_checkpoint* cp);
+int  sgp_crafts_checkpoint(sgp_crafts* cs, sgp_batch_checkpoint** io);
+int  sgp_crafts_rollback(sgp_crafts* cs, const sgp_batch_checkpoint* cp);
+int  sgp_movers_checkpoint(sgp_movers* ms, sgp_batch_checkpoint** io);
+int  sgp_movers_rollback(sgp_movers* ms, const sgp_batch_checkpoint* cp);
+int  sgp_batch_checkpoint_destroy(sgp_batch_checkpoint* cp);      /* NULL: SGP_OK */
+int  sgp_batch_checkpoint_get_info(const sgp_batch_checkpoint* cp, sgp_batch_checkpoint_info* out);
 
 #ifdef __cplusplus
 }

@@ -366,6 +366,18 @@ class CheckpointInfo(C.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+BATCH_CHARACTERS, BATCH_PARTICLES, BATCH_CRAFTS, BATCH_MOVERS = 1, 2, 3, 4
+
+
+class BatchCheckpointInfo(C.Structure):
+    """sgp_batch_checkpoint_info: what a checkpoint of a batch holds."""
+    _fields_ = [("device_bytes", u64), ("host_bytes", u64), ("kind", u32), ("capacity", u32), ("high_slot", u32),
+                ("num_alive", u32), ("world_steps_taken", u32), ("pad_", u32)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "pad_"}
+
+
 ABI_SIZEOF_ORDER = ["sgp_settings", "sgp_world_desc", "sgp_body_desc", "sgp_body_state", "sgp_body_event",
                     "sgp_contact_event", "sgp_ray", "sgp_hit", "sgp_step_stats", "sgp_step_profile", "sgp_ghost_record",
                     "sgp_vehicle_desc", "sgp_vehicle_input", "sgp_vehicle_state", "sgp_hull_info",
@@ -378,7 +390,8 @@ ABI_SIZEOF_APPENDED = ["sgp_shape_query", None, "sgp_shape_cast", "sgp_cast_hit"
                        None, "sgp_character_desc", "sgp_character_input", "sgp_character_state", "sgp_character_contact",
                        None, "sgp_particle", "sgp_particle_state", "sgp_particle_event",      # (29 likewise)
                        None, "sgp_craft_desc", "sgp_craft_input", "sgp_craft_state",          # (33 likewise)
-                       None, "sgp_path_waypoint", "sgp_path_segment", "sgp_path_progress", "sgp_mover_desc", "sgp_mover_state"]      # (37 likewise)
+                       None, "sgp_path_waypoint", "sgp_path_segment", "sgp_path_progress", "sgp_mover_desc", "sgp_mover_state",      # (37 likewise)
+                       None, "sgp_batch_checkpoint_info"]      # (43 likewise)
 ABI_SIZEOF_ALL = ABI_SIZEOF_ORDER + ABI_SIZEOF_APPENDED
 
 STRUCTS = {"sgp_settings": Settings, "sgp_world_desc": WorldDesc, "sgp_body_desc": BodyDesc,
@@ -393,7 +406,7 @@ STRUCTS = {"sgp_settings": Settings, "sgp_world_desc": WorldDesc, "sgp_body_desc
            "sgp_particle": Particle, "sgp_particle_state": ParticleState, "sgp_particle_event": ParticleEvent,
            "sgp_craft_desc": CraftDesc, "sgp_craft_input": CraftInput, "sgp_craft_state": CraftState,
            "sgp_path_waypoint": PathWaypoint, "sgp_path_segment": PathSegment, "sgp_path_progress": PathProgress,
-           "sgp_mover_desc": MoverDesc, "sgp_mover_state": MoverState}
+           "sgp_mover_desc": MoverDesc, "sgp_mover_state": MoverState, "sgp_batch_checkpoint_info": BatchCheckpointInfo}
 
 body_desc_dtype = np.dtype(BodyDesc)
 body_state_dtype = np.dtype(BodyState)
@@ -578,6 +591,17 @@ PROTOTYPES = {
     "checkpoint_write": (C.c_int, [vp, vp, u64, P(u64)]),
     "world_restore": (C.c_int, [vp, vp, u64]),
     "checkpoint_blob_info": (C.c_int, [vp, u64, P(CheckpointInfo)]),
+    # batch checkpoints
+    "characters_checkpoint": (C.c_int, [vp, P(vp)]),
+    "characters_rollback": (C.c_int, [vp, vp]),
+    "particles_checkpoint": (C.c_int, [vp, P(vp)]),
+    "particles_rollback": (C.c_int, [vp, vp]),
+    "crafts_checkpoint": (C.c_int, [vp, P(vp)]),
+    "crafts_rollback": (C.c_int, [vp, vp]),
+    "movers_checkpoint": (C.c_int, [vp, P(vp)]),
+    "movers_rollback": (C.c_int, [vp, vp]),
+    "batch_checkpoint_destroy": (C.c_int, [vp]),
+    "batch_checkpoint_get_info": (C.c_int, [vp, P(BatchCheckpointInfo)]),
     # test/debug helper, not a facade entry point
     "world_dump_constraints": (C.c_int, [vp, vp, u32, P(u32)]),
 }

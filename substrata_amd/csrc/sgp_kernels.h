@@ -637,5 +637,15 @@ void launch_ghost_refresh_records(const DV& d, const sgp_ghost_record* recs, con
 #define SGP_CKPT_MAX_SEGS 160
 struct CkptTable { uint32_t n; uint32_t start[SGP_CKPT_MAX_SEGS + 1]; const void* src[SGP_CKPT_MAX_SEGS]; void* dst[SGP_CKPT_MAX_SEGS]; };
 void launch_ckpt_copy(const CkptTable& t, uint32_t n_cus, hipStream_t s);
+// The same copy for pieces whose length only the device knows (batch checkpoints: the live particles, their events).  Piece i is at most bound[i] units long --
+// the host's bound, which sizes the buffers and the grid --; where count[i] is given, a word of device memory that nothing on the stream ahead of the launch
+// still writes, its length is min(ceil(*count[i] * per[i] / 16), bound[i]) units (per: bytes per counted record), resolved by every workgroup for itself.
+// The bounds add up to less than 2^32 - 2^8 units.
+#define SGP_CKPT_MAX_COUNTED 24
+struct CkptCountedTable {
+	uint32_t n; uint32_t bound[SGP_CKPT_MAX_COUNTED], per[SGP_CKPT_MAX_COUNTED];
+	const uint32_t* count[SGP_CKPT_MAX_COUNTED]; const void* src[SGP_CKPT_MAX_COUNTED]; void* dst[SGP_CKPT_MAX_COUNTED];
+};
+void launch_ckpt_copy_counted(const CkptCountedTable& t, uint32_t n_cus, hipStream_t s);
 // clears what the current broad-phase grid would leave for the next step to clear, and records that nothing is left (rollback / restore)
 void launch_ckpt_grid_reset(const DV& d, hipStream_t s);

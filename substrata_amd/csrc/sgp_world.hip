@@ -86,6 +86,7 @@ SGP_API int sgp_abi_sizeof(int which)
 	case 34: return (int)sizeof(sgp_craft_desc); case 35: return (int)sizeof(sgp_craft_input); case 36: return (int)sizeof(sgp_craft_state);      // (33 stays -1 likewise)
 	case 38: return (int)sizeof(sgp_path_waypoint); case 39: return (int)sizeof(sgp_path_segment); case 40: return (int)sizeof(sgp_path_progress);      // (37 stays -1 likewise)
 	case 41: return (int)sizeof(sgp_mover_desc); case 42: return (int)sizeof(sgp_mover_state);
+	case 44: return (int)sizeof(sgp_batch_checkpoint_info);      // (43 stays -1 likewise)
 	default: return -1;
 	}
 }

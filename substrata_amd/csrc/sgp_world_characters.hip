@@ -11,6 +11,15 @@ struct sgp_characters : WorldBatch {
 	// device
 	CharState* d_st = nullptr; CharContact* d_active = nullptr; uint32_t* d_seen = nullptr;
 	CharPush* d_push = nullptr; uint32_t* d_n_push = nullptr; CharAdded* d_added = nullptr; uint32_t* d_n_added = nullptr;
+	// what a checkpoint holds beyond the rec and in mirrors (d_n_push whole: the push_any word sits behind its last slot)
+	void ckpt_layout(BatchCkptLayout& l)
+	{
+		const uint32_t* n = &slots.high;
+		l.device(d_st, n); l.device(d_active, n, SGP_CHAR_MAX_CONTACTS); l.device(d_seen, n, SGP_CHAR_MAX_CONTACTS);
+		l.device(d_push, n, SGP_CHAR_MAX_PUSHES); l.device_whole(d_n_push, slots.cap + 1u); l.device(d_added, n, SGP_CHAR_MAX_ADDED); l.device(d_n_added, n);
+		l.table(slots);
+		l.capacity = slots.cap; l.high = slots.high; l.n_alive = slots.n_alive;
+	}
 };
 
 static CharBufs chars_bufs(const sgp_characters* cs)
@@ -49,7 +58,7 @@ SGP_API int sgp_characters_create(sgp_world* w, uint32_t capacity, sgp_character
 	sgp_characters* cs = new sgp_characters();
 	const size_t n = capacity;
 	cs->slots.cap = capacity;
-	cs->dv.shape(1, &cs->one); cs->rec.shape(n, &cs->slots.high); cs->in.shape(n, &cs->slots.high);
+	cs->dv.shape(1, &cs->one); cs->dv.state = false; cs->rec.shape(n, &cs->slots.high); cs->in.shape(n, &cs->slots.high);
 	for (uint32_t i = 0; i < capacity; ++i) cs->in[i].ignore = SGP_INVALID_ID;
 	bool ok = cs->adopt(w) && cs->create_mirrors({ &cs->dv, &cs->rec, &cs->in });
 	ok = ok && cs->alloc(cs->d_st, n)
@@ -163,6 +172,9 @@ SGP_API int sgp_characters_update(sgp_characters* cs, float dt)
 	launch_characters_push(w->dv, b, w->stream);
 	return cs->update_end();
 }
+
+SGP_API int sgp_characters_checkpoint(sgp_characters* cs, sgp_batch_checkpoint** io) { return batch_checkpoint(cs, SGP_BATCH_CHARACTERS, "sgp_characters_checkpoint", io); }
+SGP_API int sgp_characters_rollback(sgp_characters* cs, const sgp_batch_checkpoint* cp) { return batch_rollback(cs, SGP_BATCH_CHARACTERS, "sgp_characters_rollback", cp); }
 
 SGP_API int sgp_characters_get_states(sgp_characters* cs, uint32_t first, uint32_t n, sgp_character_state* out)
 {

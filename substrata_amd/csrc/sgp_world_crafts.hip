@@ -10,6 +10,15 @@ struct sgp_crafts : WorldBatch {
 	// device
 	CraftDyn* d_dyn = nullptr; sgp_craft_state* d_st = nullptr;
 	sgp_particle* d_emit = nullptr; sgp_particle* d_dense = nullptr; uint32_t* d_n_emit = nullptr; uint32_t* d_emit_off = nullptr;
+	// what a checkpoint holds beyond the rec and in mirrors (the emit buffers are scratch of one update; `ps` is wiring)
+	void ckpt_layout(BatchCkptLayout& l)
+	{
+		const uint32_t* n = &slots.high;
+		l.device(d_dyn, n); l.device(d_st, n);
+		l.host_array(tag, n);
+		l.table(slots); l.body_links(links, n);
+		l.capacity = slots.cap; l.high = slots.high; l.n_alive = slots.n_alive;
+	}
 };
 
 static CraftBufs crafts_bufs(const sgp_crafts* cs)
@@ -173,6 +182,9 @@ SGP_API int sgp_crafts_update(sgp_crafts* cs, float dt)
 	}
 	return cs->update_end();
 }
+
+SGP_API int sgp_crafts_checkpoint(sgp_crafts* cs, sgp_batch_checkpoint** io) { return batch_checkpoint(cs, SGP_BATCH_CRAFTS, "sgp_crafts_checkpoint", io); }
+SGP_API int sgp_crafts_rollback(sgp_crafts* cs, const sgp_batch_checkpoint* cp) { return batch_rollback(cs, SGP_BATCH_CRAFTS, "sgp_crafts_rollback", cp); }
 
 SGP_API int sgp_crafts_get_states(sgp_crafts* cs, uint32_t first, uint32_t n, sgp_craft_state* out)
 {

@@ -322,7 +322,8 @@ static inline uint32_t body_born_of(const sgp_world* w, uint32_t body) { return 
 
 // One array the host keeps and the device gets when it changed: the host's copy, the device's, where the copy is staged in WorldBatch::h_up, and whether the
 // two differ.  An upload moves the first *count units of `stride` bytes (the records up to the batch's high-water mark, the segments of the paths up to theirs).
-struct BatchMirror { const void* host = nullptr; void* dev = nullptr; size_t stride = 0, bytes = 0, off = 0; const uint32_t* count = nullptr; bool dirty = false; };
+// `state`: a batch checkpoint holds the array (not the characters' copy of the world's DV, which every update brings up to date).
+struct BatchMirror { const void* host = nullptr; void* dev = nullptr; size_t stride = 0, bytes = 0, off = 0; const uint32_t* count = nullptr; bool dirty = false, state = true; };
 template <class T> struct Mirror : BatchMirror {
 	std::vector<T> h;
 	void shape(size_t units, const uint32_t* count_, size_t per = 1)      // `units` zeroed units of `per` records each
@@ -338,20 +339,24 @@ template <class T> struct Mirror : BatchMirror {
 // Who owns the batch; device arrays zeroed on the world's stream; the uploaded mirrors and their pinned upload buffer with its fence -- `uploaded` is recorded
 // behind the copies that read the buffer and waited for before the buffer is written again, so that add, update and clear never wait for the stream --; the
 // two ends of an update; the release sequence.  (batch_created, batch_destroy, batch_update_admit and batch_read_states, below, are the rest of the skeletons.)
+uint64_t batch_next_serial();      // defined in sgp_world_batch_checkpoint.hip
 struct WorldBatch {
 	sgp_world* w = nullptr; uint64_t world_serial = 0; int device = 0;
 	std::vector<void*> dev;      // the device arrays of alloc(), freed by release()
 	std::vector<BatchMirror*> mirrors;      // in the order they are uploaded
 	char* h_up = nullptr; hipEvent_t uploaded = nullptr; bool upload_in_flight = false;
 
+	uint64_t serial = 0;         // no other batch of this process has it: what a batch checkpoint knows its batch by (an address may be handed out again)
+
 	bool usable() const { return w && world_alive(world_serial); }
 	bool adopt(sgp_world* world)
 	{
-		w = world; world_serial = world->serial; device = world->device;
+		w = world; world_serial = world->serial; device = world->device; serial = batch_next_serial();
 		return hipEventCreateWithFlags(&uploaded, hipEventDisableTiming) == hipSuccess;
 	}
 	bool alloc_bytes(void** p, size_t bytes)
 	{
+		bytes = (bytes + 15) & ~size_t(15);      // (whole 16-byte units: a checkpoint copies an array's used part rounded up to one)
 		if (hipMalloc(p, bytes) != hipSuccess) { *p = nullptr; return false; }
 		dev.push_back(*p);
 		return hipMemsetAsync(*p, 0, bytes, w->stream) == hipSuccess;
@@ -376,7 +381,8 @@ struct WorldBatch {
 	int upload_begin() { if (upload_in_flight) { HIP_TRY(hipEventSynchronize(uploaded)); upload_in_flight = false; } return SGP_OK; }      // before h_up is written
 	int upload_end() { HIP_TRY(hipEventRecord(uploaded, w->stream)); upload_in_flight = true; return SGP_OK; }                              // behind the copies that read it
 	// what changed on the host -> the device, behind whatever the stream holds (no wait for the stream; only for the previous upload to have left the staging buffer)
-	int upload()
+	// (keep_dirty: a capture's upload -- the device has the host's records, and whoever looks at the flags later finds them as they were)
+	int upload(bool keep_dirty = false)
 	{
 		bool any = false;
 		for (const BatchMirror* m : mirrors) any = any || m->dirty;
@@ -388,7 +394,7 @@ struct WorldBatch {
 			memcpy(h_up + m->off, m->host, n);
 			HIP_TRY(hipMemcpyAsync(m->dev, h_up + m->off, n, hipMemcpyHostToDevice, w->stream));
 		}
-		for (BatchMirror* m : mirrors) m->dirty = false;
+		if (!keep_dirty) for (BatchMirror* m : mirrors) m->dirty = false;
 		return upload_end();
 	}
 	// an update of characters, crafts or movers that has something to launch: the mirrors go up, and the event counters are emptied if the host has pulled the
@@ -416,6 +422,43 @@ struct WorldBatch {
 	}
 };
 static inline bool batch_usable(const WorldBatch* b) { return b && b->usable(); }
+
+// ---- batch checkpoints (sgp_world_batch_checkpoint.hip; docs/CONTRACT.md, "Batch checkpoints") ---------------------------------------------------------------
+// What a batch says of itself for a capture or a rollback: its state beyond the mirrors, which WorldBatch knows already.  Every sgp_world_<batch>.hip has one
+// ckpt_layout() that lists
+//   device   an array of the device, `*count` records of `stride` bytes of it in use (count == NULL: `n` records, as many at every capture)
+//   counted  an array whose used part is a word of device memory: at most `bound` records of `per` bytes, and the word sits `word_off` bytes into the device
+//            piece listed as number `word_piece` (the particles' PsState) -- in the batch at a capture, in the checkpoint's own copy at a rollback
+//   host     an array of the host, `*count` records of it in use
+//   scalar   a plain value of the host
+//   slots, links   the tables of sgp_batch_slots.h
+// and the counts sgp_batch_checkpoint_get_info reports.  Records beyond a count hold zeroes (as allocated), and a rollback over a count that has grown since
+// the capture makes them so again, on the device and on the host.
+struct BatchCkptLayout {
+	struct Dev { void* p; size_t stride; const uint32_t* count; uint32_t n; int word_piece; uint32_t word_off; };
+	struct Host { void* p; size_t stride; const uint32_t* count; };
+	std::vector<Dev> dev; std::vector<Host> host; std::vector<std::pair<void*, size_t>> scalars;
+	std::vector<BatchSlots*> slots; BodyLinks* links = nullptr; const uint32_t* links_high = nullptr;
+	uint32_t capacity = 0, high = 0, n_alive = 0;
+	template <class T> void device(T* p, const uint32_t* count, size_t per = 1) { dev.push_back(Dev{ (void*)p, sizeof(T) * per, count, 0u, -1, 0u }); }
+	template <class T> void device_whole(T* p, uint32_t n) { dev.push_back(Dev{ (void*)p, sizeof(T), nullptr, n, -1, 0u }); }
+	template <class T> void counted(T* p, size_t per, uint32_t bound, int word_piece, uint32_t word_off) { dev.push_back(Dev{ (void*)p, sizeof(T) * per, nullptr, bound, word_piece, word_off }); }
+	template <class T> void host_array(std::vector<T>& v, const uint32_t* count) { host.push_back(Host{ (void*)v.data(), sizeof(T), count }); }
+	template <class T> void scalar(T& v) { scalars.push_back({ (void*)&v, sizeof(T) }); }
+	void table(BatchSlots& s) { slots.push_back(&s); }
+	void body_links(BodyLinks& l, const uint32_t* high_) { links = &l; links_high = high_; }
+};
+typedef void (*BatchLayoutFn)(WorldBatch*, BatchCkptLayout&);
+int batch_checkpoint_capture(WorldBatch* b, uint32_t kind, const char* fn, BatchLayoutFn layout, sgp_batch_checkpoint** io);
+int batch_checkpoint_rollback(WorldBatch* b, uint32_t kind, const char* fn, BatchLayoutFn layout, const sgp_batch_checkpoint* cp);
+template <class B> inline int batch_checkpoint(B* b, uint32_t kind, const char* fn, sgp_batch_checkpoint** io)
+{
+	return batch_checkpoint_capture(b, kind, fn, [](WorldBatch* wb, BatchCkptLayout& l) { static_cast<B*>(wb)->ckpt_layout(l); }, io);
+}
+template <class B> inline int batch_rollback(B* b, uint32_t kind, const char* fn, const sgp_batch_checkpoint* cp)
+{
+	return batch_checkpoint_rollback(b, kind, fn, [](WorldBatch* wb, BatchCkptLayout& l) { static_cast<B*>(wb)->ckpt_layout(l); }, cp);
+}
 
 // the end of every *_create (`ok`: adopt, the allocations and the pinning all succeeded) and the whole of every *_destroy
 template <class B> inline int batch_created(B* b, bool ok, B** out, const char* fn)

@@ -13,6 +13,16 @@ struct sgp_movers : WorldBatch {
 	std::vector<MoverPath> paths; Mirror<sgp_path_segment> segs; Mirror<uint32_t> path_n;      // (segs and path_n change together)
 	// device
 	MoverDyn* d_dyn = nullptr; sgp_mover_state* d_st = nullptr; uint2* d_pub = nullptr;
+	// what a checkpoint holds beyond the segs, path_n and rec mirrors
+	void ckpt_layout(BatchCkptLayout& l)
+	{
+		const uint32_t* n = &slots.high;
+		l.device(d_dyn, n); l.device(d_st, n); l.device(d_pub, n);
+		l.host_array(leader_serial, n); l.host_array(tag, n); l.host_array(fresh, n); l.host_array(paths, &path_slots.high);
+		l.scalar(n_followers);
+		l.table(slots); l.table(path_slots); l.body_links(links, n);
+		l.capacity = slots.cap; l.high = slots.high; l.n_alive = slots.n_alive;
+	}
 };
 
 static MoverBufs movers_bufs(const sgp_movers* ms)
@@ -214,6 +224,9 @@ SGP_API int sgp_movers_update(sgp_movers* ms, float dt)
 	std::fill(ms->fresh.begin(), ms->fresh.begin() + ms->slots.high, (uint8_t)0);
 	return ms->update_end();
 }
+
+SGP_API int sgp_movers_checkpoint(sgp_movers* ms, sgp_batch_checkpoint** io) { return batch_checkpoint(ms, SGP_BATCH_MOVERS, "sgp_movers_checkpoint", io); }
+SGP_API int sgp_movers_rollback(sgp_movers* ms, const sgp_batch_checkpoint* cp) { return batch_rollback(ms, SGP_BATCH_MOVERS, "sgp_movers_rollback", cp); }
 
 SGP_API int sgp_movers_get_states(sgp_movers* ms, uint32_t first, uint32_t n, sgp_mover_state* out)
 {

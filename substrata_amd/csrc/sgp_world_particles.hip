@@ -14,6 +14,15 @@ struct sgp_particles : WorldBatch {
 	// the device copy of the newcomers' pinned staging (WorldBatch::h_up): up_cap records each, both grown by add
 	sgp_particle* d_up = nullptr; uint32_t up_cap = 0;
 	~sgp_particles() { if (d_up) hipFree(d_up); if (h_st) hipHostFree(h_st); }      // (behind WorldBatch::release, which has waited for the stream)
+	// what a checkpoint holds: the counts, and as much of the current copy and of the event list as the counts say -- the host knows neither without a read
+	void ckpt_layout(BatchCkptLayout& l)
+	{
+		l.device_whole(b.st, 1u);
+		l.counted(b.hot[cur], 2, upper, 0, offsetof(PsState, n_live)); l.counted(b.cold[cur], 2, upper, 0, offsetof(PsState, n_live));
+		l.counted(b.events, 1, ev_cap, 0, offsetof(PsState, n_events));
+		l.scalar(cur); l.scalar(upper);
+		l.capacity = cap; l.high = upper; l.n_alive = upper;
+	}
 };
 
 SGP_API void sgp_default_particle(sgp_particle* p)
@@ -129,6 +138,14 @@ SGP_API int sgp_particles_clear(sgp_particles* ps)
 	HIP_TRY(hipMemsetAsync(ps->b.st, 0, 2 * sizeof(uint32_t), w->stream));      // n_live, cursor
 	ps->upper = 0; ps->st_known = false;
 	return SGP_OK;
+}
+
+SGP_API int sgp_particles_checkpoint(sgp_particles* ps, sgp_batch_checkpoint** io) { return batch_checkpoint(ps, SGP_BATCH_PARTICLES, "sgp_particles_checkpoint", io); }
+SGP_API int sgp_particles_rollback(sgp_particles* ps, const sgp_batch_checkpoint* cp)
+{
+	const int r = batch_rollback(ps, SGP_BATCH_PARTICLES, "sgp_particles_rollback", cp);
+	if (r == SGP_OK) ps->st_known = false;      // (what the last read learned of the counts is of the abandoned history)
+	return r;
 }
 
 SGP_API int sgp_particles_read(sgp_particles* ps, sgp_particle_state* out, uint32_t cap, uint32_t* n_out)

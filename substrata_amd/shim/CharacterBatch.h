@@ -8,6 +8,7 @@
 // update() enqueues the work on the world's stream and returns; readBack() waits and fetches the states the getters then answer from.
 #pragma once
 #include "Jolt/JoltCharacterLite.h"
+#include "BatchCheckpoint.h"
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -103,6 +104,20 @@ public:
 		out.resize(std::min<size_t>(n, out.size()));
 	}
 	sgp_characters* handle() const { return batch; }
+
+	// Extensions (not in the reference): the batch as it is now, to come back to after PhysicsWorld's rollback to the checkpoint of the same moment -- the
+	// library's state and, with it, the inputs set here and not sent yet and what the last readBack() fetched.
+	struct SavedState { BatchCheckpoint lib; std::vector<sgp_character_input> inputs; std::vector<sgp_character_state> states; std::vector<uint8_t> dirty; uint32_t used = 0; bool inputs_dirty = false; };
+	void saveState(SavedState& s)
+	{
+		check(sgp_characters_checkpoint(batch, &s.lib.cp), "sgp_characters_checkpoint");
+		s.inputs = inputs; s.states = states; s.dirty = dirty; s.used = used; s.inputs_dirty = inputs_dirty;
+	}
+	void restoreState(const SavedState& s)
+	{
+		check(sgp_characters_rollback(batch, s.lib.cp), "sgp_characters_rollback");
+		inputs = s.inputs; states = s.states; dirty = s.dirty; used = s.used; inputs_dirty = s.inputs_dirty;
+	}
 
 private:
 	static void set3(float* d, const JPH::Vec3& v) { d[0] = v.x; d[1] = v.y; d[2] = v.z; }

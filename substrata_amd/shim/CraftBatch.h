@@ -161,6 +161,21 @@ public:
 	uint32_t capacity() const { return cap; }
 	sgp_crafts* handle() const { return batch; }
 
+	// Extensions (not in the reference): the batch as it is now, to come back to after PhysicsWorld's rollback to the checkpoint of the same moment -- the
+	// library's state and, with it, the inputs set here and not sent yet and what the last readBack() fetched.  The attached ParticleBatch is saved and restored
+	// by its own pair; which one is attached is not state.
+	struct SavedState { BatchCheckpoint lib; std::vector<sgp_craft_input> inputs; std::vector<uint32_t> kinds; std::vector<sgp_craft_state> states; uint32_t high = 0; bool dirty = false; };
+	void saveState(SavedState& s)
+	{
+		check(sgp_crafts_checkpoint(batch, &s.lib.cp), "sgp_crafts_checkpoint");
+		s.inputs = inputs; s.kinds = kinds; s.states = states; s.high = high; s.dirty = dirty;
+	}
+	void restoreState(const SavedState& s)
+	{
+		check(sgp_crafts_rollback(batch, s.lib.cp), "sgp_crafts_rollback");
+		inputs = s.inputs; kinds = s.kinds; states = s.states; high = s.high; dirty = s.dirty;
+	}
+
 private:
 	static void check(int rc, const char* what) { if (rc != SGP_OK) throw std::runtime_error(std::string(what) + ": " + sgp_last_error()); }
 	static void setRotations(sgp_craft_desc& d, const CraftScriptSettings& s)

@@ -9,6 +9,7 @@
 #pragma once
 #include "../../include/sgp.h"
 #include "PhysicsWorld.h"
+#include "BatchCheckpoint.h"
 #include "maths/Quat.h"
 #include "maths/Vec4f.h"
 #include <algorithm>
@@ -220,6 +221,24 @@ private:
 		}
 		world->setNewObToWorldTransform(ob, new_pos, new_rot, /*linear vel=*/Vec4f(0.f), /*angular vel=*/Vec4f(0.f));
 	}
+
+public:
+	// Extensions (not in the reference): the batch as it is now, to come back to after PhysicsWorld's rollback to the checkpoint of the same moment -- the
+	// library's state and, with it, what this header keeps on the host: the controllers (a follower that still waits for its leader waits again, one that was
+	// added since is forgotten; the tracks of the move-to controllers of static bodies with their clocks) and the table of shared paths.
+	struct SavedState { BatchCheckpoint lib; std::vector<Controller> controllers; std::map<std::string, uint32_t> paths; std::vector<sgp_mover_state> states; };
+	void saveState(SavedState& s)
+	{
+		check(sgp_movers_checkpoint(batch, &s.lib.cp), "sgp_movers_checkpoint");
+		s.controllers = controllers; s.paths = paths; s.states = states;
+	}
+	void restoreState(const SavedState& s)
+	{
+		check(sgp_movers_rollback(batch, s.lib.cp), "sgp_movers_rollback");
+		controllers = s.controllers; paths = s.paths; states = s.states;
+	}
+
+private:
 
 	PhysicsWorld* world;
 	sgp_movers* batch;

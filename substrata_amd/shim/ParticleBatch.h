@@ -10,6 +10,7 @@
 #pragma once
 #include "../../include/sgp.h"
 #include "Jolt/JoltLite.h"
+#include "BatchCheckpoint.h"
 #include "maths/Vec4f.h"
 #include <algorithm>
 #include <stdexcept>
@@ -88,6 +89,20 @@ public:
 	const std::vector<sgp_particle_event>& events() const { return evs; }         // since the previous readBack(), in order
 	uint32_t eventsDropped() const { return dropped; }                            // ... and how many did not fit event_capacity
 	sgp_particles* handle() const { return batch; }
+
+	// Extensions (not in the reference): the batch as it is now, to come back to after PhysicsWorld's rollback to the checkpoint of the same moment -- the
+	// library's state and, with it, the particles queued here and not sent yet and what the last readBack() fetched.  Nothing is sent or waited for.
+	struct SavedState { BatchCheckpoint lib; std::vector<sgp_particle> pending; std::vector<sgp_particle_state> states; std::vector<sgp_particle_event> evs; uint32_t dropped = 0; };
+	void saveState(SavedState& s)
+	{
+		check(sgp_particles_checkpoint(batch, &s.lib.cp), "sgp_particles_checkpoint");
+		s.pending = pending; s.states = states; s.evs = evs; s.dropped = dropped;
+	}
+	void restoreState(const SavedState& s)
+	{
+		check(sgp_particles_rollback(batch, s.lib.cp), "sgp_particles_rollback");
+		pending = s.pending; states = s.states; evs = s.evs; dropped = s.dropped;
+	}
 
 private:
 	static void check(int rc, const char* what) { if (rc != SGP_OK) throw std::runtime_error(std::string(what) + ": " + sgp_last_error()); }

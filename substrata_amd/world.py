@@ -63,6 +63,33 @@ class _Batch(_Owned):
         self._w._check(self._w._fn(self._stem + "_get_states")(self._h, int(first), n, out.ctypes.data), self._stem + "_get_states")
         return out
 
+    def checkpoint(self, cp=None):
+        """Captures the batch's state; cp: a BatchCheckpoint of this batch to overwrite in place (its buffers are re-used).  Enqueues and returns."""
+        if cp is None:
+            h = C.c_void_p()
+            self._w._check(self._w._fn(self._stem + "_checkpoint")(self._h, C.byref(h)), self._stem + "_checkpoint")
+            return BatchCheckpoint(self._w, h)
+        if not cp._h:
+            raise SgpError("checkpoint: the BatchCheckpoint to overwrite has been closed")
+        self._w._check(self._w._fn(self._stem + "_checkpoint")(self._h, C.byref(cp._h)), self._stem + "_checkpoint")
+        return cp
+
+    def rollback(self, cp):
+        """The batch becomes what it was when cp was captured; pair it with CWorld.rollback to the checkpoint of the same moment."""
+        if not cp._h:
+            raise SgpError("rollback: the BatchCheckpoint has been closed")
+        self._w._check(self._w._fn(self._stem + "_rollback")(self._h, cp._h), self._stem + "_rollback")
+
+
+class BatchCheckpoint(_Owned):
+    """A captured state of one batch (sgp_batch_checkpoint): owns device and host memory, belongs to the batch that made it."""
+    _stem = "batch_checkpoint"
+
+    def info(self):
+        i = abi.BatchCheckpointInfo()
+        self._w._check(self._w._fn("batch_checkpoint_get_info")(self._h, C.byref(i)), "batch_checkpoint_get_info")
+        return i.as_dict()
+
 
 class Checkpoint(_Owned):
     """A captured world state (sgp_checkpoint): owns device and host memory, belongs to the world that made it."""
