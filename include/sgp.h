@@ -1255,6 +1255,106 @@ int  sgp_movers_rollback(sgp_movers* ms, const sgp_batch_checkpoint* cp);
 int  sgp_batch_checkpoint_destroy(sgp_batch_checkpoint* cp);      /* NULL: SGP_OK */
 int  sgp_batch_checkpoint_get_info(const sgp_batch_checkpoint* cp, sgp_batch_checkpoint_info* out);
 
+/* ---- batched proximity and zone watchers (ScriptedObjectProximityChecker, the parcel enter / exit events of GUIClient) ----
+ * A batch of watched objects, up to SGP_PROX_MAX_OBSERVERS observers and a table of zones (parcels) that belongs to one world and lives on
+ * the device.  sgp_proximity_update runs ScriptedObjectProximityChecker::think (ScriptedObjectProximityChecker.cpp:40-90) for every observer
+ * against every watched object, a lane per object, on the bounds the last step or edit flush left in the world (the PHYSICS body's AABB), and
+ * the parcel bookkeeping of GUIClient.cpp:6874-6968 for every observer: which zone it stands in, and for the objects whose centroid lies in
+ * the zone it left or entered an EXITED or ENTERED event.  The near bit of every (object, observer) pair and every observer's zone stay on
+ * the device between updates; only transitions become events.  The arithmetic is written out in docs/CONTRACT.md 4l.  Departures from the
+ * reference: docs/GAPS.md ("Proximity watchers").  A world checkpoint holds nothing of a batch (sgp_proximity_checkpoint / _rollback do, by
+ * the rule of the batch checkpoints above, with SGP_BATCH_PROXIMITY); tiled worlds are refused. */
+typedef struct sgp_proximity sgp_proximity;
+#define SGP_BATCH_PROXIMITY 5u
+#define SGP_PROX_MAX_OBSERVERS 32
+#define SGP_PROXIMITY_MAX_OBJECTS (1u << 20)
+#define SGP_PROXIMITY_MAX_ZONES   (1u << 12)
+#define SGP_PROX_WANT_NEAR 1u         /* onUserMovedNearToObject / onUserMovedAwayFromObject are wanted                        */
+#define SGP_PROX_WANT_ZONE 2u         /* onUserEnteredParcel / onUserExitedParcel are wanted                                   */
+#define SGP_PROX_OBS_POINT 0u         /* the observer is where the host puts it                                                */
+#define SGP_PROX_OBS_BODY  1u         /* the observer is a body's position plus a world-space offset, read on the device       */
+#define SGP_PROX_ST_BODY_GONE 1u      /* the body is no longer the one the object was added on: the object is skipped          */
+#define SGP_PROX_OBS_ST_BODY_GONE 1u  /* a body-sourced observer whose body has gone: it is no longer updated and fires nothing */
+#define SGP_PROX_EV_NEAR    1u        /* onUserMovedNearToObject                                                               */
+#define SGP_PROX_EV_AWAY    2u        /* onUserMovedAwayFromObject                                                             */
+#define SGP_PROX_EV_EXITED  3u        /* onUserExitedParcel (object == SGP_INVALID_ID: the observer left the zone)             */
+#define SGP_PROX_EV_ENTERED 4u        /* onUserEnteredParcel (object == SGP_INVALID_ID: UserEnteredParcelMessage)              */
+typedef struct sgp_proximity_object {
+	uint32_t body;                 /* a live body of any motion type: no compound, ghost or alias slot, no other object of the batch on it */
+	float    radius;               /* finite, > 0 (the reference: 20)                                                   */
+	uint32_t flags;                /* SGP_PROX_WANT_*                                                                   */
+	uint32_t reserved_;
+	uint64_t tag;                  /* the caller's WorldObject*: not interpreted, reported with every event              */
+} sgp_proximity_object;
+typedef struct sgp_proximity_observer {
+	uint32_t source;               /* SGP_PROX_OBS_POINT | SGP_PROX_OBS_BODY                                            */
+	uint32_t body;                 /* BODY: a live body (no compound, ghost or alias slot)                              */
+	float    pos[3];               /* POINT: where the observer is                                                      */
+	float    offset[3];            /* BODY: added to the body's position, in world space                                */
+} sgp_proximity_observer;
+typedef struct sgp_proximity_event {
+	uint32_t kind;                 /* SGP_PROX_EV_*                                                                     */
+	uint32_t object;               /* the object's id, or SGP_INVALID_ID in an observer-level zone record               */
+	uint32_t observer;
+	uint32_t zone_key;             /* EXITED / ENTERED: the zone's key; else SGP_INVALID_ID                             */
+	uint64_t tag;                  /* the object's (0 in an observer-level record)                                      */
+	uint32_t update_index;         /* the update of the batch that raised it, counted from 0                            */
+	uint32_t reserved_;
+} sgp_proximity_event;
+typedef struct sgp_proximity_state {
+	uint32_t status;               /* SGP_PROX_ST_*                                                                     */
+	uint32_t near_mask;            /* bit k: observer k was within the radius at the last update that tested it         */
+} sgp_proximity_state;
+typedef struct sgp_proximity_observer_state {
+	float    pos[3];               /* where the last update found the observer                                          */
+	uint32_t zone_key;             /* the zone it stands in, or SGP_INVALID_ID                                          */
+	uint32_t update_index;         /* updates this observer has run                                                     */
+	uint32_t status;               /* SGP_PROX_OBS_ST_*                                                                 */
+} sgp_proximity_observer_state;
+/* object_capacity in 1 .. SGP_PROXIMITY_MAX_OBJECTS, zone_capacity in 1 .. SGP_PROXIMITY_MAX_ZONES, event_capacity >= 1: event records the
+ * batch holds between two drains.  SGP_ERR_INVALID for a world that holds ghost bodies. */
+int  sgp_proximity_create(sgp_world* w, uint32_t object_capacity, uint32_t zone_capacity, uint32_t event_capacity, sgp_proximity** out);
+/* After sgp_world_destroy of its world this still frees the batch and returns SGP_OK; every other call on such a batch is SGP_ERR_INVALID. */
+int  sgp_proximity_destroy(sgp_proximity* pb);
+/* n objects at once, all or none: ids_out[i] is the id of descs[i].  A new object is near nobody.  SGP_ERR_INVALID, with nothing added, for a
+ * radius that is not finite and > 0, an unknown flag, a body that does not qualify, carries an object of the batch already or is named
+ * twice; SGP_ERR_CAPACITY when the n do not all fit. */
+int  sgp_proximity_add(sgp_proximity* pb, const sgp_proximity_object* descs, uint32_t n, uint32_t* ids_out);
+int  sgp_proximity_remove(sgp_proximity* pb, uint32_t id);      /* fires nothing */
+/* The want flags of a live object.  The near mask is not touched: a transition that passed while the flag was off is not replayed. */
+int  sgp_proximity_set_flags(sgp_proximity* pb, uint32_t id, uint32_t flags);
+/* Observer k < SGP_PROX_MAX_OBSERVERS.  A slot that held no observer gets a NEW one: near nothing and in no zone, so that its first update
+ * fires NEAR for everything in range and ENTERED for its zone (in_script_proximity = false, an invalid cur_in_parcel_id).  On a slot that
+ * holds one, only the source changes.  SGP_ERR_INVALID for a non-finite value, an unknown source, a body that does not qualify. */
+int  sgp_proximity_set_observer(sgp_proximity* pb, uint32_t k, const sgp_proximity_observer* obs);
+/* Moves POINT observers first .. first + n - 1 (all must be live POINT observers): a host write, uploaded by the next update. */
+int  sgp_proximity_set_points(sgp_proximity* pb, uint32_t first, uint32_t n, const float* xyz);
+/* Clears the observer's bit in every near mask and forgets its zone; fires no events. */
+int  sgp_proximity_remove_observer(sgp_proximity* pb, uint32_t k);
+/* Bounds are fp32, mn <= mx and finite; `key` is unique among the live zones (the ParcelID: among the zones that contain a point the lowest
+ * key wins).  A zone slot carries a generation: an observer that stood in a removed zone sees it as gone even when the slot is refilled. */
+int  sgp_proximity_zone_add(sgp_proximity* pb, const float mn[3], const float mx[3], uint32_t key, uint32_t* zone_id_out);
+int  sgp_proximity_zone_remove(sgp_proximity* pb, uint32_t zone_id);
+/* One update: flushes pending body edits, uploads what the host changed and enqueues four launches on the world's stream -- no wait, no copy
+ * to the host, no allocation.  Nothing is launched while the batch has no live object or no live observer.  No body and nothing a step
+ * reads is altered. */
+int  sgp_proximity_update(sgp_proximity* pb);
+/* The events since the last drain in the order of the updates that raised them; within one update first the observer-level zone records by
+ * ascending observer, EXITED before ENTERED, then the objects' events by ascending object id, then ascending observer, then kind (NEAR or
+ * AWAY, EXITED, ENTERED).  Waits.  *n_out = records held (<= cap are written; all are consumed), *n_dropped = events that did not fit
+ * event_capacity since the last drain: always the LAST of that order. */
+int  sgp_proximity_drain_events(sgp_proximity* pb, sgp_proximity_event* out, uint32_t cap, uint32_t* n_out, uint32_t* n_dropped);
+/* Waits for the updates in flight.  Slots that are not live read as zeroes. */
+int  sgp_proximity_get_states(sgp_proximity* pb, uint32_t first, uint32_t n, sgp_proximity_state* out);
+int  sgp_proximity_get_observers(sgp_proximity* pb, uint32_t first, uint32_t n, sgp_proximity_observer_state* out);
+int  sgp_proximity_checkpoint(sgp_proximity* pb, sgp_batch_checkpoint** io);
+int  sgp_proximity_rollback(sgp_proximity* pb, const sgp_batch_checkpoint* cp);
+/* The arithmetic of an update on the host, bit-equal to the device (no world, no device).  test_point: closest point of the box [mn, mx] to p,
+ * *dist2_out = the squared distance, *near_out = dist2 < radius * radius.  pick_zone: `current` (an index < n, or SGP_INVALID_ID) stays if it is
+ * live and contains p; else the live zone of the lowest key that contains p; else SGP_INVALID_ID.  mins / maxs: n * 3 floats; live: n words. */
+int  sgp_proximity_test_point(const float mn[3], const float mx[3], const float p[3], float radius, uint32_t* near_out, float* dist2_out);
+int  sgp_proximity_pick_zone(const float* mins, const float* maxs, const uint32_t* keys, const uint32_t* live, uint32_t n, uint32_t current, const float p[3], uint32_t* zone_out);
+
 #ifdef __cplusplus
 }
 #endif

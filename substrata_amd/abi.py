@@ -346,6 +346,36 @@ class MoverState(C.Structure):
                 ("rot", f32 * 4), ("dir", f32 * 3), ("pos_elapsed", f32), ("rot_elapsed", f32), ("update_index", u32)]
 
 
+PROX_MAX_OBSERVERS, PROXIMITY_MAX_OBJECTS, PROXIMITY_MAX_ZONES = 32, 1 << 20, 1 << 12      # SGP_PROX_MAX_OBSERVERS, SGP_PROXIMITY_MAX_*
+PROX_WANT_NEAR, PROX_WANT_ZONE = 1, 2                                     # SGP_PROX_WANT_*
+PROX_OBS_POINT, PROX_OBS_BODY = 0, 1                                      # SGP_PROX_OBS_*
+PROX_ST_BODY_GONE, PROX_OBS_ST_BODY_GONE = 1, 1
+PROX_EV = {"NEAR": 1, "AWAY": 2, "EXITED": 3, "ENTERED": 4}               # SGP_PROX_EV_*
+
+
+class ProximityObject(C.Structure):
+    """sgp_proximity_object: one watched object of a proximity batch."""
+    _fields_ = [("body", u32), ("radius", f32), ("flags", u32), ("reserved_", u32), ("tag", u64)]
+
+
+class ProximityObserver(C.Structure):
+    """sgp_proximity_observer: where an observer is -- a point of the host, or a body plus a world-space offset."""
+    _fields_ = [("source", u32), ("body", u32), ("pos", f32 * 3), ("offset", f32 * 3)]
+
+
+class ProximityEvent(C.Structure):
+    """sgp_proximity_event: NEAR / AWAY / EXITED / ENTERED of one (object, observer) pair, or an observer-level zone record."""
+    _fields_ = [("kind", u32), ("object", u32), ("observer", u32), ("zone_key", u32), ("tag", u64), ("update_index", u32), ("reserved_", u32)]
+
+
+class ProximityState(C.Structure):
+    _fields_ = [("status", u32), ("near_mask", u32)]
+
+
+class ProximityObserverState(C.Structure):
+    _fields_ = [("pos", f32 * 3), ("zone_key", u32), ("update_index", u32), ("status", u32)]
+
+
 class CompoundChild(C.Structure):
     _fields_ = [("shape_type", i32), ("shape", f32 * 4), ("pos", f32 * 3), ("rot", f32 * 4)]
 
@@ -366,7 +396,7 @@ class CheckpointInfo(C.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
-BATCH_CHARACTERS, BATCH_PARTICLES, BATCH_CRAFTS, BATCH_MOVERS = 1, 2, 3, 4
+BATCH_CHARACTERS, BATCH_PARTICLES, BATCH_CRAFTS, BATCH_MOVERS, BATCH_PROXIMITY = 1, 2, 3, 4, 5
 
 
 class BatchCheckpointInfo(C.Structure):
@@ -391,7 +421,9 @@ ABI_SIZEOF_APPENDED = ["sgp_shape_query", None, "sgp_shape_cast", "sgp_cast_hit"
                        None, "sgp_particle", "sgp_particle_state", "sgp_particle_event",      # (29 likewise)
                        None, "sgp_craft_desc", "sgp_craft_input", "sgp_craft_state",          # (33 likewise)
                        None, "sgp_path_waypoint", "sgp_path_segment", "sgp_path_progress", "sgp_mover_desc", "sgp_mover_state",      # (37 likewise)
-                       None, "sgp_batch_checkpoint_info"]      # (43 likewise)
+                       None, "sgp_batch_checkpoint_info",      # (43 likewise)
+                       None, "sgp_proximity_object", "sgp_proximity_observer", "sgp_proximity_event", "sgp_proximity_state",      # (45 likewise)
+                       "sgp_proximity_observer_state"]
 ABI_SIZEOF_ALL = ABI_SIZEOF_ORDER + ABI_SIZEOF_APPENDED
 
 STRUCTS = {"sgp_settings": Settings, "sgp_world_desc": WorldDesc, "sgp_body_desc": BodyDesc,
@@ -406,7 +438,9 @@ STRUCTS = {"sgp_settings": Settings, "sgp_world_desc": WorldDesc, "sgp_body_desc
            "sgp_particle": Particle, "sgp_particle_state": ParticleState, "sgp_particle_event": ParticleEvent,
            "sgp_craft_desc": CraftDesc, "sgp_craft_input": CraftInput, "sgp_craft_state": CraftState,
            "sgp_path_waypoint": PathWaypoint, "sgp_path_segment": PathSegment, "sgp_path_progress": PathProgress,
-           "sgp_mover_desc": MoverDesc, "sgp_mover_state": MoverState, "sgp_batch_checkpoint_info": BatchCheckpointInfo}
+           "sgp_mover_desc": MoverDesc, "sgp_mover_state": MoverState, "sgp_batch_checkpoint_info": BatchCheckpointInfo,
+           "sgp_proximity_object": ProximityObject, "sgp_proximity_observer": ProximityObserver, "sgp_proximity_event": ProximityEvent,
+           "sgp_proximity_state": ProximityState, "sgp_proximity_observer_state": ProximityObserverState}
 
 body_desc_dtype = np.dtype(BodyDesc)
 body_state_dtype = np.dtype(BodyState)
@@ -437,6 +471,10 @@ craft_state_dtype = np.dtype(CraftState)
 path_waypoint_dtype = np.dtype(PathWaypoint)
 path_segment_dtype = np.dtype(PathSegment)
 mover_state_dtype = np.dtype(MoverState)
+proximity_object_dtype = np.dtype(ProximityObject)
+proximity_event_dtype = np.dtype(ProximityEvent)
+proximity_state_dtype = np.dtype(ProximityState)
+proximity_observer_state_dtype = np.dtype(ProximityObserverState)
 compound_child_dtype = np.dtype(CompoundChild)
 migration_dtype = np.dtype(Migration)
 
@@ -598,6 +636,24 @@ PROTOTYPES = {
     "particles_rollback": (C.c_int, [vp, vp]),
     "crafts_checkpoint": (C.c_int, [vp, P(vp)]),
     "crafts_rollback": (C.c_int, [vp, vp]),
+    "proximity_create": (C.c_int, [vp, u32, u32, u32, P(vp)]),
+    "proximity_destroy": (C.c_int, [vp]),
+    "proximity_add": (C.c_int, [vp, vp, u32, vp]),
+    "proximity_remove": (C.c_int, [vp, u32]),
+    "proximity_set_flags": (C.c_int, [vp, u32, u32]),
+    "proximity_set_observer": (C.c_int, [vp, u32, P(ProximityObserver)]),
+    "proximity_set_points": (C.c_int, [vp, u32, u32, vp]),
+    "proximity_remove_observer": (C.c_int, [vp, u32]),
+    "proximity_zone_add": (C.c_int, [vp, P(f32), P(f32), u32, P(u32)]),
+    "proximity_zone_remove": (C.c_int, [vp, u32]),
+    "proximity_update": (C.c_int, [vp]),
+    "proximity_drain_events": (C.c_int, [vp, vp, u32, P(u32), P(u32)]),
+    "proximity_get_states": (C.c_int, [vp, u32, u32, vp]),
+    "proximity_get_observers": (C.c_int, [vp, u32, u32, vp]),
+    "proximity_checkpoint": (C.c_int, [vp, P(vp)]),
+    "proximity_rollback": (C.c_int, [vp, vp]),
+    "proximity_test_point": (C.c_int, [P(f32), P(f32), P(f32), f32, P(u32), P(f32)]),
+    "proximity_pick_zone": (C.c_int, [vp, vp, vp, vp, u32, u32, P(f32), P(u32)]),
     "movers_checkpoint": (C.c_int, [vp, P(vp)]),
     "movers_rollback": (C.c_int, [vp, vp]),
     "batch_checkpoint_destroy": (C.c_int, [vp]),

@@ -1,4 +1,4 @@
-// sgp_batch_slots.h -- the host bookkeeping the device-resident batches share (sgp_characters, sgp_crafts, sgp_movers and the movers' paths): which slots are
+// sgp_batch_slots.h -- the host bookkeeping the device-resident batches share (sgp_characters, sgp_crafts, sgp_movers and the movers' paths, sgp_proximity and its zones): which slots are
 // handed out, and which body each slot was attached to.  Host only and free of HIP types, so that tests/cpp/batch_slots_check.cpp can exercise it under a
 // sanitizer without a GPU.
 #pragma once

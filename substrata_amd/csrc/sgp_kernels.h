@@ -19,6 +19,7 @@
 //   sgp_k_particles.hip    A7     k_particles_update (a lane per particle: raycast_one + ParticleManager::think), k_particles_scan, k_particles_scatter (stable compaction + events), k_particles_append (sgp_particles_*)
 //   sgp_k_crafts.hip       A7     k_crafts_update (a lane per craft: HoverCarPhysics::update / BoatPhysics::update, forces into the accumulators), k_crafts_scan, k_crafts_compact (particle hand-over) (sgp_crafts_*)
 //   sgp_k_movers.hip       A5     k_movers_update (a lane per mover: ObjectPathController::update / ObjectMoveToController::update, MoveKinematic on the body), k_movers_follow (the carriages) (sgp_movers_*)
+//   sgp_k_proximity.hip    A7     k_prox_observers (a workgroup per observer: its position and zone), k_prox_test (a lane per watched object: near bits, zone events counted), k_prox_scan, k_prox_emit (sgp_proximity_*)
 //   sgp_k_edits.hip        A5/A6  k_apply_cmds, k_ghost_refresh, read-back
 //   sgp_k_tiles.hip        (e)    tile export / routing, re-tiling histograms
 //   sgp_k_checkpoint.hip          k_ckpt_copy: the segmented copy of sgp_world_checkpoint / sgp_world_rollback
@@ -599,6 +600,39 @@ struct MoverBufs {
 };
 void launch_movers_update(const DV& d, const MoverBufs& b, float dt, hipStream_t s);      // walkers and move-to movers
 void launch_movers_follow(const DV& d, const MoverBufs& b, float dt, hipStream_t s);      // followers, behind launch_movers_update
+// ---- batched proximity and zone watchers (sgp_k_proximity.hip, sgp_dev_proximity.h, sgp_proximity_math.h) ----------------------------------------------------
+// The host owns the objects' records and tags, the observers' sources and the zones (uploaded when they change); the device owns the near masks, the
+// observers' zones and the pending events.  It reaches the host's wishes through serial numbers, as the movers do: a record whose serial differs from the
+// one the state has seen is a newcomer in its slot.  Events are placed without atomics: k_prox_test counts per workgroup, k_prox_scan turns the counts into
+// offsets, k_prox_emit writes.
+#define PROX_WG 256                    // lanes per workgroup of every launch; objects per count of k_prox_test
+#define PROX_SCAN_PASS PROX_WG         // counts the single workgroup of k_prox_scan takes in one pass of its loop
+#define PROX_ALIVE (1u << 31)          // ProxRec::flags beside SGP_PROX_WANT_*
+#define PROX_GONE  (1u << 30)          //   the body is no longer the one the object was added on (the host knows: it hands out the slots)
+#define PROX_ST_SERIAL_SHIFT 8         // the device's sgp_proximity_state::status: SGP_PROX_ST_* in the low byte, the record's serial (16 bits) above it
+struct ProxRec { uint32_t body; float radius; uint32_t flags, serial; };                                    // 16 bytes: one load
+struct ProxZone { float mn[3]; uint32_t key; float mx[3]; uint32_t gen_live; };                             // gen_live: generation << 1 | live
+struct ProxObsRec { uint32_t alive, serial, source, body; float pos[3]; uint32_t gone; float off[3]; uint32_t pad_; };
+struct ProxObsDyn { float pos[3]; uint32_t zone, zone_gen, zone_key, update_index, status, serial, pad_[3]; };      // zone: the slot it stands in, or SGP_INVALID_ID
+// what k_prox_observers leaves of one observer for the other launches of the update: where it is, and the zone it left and the one it entered if its zone changed
+struct ProxObsRun {
+	float p[3]; uint32_t live;            // live: tested in this update
+	uint32_t changed, prev_ok, prev_key, cur_ok;      // prev_ok: it was in a zone, and that zone is still live (an EXITED may be raised); cur_ok: it is in a zone now
+	float pmn[3]; uint32_t cur_key; float pmx[3]; uint32_t pad0_;
+	float cmn[3]; uint32_t pad1_; float cmx[3]; uint32_t pad2_;
+};
+struct ProxState { uint32_t n_events, update_index, cur_update, pad_; };      // n_events: raised since the last drain (what did not fit included); cur_update: the index the running update stamps
+struct ProxBufs {
+	const ProxRec* rec; const uint64_t* tag; uint2* st;      // st[object]: (status | serial << PROX_ST_SERIAL_SHIFT, near mask)
+	uint4* evw;                  // [object] of the running update, where the workgroup has events: (near bits that changed and are wanted, new mask, exited bits, entered bits)
+	uint32_t* wg_counts; uint32_t* wg_off;      // [workgroup of k_prox_test]: its events, and where they start in `events`
+	const ProxZone* zones; const ProxObsRec* obs; ProxObsDyn* obs_dyn; ProxObsRun* run; ProxState* state;
+	sgp_proximity_event* events;
+	uint32_t n, n_zones, ev_cap;      // object slots and zone slots in use (high-water marks), event records held between drains
+	uint32_t live_obs, clear_obs;     // observers that are alive; observers removed since the last launch (their bits leave every mask)
+};
+static_assert(sizeof(ProxObsRun) == 96 && sizeof(ProxObsRec) == 48 && sizeof(ProxObsDyn) == 48 && sizeof(ProxZone) == 32 && sizeof(sgp_proximity_event) == 32, "proximity records: whole 16-byte units");
+void launch_proximity_update(const DV& d, const ProxBufs& b, hipStream_t s);      // k_prox_observers, k_prox_test, k_prox_scan, k_prox_emit
 void launch_export_boundary(const DV& d, uint32_t nb, float3 lo, float3 hi, float margin, sgp_ghost_record* out, uint32_t cap, uint32_t* count, hipStream_t s);
 
 // ---- tile exchange with the routing on the device (sgp_tiles_*) ----------------------------------------------------

@@ -18,6 +18,7 @@
 #include "sgp_k_particles.hip"
 #include "sgp_k_crafts.hip"
 #include "sgp_k_movers.hip"
+#include "sgp_k_proximity.hip"
 #include "sgp_k_vehicle.hip"
 #include "sgp_k_tiles.hip"
 #include "sgp_k_checkpoint.hip"

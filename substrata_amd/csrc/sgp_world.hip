@@ -87,6 +87,8 @@ SGP_API int sgp_abi_sizeof(int which)
 	case 38: return (int)sizeof(sgp_path_waypoint); case 39: return (int)sizeof(sgp_path_segment); case 40: return (int)sizeof(sgp_path_progress);      // (37 stays -1 likewise)
 	case 41: return (int)sizeof(sgp_mover_desc); case 42: return (int)sizeof(sgp_mover_state);
 	case 44: return (int)sizeof(sgp_batch_checkpoint_info);      // (43 stays -1 likewise)
+	case 46: return (int)sizeof(sgp_proximity_object); case 47: return (int)sizeof(sgp_proximity_observer); case 48: return (int)sizeof(sgp_proximity_event);      // (45 stays -1 likewise)
+	case 49: return (int)sizeof(sgp_proximity_state); case 50: return (int)sizeof(sgp_proximity_observer_state);
 	default: return -1;
 	}
 }

@@ -1,4 +1,4 @@
-// sgp_world_batch_checkpoint.hip -- capture and rollback of a device-resident batch (sgp_characters, sgp_particles, sgp_crafts, sgp_movers): the part the four
+// sgp_world_batch_checkpoint.hip -- capture and rollback of a device-resident batch (sgp_characters, sgp_particles, sgp_crafts, sgp_movers, sgp_proximity): the part they
 // share, which is all of it but the list each batch gives of its state (BatchCkptLayout, sgp_world_internal.h; docs/CONTRACT.md, "Batch checkpoints").
 //
 // A checkpoint holds, on the device, one buffer with a piece per listed array -- the mirrors' device copies first, then the batch's own arrays --, and on the

@@ -304,7 +304,7 @@ int particles_append_device(sgp_particles* ps, const sgp_particle* d_recs, const
 int add_one(sgp_world* w, const sgp_body_desc* d, uint32_t* id_out, bool ghost);
 int book_record_body(sgp_world* w, uint32_t* flags_io, uint64_t userdata, float radius, float volume, bool ghost, uint32_t* id_out);      // (the host's share of add_one for a body created on the device from a record)
 
-// ---- the host side the device-resident batches of a world share (sgp_characters, sgp_particles, sgp_crafts, sgp_movers) ---------------------------------------
+// ---- the host side the device-resident batches of a world share (sgp_characters, sgp_particles, sgp_crafts, sgp_movers, sgp_proximity) ------------------------
 static inline int fail_in(int code, const char* fn, const char* what) { char msg[256]; snprintf(msg, sizeof(msg), "%s: %s", fn, what); return fail(code, msg); }
 static inline int fail_ghosts(const char* fn, const char* whose)
 {

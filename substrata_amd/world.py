@@ -203,6 +203,70 @@ class Movers(_Batch):
         self._w._check(self._w._fn("movers_set_rotation_track")(self._h, int(i), a, b, float(duration), int(easing), float(cur_elapsed)), "movers_set_rotation_track")
 
 
+class Proximity(_Batch):
+    """A batch of proximity and zone watchers of one world (sgp_proximity): numpy in, numpy out.  update() enqueues and returns; states(), observers() and
+    drain_events() wait."""
+    _stem, _state_dtype = "proximity", abi.proximity_state_dtype
+
+    def __init__(self, world, object_capacity, zone_capacity=16, event_capacity=4096):
+        super().__init__(world, object_capacity, zone_capacity, event_capacity)
+        self.event_capacity = int(event_capacity)
+
+    def update(self):
+        self._w._check(self._update(self._h), "proximity_update")
+
+    def add(self, bodies, radius=20.0, flags=abi.PROX_WANT_NEAR | abi.PROX_WANT_ZONE, tags=None):
+        """One call for all of `bodies`; radius, flags and tags are scalars or one value per body.  Returns the ids (uint32)."""
+        bodies = np.ascontiguousarray(bodies, dtype=np.uint32).reshape(-1)
+        d = np.zeros(len(bodies), dtype=abi.proximity_object_dtype)
+        d["body"], d["radius"], d["flags"] = bodies, radius, flags
+        d["tag"] = 0 if tags is None else tags
+        ids = np.zeros(len(bodies), dtype=np.uint32)
+        self._w._check(self._w._fn("proximity_add")(self._h, d.ctypes.data, len(d), ids.ctypes.data), "proximity_add")
+        return ids
+
+    def remove(self, i):
+        self._w._check(self._w._fn("proximity_remove")(self._h, int(i)), "proximity_remove")
+
+    def set_flags(self, i, flags):
+        self._w._check(self._w._fn("proximity_set_flags")(self._h, int(i), int(flags)), "proximity_set_flags")
+
+    def set_observer(self, k, pos=None, body=None, offset=(0.0, 0.0, 0.0)):
+        """Observer k at `pos`, or riding `body` at the world-space `offset`."""
+        o = abi.ProximityObserver(source=abi.PROX_OBS_POINT if body is None else abi.PROX_OBS_BODY, body=0 if body is None else int(body))
+        o.pos[:] = [float(x) for x in ((0.0, 0.0, 0.0) if pos is None else pos)]
+        o.offset[:] = [float(x) for x in offset]
+        self._w._check(self._w._fn("proximity_set_observer")(self._h, int(k), C.byref(o)), "proximity_set_observer")
+
+    def set_points(self, first, xyz):
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        self._w._check(self._w._fn("proximity_set_points")(self._h, int(first), len(xyz), xyz.ctypes.data), "proximity_set_points")
+
+    def remove_observer(self, k):
+        self._w._check(self._w._fn("proximity_remove_observer")(self._h, int(k)), "proximity_remove_observer")
+
+    def add_zone(self, mn, mx, key):
+        z = C.c_uint32(0)
+        self._w._check(self._w._fn("proximity_zone_add")(self._h, _fp(_f3(mn)), _fp(_f3(mx)), int(key), C.byref(z)), "proximity_zone_add")
+        return int(z.value)
+
+    def remove_zone(self, zone):
+        self._w._check(self._w._fn("proximity_zone_remove")(self._h, int(zone)), "proximity_zone_remove")
+
+    def observers(self, first=0, n=abi.PROX_MAX_OBSERVERS):
+        out = np.zeros(int(n), dtype=abi.proximity_observer_state_dtype)
+        self._w._check(self._w._fn("proximity_get_observers")(self._h, int(first), int(n), out.ctypes.data), "proximity_get_observers")
+        return out
+
+    def drain_events(self, cap=None):
+        """(events since the last drain as abi.proximity_event_dtype, in their order; how many more did not fit event_capacity)"""
+        cap = self.event_capacity if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), dtype=abi.proximity_event_dtype)
+        n, dropped = C.c_uint32(0), C.c_uint32(0)
+        self._w._check(self._w._fn("proximity_drain_events")(self._h, out.ctypes.data, cap, C.byref(n), C.byref(dropped)), "proximity_drain_events")
+        return out[:min(n.value, cap)].copy(), int(dropped.value)
+
+
 class Crafts(_Batch):
     """A batch of hover cars and boats of one world (sgp_crafts): update() enqueues and returns; states() waits."""
     _stem, _state_dtype = "crafts", abi.craft_state_dtype
@@ -656,6 +720,10 @@ class CWorld:
     def movers(self, capacity, path_capacity=16):
         """A batch of up to `capacity` path and move-to controllers over `path_capacity` shared paths that belongs to this world (close it before the world)."""
         return Movers(self, capacity, path_capacity)
+
+    def proximity(self, object_capacity, zone_capacity=16, event_capacity=4096):
+        """A batch of up to `object_capacity` watched objects, `zone_capacity` zones and 32 observers that belongs to this world (close it before the world)."""
+        return Proximity(self, object_capacity, zone_capacity, event_capacity)
 
     def characters(self, capacity):
         """A batch of up to `capacity` virtual characters that belongs to this world (close it before the world)."""
