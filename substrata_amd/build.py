@@ -14,8 +14,6 @@ operations it stood for: results do not change.  The load/store vectorizer is an
 flag only where its kernels measured no slower without the pairing (profiles/scalar_f32_step_kernels.md): sgp_k_constraints.hip
 (k_setup) and sgp_k_solve_hc.hip (k_solve_hc, a stage file of its own for this reason) measured slower and keep the pairing.  The
 query, character, particle, craft, mover, cast, mesh, tile, checkpoint and edit files have not been measured and stay as they were.
-The unity translation unit of --experiments contains every stage file and takes the flag as a whole, so in such a build k_setup,
-k_solve_hc and the query, character, particle, ... kernels are compiled without the pairing too.
 """
 import os
 import subprocess
@@ -28,9 +26,7 @@ OBJ = os.path.join(CSRC, ".obj")
 LIB = os.path.join(HERE, "libsgp.so")
 KERNEL_SOURCES = sorted(f for f in os.listdir(CSRC) if f.startswith("sgp_k_") and f.endswith(".hip"))
 HOST_SOURCES = sorted(f for f in os.listdir(CSRC) if f.startswith("sgp_world") and f.endswith(".hip"))
-UNITY = "sgp_kernels_experiments.hip"      # every stage file + csrc/experiments/* as one translation unit (--experiments)
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "sgp.h")]      # every header: several are generated
-EXPERIMENT_FILES = [os.path.join("experiments", f) for f in sorted(os.listdir(os.path.join(CSRC, "experiments")))]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC",
          "-fvisibility=hidden", "-mllvm", "-amdgpu-kernarg-preload-count=16", "-Wall", "-Wno-unused-function", "-Wno-unused-result", "-Wno-unused-value"]
 NO_F32_PAIRING = ["-fno-slp-vectorize"]
@@ -39,7 +35,6 @@ SOURCE_FLAGS = {
     "sgp_k_narrowphase.hip": NO_F32_PAIRING,
     "sgp_k_sweep.hip": NO_F32_PAIRING,
     "sgp_k_vehicle.hip": NO_F32_PAIRING,
-    UNITY: NO_F32_PAIRING,
 }
 
 
@@ -62,42 +57,31 @@ def _newer(deps, target):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def _common_deps(experiments):
-    deps = [os.path.join(CSRC, h) for h in HEADERS] + [os.path.abspath(__file__)]
-    if experiments:
-        deps += [os.path.join(CSRC, f) for f in EXPERIMENT_FILES + KERNEL_SOURCES]
-    return deps
+def _common_deps():
+    return [os.path.join(CSRC, h) for h in HEADERS] + [os.path.abspath(__file__)]
 
 
-def _sources(experiments):
-    return ([UNITY] if experiments else KERNEL_SOURCES) + HOST_SOURCES
+def _sources():
+    return KERNEL_SOURCES + HOST_SOURCES
 
 
-def _obj(src, experiments):
-    return os.path.join(OBJ, src[:-4] + (".x.o" if experiments else ".o"))
+def _obj(src):
+    return os.path.join(OBJ, src[:-4] + ".o")
 
 
-def _tag_path():
-    return os.path.join(HERE, "libsgp.tag")      # what the library was linked from: "product" or "experiments" (travels with it to the GPU box; the objects do not)
-
-
-def needs_build(experiments=False):
-    tag = "experiments" if experiments else "product"
-    if not os.path.exists(LIB) or not os.path.exists(_tag_path()) or open(_tag_path()).read().strip() != tag:
-        return True
-    return _newer(_common_deps(experiments) + [os.path.join(CSRC, s) for s in _sources(experiments)], LIB)
+def needs_build():
+    return _newer(_common_deps() + [os.path.join(CSRC, s) for s in _sources()], LIB)
 
 
 def build(force=False, verbose=False, extra=()):
-    experiments = "-DSGP_EXPERIMENTS" in extra
-    if not force and not needs_build(experiments):
+    if not force and not needs_build():
         return LIB
     os.makedirs(OBJ, exist_ok=True)
-    common = _common_deps(experiments)
-    todo = [s for s in _sources(experiments) if force or _newer(common + [os.path.join(CSRC, s)], _obj(s, experiments))]
+    common = _common_deps()
+    todo = [s for s in _sources() if force or _newer(common + [os.path.join(CSRC, s)], _obj(s))]
 
     def compile_one(src):
-        cmd = [hipcc()] + source_flags(src) + list(extra) + ["-c", os.path.join(CSRC, src), "-o", _obj(src, experiments)]
+        cmd = [hipcc()] + source_flags(src) + list(extra) + ["-c", os.path.join(CSRC, src), "-o", _obj(src)]
         if verbose:
             print(" ".join(cmd), flush=True)
         return src, subprocess.run(cmd, capture_output=True, text=True)
@@ -110,19 +94,15 @@ def build(force=False, verbose=False, extra=()):
             sys.stderr.write(f"---- {s}\n{r.stdout}{r.stderr}")
     if failed:
         raise RuntimeError("hipcc failed building " + ", ".join(s for s, _ in failed))
-    cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-fvisibility=hidden"] + [_obj(s, experiments) for s in _sources(experiments)] + ["-o", LIB]
+    cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-fvisibility=hidden"] + [_obj(s) for s in _sources()] + ["-o", LIB]
     if verbose:
         print(" ".join(cmd), flush=True)
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         sys.stderr.write(r.stdout + r.stderr)
         raise RuntimeError("hipcc failed linking libsgp.so")
-    with open(_tag_path(), "w") as f:
-        f.write("experiments" if experiments else "product")
     return LIB
 
 
 if __name__ == "__main__":
-    # --experiments: also compile csrc/experiments/* (the resident tile solver of round 3, the solver probe) into the library -- measured negatives and
-    # timing aids that the product does not carry (SGP_TILE_SOLVER, tools/solve_probe.py, tests/test_tile_solver_gpu.py need such a build)
-    build(force="--force" in sys.argv, verbose=True, extra=("-DSGP_EXPERIMENTS",) if "--experiments" in sys.argv else ())
+    build(force="--force" in sys.argv, verbose=True)

@@ -238,7 +238,6 @@ SGP_DEV void step_end_block(const DV& d, StepCounters* host_mapped, EventWindow*
 	uint32_t* dst = (uint32_t*)host_mapped;
 	for (uint32_t i = threadIdx.x; i < sizeof(StepCounters) / 4; i += blockDim.x) dst[i] = src[i];
 	__syncthreads();
-	if (threadIdx.x == 0 && d.ts_nt) { host_mapped->ts_error = d.ts_flags[0]; host_mapped->ts_all_adjacent = d.ts_flags[1]; }
 	if (threadIdx.x < sizeof(EventCounters) / 4) ((uint32_t*)&host_events->c)[threadIdx.x] = ((const uint32_t*)d.evc)[threadIdx.x];
 	const uint32_t win = min(min(d.ev_window, SGP_EVENT_WINDOW), d.cap_bodies);
 	const uint32_t* lists[3] = { d.ev_activated, d.ev_deactivated, d.ev_water };

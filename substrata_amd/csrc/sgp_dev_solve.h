@@ -20,7 +20,7 @@ SGP_DEV sym33 body_world_inv_inertia_rec(const DV& d, uint32_t body)
 // every point first (they use the normal impulse of the previous iteration), then the non-penetration rows.
 // The lever-arm products of every (point, axis) come precomputed from k_setup (axis_rows); they are the very values the expressions
 // cross(r, axis) and I (r x axis) would yield here, so the arithmetic -- and every bit of the result -- is that of the plain
-// formulation (apply_impulse / axis_jv above, which the warm start and the oracle use), at less than half the instructions.
+// formulation (the oracle's apply_impulse / axis_jv), at less than half the instructions.
 // The value the neighbouring lane (lane ^ 1) holds: a DPP quad permutation [1, 0, 3, 2] -- a register move modifier, where __shfl_xor compiles to
 // ds_bpermute_b32, a round trip through the LDS crossbar that sat on the dependent chain of every row of every constraint.
 SGP_DEV float lane_swap1(float x)
@@ -155,10 +155,6 @@ template <int ST = ST_PLAIN> SGP_DEV void half_store(const ConstraintArrays& ca,
 	for (int i = 0; i < 4; ++i) { if (i < np) store_rec<ST>(ca.lam[i], slot, F4(h.lam[i], 0.0f)); }
 }
 
-// (the forms that look the buffer up themselves: experiments)
-template <int ROWS = -1> SGP_DEV void half_load(const DV& d, uint32_t slot, int side, ConHalf& h) { half_load<ROWS>(d, CUR(d), slot, side, h); }
-SGP_DEV void half_store(const DV& d, uint32_t slot, int side, const ConHalf& h) { half_store(CUR(d), slot, side, h); }
-
 // this body's share of J v for one row, the neighbour's share, their difference (share of body 1 minus share of body 2: identical on both lanes)
 SGP_DEV float half_jv(v3 lv, v3 av, v3 axis, v3 c, int side)
 {
@@ -232,8 +228,6 @@ template <int VS, int ROWS = -1, int ST = ST_PLAIN> SGP_DEV void solve_velocity_
 	half_solve<VS, ST>(h, side, vel, d.dbg_flags);
 	half_store<ST>(ca, slot, side, h);
 }
-
-template <int VS, int ROWS = -1> SGP_DEV void solve_velocity_pair_t(const DV& d, uint32_t slot, int side, float4* vel) { solve_velocity_pair_t<VS, ROWS>(d, CUR(d), slot, side, vel); }
 
 // The same for the layout without rows (ROWS = 2: worlds of a million constraints and more), written so that nothing is kept that is used once: a colour launch
 // loads a constraint, iterates it ONCE and stores it, so r x axis and I (r x axis) -- 72 registers of a ConHalf -- are built where the row is applied instead of
@@ -414,4 +408,9 @@ SGP_DEV uint32_t overflow_next(const ConstraintArrays& ca, uint32_t first, uint3
 	last = best; have_last = true;
 	return bslot;
 }
-SGP_DEV uint32_t overflow_next(const DV& d, uint32_t first, uint32_t count, uint64_t& last, bool& have_last) { return overflow_next(CUR(d), first, count, last, have_last); }
+// the walk itself: f(slot) for every constraint of the overflow colour, one after the other in that order (the lanes that call it walk in step)
+template <class F> SGP_DEV void overflow_walk(const ConstraintArrays& ca, uint32_t first, uint32_t count, F f)
+{
+	uint64_t last = 0; bool have_last = false;
+	for (uint32_t it = 0; it < count; ++it) f(overflow_next(ca, first, count, last, have_last));
+}

@@ -7,23 +7,6 @@
 
 struct BodyVel { v3 lv, av; };
 
-SGP_DEV void apply_impulse(BodyVel& A, BodyVel& B, float im1, const sym33& I1, float im2, const sym33& I2, v3 r1, v3 r2, v3 axis, float lambda)
-{
-	if (im1 > 0.0f) {
-		A.lv = v3_sub(A.lv, v3_scale(axis, lambda * im1));
-		A.av = v3_sub(A.av, v3_scale(sym33_mul(I1, v3_cross(r1, axis)), lambda));
-	}
-	if (im2 > 0.0f) {
-		B.lv = v3_add(B.lv, v3_scale(axis, lambda * im2));
-		B.av = v3_add(B.av, v3_scale(sym33_mul(I2, v3_cross(r2, axis)), lambda));
-	}
-}
-
-SGP_DEV float axis_jv(const BodyVel& A, const BodyVel& B, v3 r1, v3 r2, v3 axis)
-{
-	return (v3_dot(axis, A.lv) + v3_dot(v3_cross(r1, axis), A.av)) - (v3_dot(axis, B.lv) + v3_dot(v3_cross(r2, axis), B.av));
-}
-
 struct PairCtx { uint2 ab; float im1, im2; sym33 I1, I2; BodyVel A, B; v3 n, t1, t2; float friction; int np; };
 template <int VS> SGP_DEV void load_pair(const DV& d, const ConstraintArrays& ca, uint32_t slot, PairCtx& c, const float4* vel)
 {
@@ -40,8 +23,6 @@ template <int VS> SGP_DEV void load_pair(const DV& d, const ConstraintArrays& ca
 	c.A.lv = V3(va); c.A.av = V3(wa);
 	c.B.lv = V3(vb); c.B.av = V3(wb);
 }
-
-template <int VS> SGP_DEV void load_pair(const DV& d, uint32_t slot, PairCtx& c, const float4* vel) { load_pair<VS>(d, CUR(d), slot, c, vel); }
 
 // (plain stores, also from k_solve_colour<0>, whose records would qualify for write-through: one lane holds both bodies and its neighbour may be past the colour's
 // end, so there is no lane pair for store_rec2, and a record's halves written through one by one leave the L2 as two partial writes -- docs/KERNELS.md,
@@ -124,8 +105,7 @@ __global__ void __launch_bounds__(TPB) k_warm_bodies(DV d)
 	if (count == 0u) return;                                    // (uniform over the grid)
 	if (!last_block(&d.ctr->tickets[1]) || threadIdx.x != 0) return;
 	const ConstraintArrays ca = cur_arrays(d, d.sp->parity);
-	uint64_t last = 0; bool have_last = false;
-	for (uint32_t it = 0; it < count; ++it) warm_start_one(d, ca, overflow_next(ca, first, count, last, have_last));
+	overflow_walk(ca, first, count, [&](uint32_t slot) { warm_start_one(d, ca, slot); });
 }
 struct AxisRows { float4 c1, c2, i1, i2; };      // r1 x axis (w: bias), r2 x axis (w: effective mass), I1 (r1 x axis), I2 (r2 x axis)
 
@@ -253,7 +233,7 @@ template <int MODE, int ROWS = -1, int OCC = 1> __global__ void __launch_bounds_
 // every colour from first_colour on, it is also the catch-all when this step uses more colours than the plan expected.
 // k_solve_tail: warm start of the overflow colour (mode 0) and position iterations (mode 2), one thread per constraint;
 // k_solve_tail_vel: velocity iterations, two lanes per constraint (768 threads = 384 constraints per phase).
-// (overflow_next: sgp_dev_solve.h)
+// (overflow_walk: sgp_dev_solve.h)
 __global__ void __launch_bounds__(512) k_solve_tail(DV d, int first_colour, int mode)
 {
 	// the colour table in LDS: one coalesced load instead of a dependent global load per (mostly empty) colour
@@ -272,11 +252,7 @@ __global__ void __launch_bounds__(512) k_solve_tail(DV d, int first_colour, int 
 	}
 	const uint32_t first = cs[SGP_OVERFLOW_COLOUR], count = cs[SGP_OVERFLOW_COLOUR + 1] - first;
 	if (count == 0 || threadIdx.x != 0) return;
-	uint64_t last = 0; bool have_last = false;
-	for (uint32_t it = 0; it < count; ++it) {
-		const uint32_t bslot = overflow_next(ca, first, count, last, have_last);
-		if (mode == 0) warm_start_one(d, ca, bslot); else solve_position_one(d, ca, bslot);
-	}
+	overflow_walk(ca, first, count, [&](uint32_t slot) { if (mode == 0) warm_start_one(d, ca, slot); else solve_position_one(d, ca, slot); });
 }
 
 #define TAIL_VEL_TPB 768    // 384 constraints per phase; 3 waves per SIMD (a constraint half needs ~150 registers)
@@ -312,11 +288,7 @@ template <int ROWS> __global__ void __launch_bounds__(TAIL_VEL_TPB) k_solve_tail
 	}
 	const uint32_t first = cs[SGP_OVERFLOW_COLOUR], count = cs[SGP_OVERFLOW_COLOUR + 1] - first;
 	if (count == 0 || threadIdx.x >= 2) return;                   // lanes 0 and 1: the two sides of one constraint at a time
-	uint64_t last = 0; bool have_last = false;
-	for (uint32_t it = 0; it < count; ++it) {
-		const uint32_t bslot = overflow_next(ca, first, count, last, have_last);
-		solve_velocity_pair_t<VEL_F4, ROWS>(d, ca, bslot, side, d.vel);
-	}
+	overflow_walk(ca, first, count, [&](uint32_t slot) { solve_velocity_pair_t<VEL_F4, ROWS>(d, ca, slot, side, d.vel); });
 }
 // (HC_CLASSES, HC_WG_PAIRS and the other constants of the component layout: sgp_dev_solve.h)
 SGP_DEV bool hc_can_move(const DV& d, uint32_t body) { return d.vel[VEL_F4 * (size_t)body].w > 0.0f; }      // effective inverse mass of the step (k_pre_solve)
@@ -531,11 +503,9 @@ __global__ void __launch_bounds__(SMALL_TPB) k_solve_small(DV d, int warm_start,
 			const uint32_t first = cs[SGP_OVERFLOW_COLOUR], count = cs[SGP_OVERFLOW_COLOUR + 1] - first;
 			if (count != 0) {
 				if (threadIdx.x < 2) {                     // lanes 0 and 1: the two sides of one constraint at a time (the warm start: lane 0 alone)
-					uint64_t last = 0; bool have_last = false;
-					for (uint32_t it = 0; it < count; ++it) {
-						const uint32_t bslot = overflow_next(ca, first, count, last, have_last);
-						if (pass < 0) { if (side == 0) warm_start_one_t<2>(d, ca, bslot, sv); } else solve_velocity_pair_t<2, 0>(d, ca, bslot, side, sv);
-					}
+					overflow_walk(ca, first, count, [&](uint32_t slot) {
+						if (pass < 0) { if (side == 0) warm_start_one_t<2>(d, ca, slot, sv); } else solve_velocity_pair_t<2, 0>(d, ca, slot, side, sv);
+					});
 				}
 				__syncthreads();
 			}
@@ -628,6 +598,7 @@ __global__ void __launch_bounds__(512) k_solve_small_single(DV d, int warm_start
 {
 	__shared__ float4 sv[2 * SMALL_LDS_BODIES];        // 64 KB: [lin vel, effective inverse mass][ang vel, -] per body slot
 	__shared__ uint32_t cs[SGP_MAX_COLOURS + 1];
+	const ConstraintArrays ca = cur_arrays(d, d.sp->parity);
 	const uint32_t n = min(d.sp->n_slots, (uint32_t)SMALL_LDS_BODIES);
 	if (threadIdx.x <= SGP_MAX_COLOURS) cs[threadIdx.x] = d.cstarts[threadIdx.x];
 	for (uint32_t i = threadIdx.x; i < 2 * n; i += 512) sv[i] = d.vel[VEL_F4 * (size_t)(i >> 1) + (i & 1u)];
@@ -643,12 +614,12 @@ __global__ void __launch_bounds__(512) k_solve_small_single(DV d, int warm_start
 			for (int c = 0; c < SGP_OVERFLOW_COLOUR; ++c) {
 				const uint32_t b = cs[c], e = cs[c + 1];
 				if (b == e) continue;
-				if (slot >= b && slot < e) warm_start_one_t<2>(d, CUR(d), slot, sv);
+				if (slot >= b && slot < e) warm_start_one_t<2>(d, ca, slot, sv);
 				__syncthreads();
 			}
 		}
 		ConReg r; int my_col = -1;
-		if (mine) { con_load(d, CUR(d), slot, r); my_col = (r.np_col >> 8) & 0xFF; }
+		if (mine) { con_load(d, ca, slot, r); my_col = (r.np_col >> 8) & 0xFF; }
 		for (int pass = 0; pass < iterations; ++pass) {
 			for (int c = 0; c < SGP_OVERFLOW_COLOUR; ++c) {
 				if (cs[c] == cs[c + 1]) continue;
@@ -656,7 +627,7 @@ __global__ void __launch_bounds__(512) k_solve_small_single(DV d, int warm_start
 				__syncthreads();
 			}
 		}
-		if (mine) con_store(CUR(d), slot, r);
+		if (mine) con_store(ca, slot, r);
 	} else
 	if (cs[0] != cs[SGP_MAX_COLOURS]) {
 		for (int pass = warm_start ? -1 : 0; pass < iterations; ++pass) {
@@ -664,23 +635,14 @@ __global__ void __launch_bounds__(512) k_solve_small_single(DV d, int warm_start
 				const uint32_t b = cs[c], e = cs[c + 1];
 				if (b == e) continue;
 				for (uint32_t k = b + threadIdx.x; k < e; k += 512) {
-					if (pass < 0) warm_start_one_t<2>(d, CUR(d), k, sv); else solve_velocity_one_t<2>(d, CUR(d), k, sv);
+					if (pass < 0) warm_start_one_t<2>(d, ca, k, sv); else solve_velocity_one_t<2>(d, ca, k, sv);
 				}
 				__syncthreads();
 			}
 			const uint32_t first = cs[SGP_OVERFLOW_COLOUR], count = cs[SGP_OVERFLOW_COLOUR + 1] - first;
 			if (count != 0) {
 				if (threadIdx.x == 0) {
-					uint64_t last = 0; bool have_last = false;
-					for (uint32_t it = 0; it < count; ++it) {
-						uint64_t best = ~0ull; uint32_t bslot = first;
-						for (uint32_t k = 0; k < count; ++k) {
-							const uint2 okab = con_ab(CUR(d), first + k); const uint64_t pr = sgp_mix64(((uint64_t)okab.x << 32) | okab.y);
-							if ((!have_last || pr > last) && pr <= best) { best = pr; bslot = first + k; }
-						}
-						last = best; have_last = true;
-						if (pass < 0) warm_start_one_t<2>(d, CUR(d), bslot, sv); else solve_velocity_one_t<2>(d, CUR(d), bslot, sv);
-					}
+					overflow_walk(ca, first, count, [&](uint32_t slot) { if (pass < 0) warm_start_one_t<2>(d, ca, slot, sv); else solve_velocity_one_t<2>(d, ca, slot, sv); });
 				}
 				__syncthreads();
 			}
@@ -688,15 +650,6 @@ __global__ void __launch_bounds__(512) k_solve_small_single(DV d, int warm_start
 	}
 	for (uint32_t i = threadIdx.x; i < 2 * n; i += 512) d.vel[VEL_F4 * (size_t)(i >> 1) + (i & 1u)] = sv[i];
 }
-#ifndef SGP_EXPERIMENTS
-// (the solver probe and the resident tile solver of round 3 are experiments: built only with -DSGP_EXPERIMENTS, as the unity file sgp_kernels_experiments.hip;
-// a plain build never plans them, sgp_world.hip)
-void launch_solve_probe(const DV&, int, int, uint32_t, hipStream_t) {}
-void launch_ts_label(const DV&, uint32_t, hipStream_t) {}
-void launch_colour_count_ts(const DV&, uint32_t, hipStream_t) {}
-void launch_setup_ts(const DV&, uint32_t, hipStream_t) {}
-void launch_ts_solve(const DV&, int, int, hipStream_t) {}
-#endif
 #define SOLVE_MANY_MIN 131072u      // constraints in a colour from which the launch runs in rounds (256 CUs x 4 SIMDs x 2-3 waves x 32 constraints = 65k-98k in flight)
 #ifndef SOLVE_MANY_OCC
 #define SOLVE_MANY_OCC 3

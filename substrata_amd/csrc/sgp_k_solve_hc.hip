@@ -106,11 +106,7 @@ template <int MODE, int ROWS = -1> __global__ void __launch_bounds__(HC_TPB) k_s
 		__syncthreads();
 	}
 	if (ocount == 0u || threadIdx.x >= 2u) return;               // lanes 0 and 1: the two sides of one constraint at a time
-	uint64_t last = 0; bool have_last = false;
-	for (uint32_t it = 0; it < ocount; ++it) {
-		const uint32_t bslot = overflow_next(CUR(d), ofirst, ocount, last, have_last);
-		if (MODE == 1) solve_velocity_pair_t<VEL_F4, ROWS>(d, CUR(d), bslot, side, d.vel); else solve_position_pair(d, CUR(d), bslot, side);
-	}
+	overflow_walk(CUR(d), ofirst, ocount, [&](uint32_t slot) { if (MODE == 1) solve_velocity_pair_t<VEL_F4, ROWS>(d, CUR(d), slot, side, d.vel); else solve_position_pair(d, CUR(d), slot, side); });
 }
 
 void launch_solve_hc(const DV& d, int first_colour, uint32_t est, int mode, hipStream_t s, int compact_rows)

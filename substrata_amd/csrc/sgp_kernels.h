@@ -153,8 +153,8 @@ struct StepCounters {
 	                             //   asleep as a whole finds its contacts when it wakes (round 6; VERDICT r05 'a pile that wakes later starts cold')
 	uint32_t wake_any;           // some sleeping body was marked for wake-up this step (plain store of 1: k_wake_pairs has nothing to do otherwise)
 	uint32_t tickets[4];         // last_block(): workgroups of k_colour_count / k_warm_bodies / k_cache_build that have finished
-	uint32_t ts_error;           // tile solver: a tile gave up waiting for a neighbour (k_step_end copies ts_flags[0])
-	uint32_t ts_all_adjacent;    // tile solver: some body was touched by more than four tiles
+	uint32_t ts_error;           // reserved, always 0 (the struct is part of checkpoint blobs: the words behind it keep their offsets)
+	uint32_t ts_all_adjacent;    // reserved, always 0
 	uint32_t round_n[32];        // uncoloured manifolds at the start of colouring round r (the host plans the next step's wide rounds from it)
 	uint32_t colour_count[SGP_MAX_COLOURS];
 	uint32_t colour_fill[SGP_MAX_COLOURS];
@@ -164,6 +164,7 @@ struct StepCounters {
 	uint32_t cnp_start[SGP_MAX_COLOURS * 4];
 	uint32_t cnp_fill[SGP_MAX_COLOURS * 4];
 };
+static_assert(sizeof(StepCounters) == 3928, "StepCounters is copied to host-mapped memory and written into checkpoint blobs (CkptScalars): its layout must not move");
 
 // Event counters: NOT cleared at step start (edits between steps also raise activation events); the host drains them.
 struct EventCounters {
@@ -295,20 +296,6 @@ struct DV {
 	uint32_t* island_awake;
 	uint32_t* export_counts;   // per 256-body block: bodies the tile export picks (k_export_count)
 	uint32_t* awake_mark;      // per body: 1 = sleepy but known to stay awake this step (k_island_mark)
-	// tile solver (k_ts_*): ts_nt tiles = workgroups of the one resident velocity-iteration launch, a ts_gx x ts_gy grid over the world (0: unavailable)
-	uint32_t ts_nt, ts_gx, ts_gy;
-	uint8_t*  body_tile;       // tile of every body (k_ts_label)
-	uint64_t* body_tiles4;     // up to four tile ids (16 bits each, 0xFFFF free): the tiles whose constraints touch the body this step
-	uint8_t*  man_tile;        // tile of every manifold's constraint
-	uint32_t* ts_count;        // [colour * ts_nt + tile] constraints; ts_start: their first slot (+ 1 entry: the total); ts_fill: scratch of the slot assignment
-	uint32_t* ts_start;
-	uint32_t* ts_fill;
-	uint32_t* ts_adj;          // [tile][8]: bit U set = this tile and tile U touch a common body
-	uint64_t* ts_wait;         // [tile]: colours in which the tile touches a shared body (it waits for its neighbours before those phases)
-	uint32_t* ts_epoch;        // [tile * 32]: phases the tile has completed (one 128 B line per tile)
-	uint32_t* ts_flags;        // [0] a tile gave up waiting (the step fails), [1] some body is touched by more than four tiles (all tiles neighbours)
-	uint16_t* ts_at;           // [2 * slot + side]: where that side's body lives during the launch: LDS slot, TS_AT_SHARED or TS_AT_IMMOVABLE
-	uint8_t*  ts_side;         // [2 * slot + side]: 0 immovable, 1 private to the constraint's tile, 2 shared
 	// broad phase
 	uint32_t table_size;       // power of two
 	uint32_t* cell_hash;       // per body: linear cell index in the dense grid (0xFFFFFFFF = not binned)
@@ -412,15 +399,10 @@ void launch_colour_commit(const DV& d, uint32_t n_man, uint32_t round, hipStream
 void launch_colour_count(const DV& d, uint32_t n_man, hipStream_t s);
 void launch_colour_finish(const DV& d, uint32_t first_round, int build_list, hipStream_t s);
 void launch_setup(const DV& d, uint32_t n_man, hipStream_t s);
-void launch_ts_label(const DV& d, uint32_t nb, hipStream_t s);
-void launch_colour_count_ts(const DV& d, uint32_t n_man, hipStream_t s);
-void launch_setup_ts(const DV& d, uint32_t n_man, hipStream_t s);
-void launch_ts_solve(const DV& d, int passes, int colour_end, hipStream_t s);      // colours < colour_end, `passes` times
 // mode: 0 warm start, 1 velocity iteration, 2 position iteration.  est = expected constraints of that colour (grid sizing only)
 void launch_solve_colour(const DV& d, int colour, uint32_t est, int mode, hipStream_t s, int compact_rows);      // compact_rows: StepParams::compact_rows of the step (selects the kernel)
-void launch_solve_probe(const DV& d, int variant, int colour, uint32_t est, hipStream_t s);
 void launch_warm_bodies(const DV& d, uint32_t nb, hipStream_t s);
-void launch_solve_tail(const DV& d, int first_colour, int mode, hipStream_t s, int compact_rows = 0);
+void launch_solve_tail(const DV& d, int first_colour, int mode, hipStream_t s, int compact_rows);
 // small worlds: warm start + all velocity iterations in one single-workgroup launch (needs n_slots <= SGP_SMALL_WORLD_BODIES)
 #define SGP_SMALL_WORLD_BODIES 2048
 void launch_hc_build(const DV& d, int first_colour, uint32_t est, hipStream_t s);      // components of the colours >= first_colour (after launch_setup)

@@ -196,22 +196,6 @@ SGP_API int sgp_world_create(const sgp_world_desc* desc, sgp_world** out)
 	HIP_TRY(hipMemsetAsync(d.slot_gen, 0, sizeof(uint32_t) * N, w->stream));
 	DEV_ALLOC(d.man_ab, M); DEV_ALLOC(d.man_n, M); DEV_ALLOC(d.man_colour, M); DEV_ALLOC(d.man_prio, M); DEV_ALLOC(d.man_prev, M); DEV_ALLOC(d.man_slot, M);
 	DEV_ALLOC(d.hc_root, N); DEV_ALLOC(d.hc_count, N); DEV_ALLOC(d.hc_base, N); DEV_ALLOC(d.hc_rank, M);
-	// tile solver: one workgroup per compute unit must be resident, so the tile grid follows the device (256 CUs: 16 x 16)
-	{
-		int dev = 0, cus = 0;
-		if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-		d.ts_nt = 0; d.ts_gx = d.ts_gy = 0;
-#ifdef SGP_EXPERIMENTS      // (the resident tile solver is an experiment: csrc/experiments/sgp_tile_solver.inc; a plain build neither allocates for it nor plans it)
-		if (cus >= 256) { d.ts_nt = 256; d.ts_gx = 16; d.ts_gy = 16; } else if (cus >= 128) { d.ts_nt = 128; d.ts_gx = 16; d.ts_gy = 8; } else if (cus >= 64) { d.ts_nt = 64; d.ts_gx = 8; d.ts_gy = 8; }
-#endif
-		if (d.ts_nt) {
-			const size_t E = (size_t)SGP_MAX_COLOURS * d.ts_nt;
-			DEV_ALLOC(d.body_tile, N); DEV_ALLOC(d.body_tiles4, N); DEV_ALLOC(d.man_tile, M);
-			DEV_ALLOC(d.ts_count, E + 1); DEV_ALLOC(d.ts_start, E + 1); DEV_ALLOC(d.ts_fill, E + 1);
-			DEV_ALLOC(d.ts_adj, (size_t)d.ts_nt * 8); DEV_ALLOC(d.ts_wait, d.ts_nt); DEV_ALLOC(d.ts_epoch, (size_t)d.ts_nt * 32); DEV_ALLOC(d.ts_flags, 4);
-			DEV_ALLOC(d.ts_at, 2 * (size_t)M); DEV_ALLOC(d.ts_side, 2 * (size_t)M);
-		}
-	}
 	d.cap_hc_list = 2u * M + 4096u; DEV_ALLOC(d.hc_list, d.cap_hc_list); DEV_ALLOC(d.hc_entry, d.cap_hc_list); DEV_ALLOC(d.hc_big_list, 1024);
 	DEV_ALLOC(d.ulist[0], M); DEV_ALLOC(d.ulist[1], M);
 	for (int k = 0; k < 4; ++k) { DEV_ALLOC(d.man_p1[k], M); DEV_ALLOC(d.man_p2[k], M); }
@@ -250,9 +234,6 @@ SGP_API int sgp_world_create(const sgp_world_desc* desc, sgp_world** out)
 	{ const char* e = getenv("SGP_CHECKPOINT_FULL"); if (e && e[0] == '1') w->checkpoint_full = true; }      // (checkpoints copy every device allocation whole: the A side of profiles/r08_checkpoint.md)
 	w->serial = world_register();
 	{ const char* e = getenv("SGP_DEBUG_FLAGS"); w->dv.dbg_flags = e ? (uint32_t)atoi(e) : 0u; }
-#ifdef SGP_EXPERIMENTS
-	{ const char* e = getenv("SGP_TILE_SOLVER"); if (e) w->use_tile_solver = atoi(e); }
-#endif
 	{ const char* e = getenv("SGP_VEHICLE_FUSED"); if (e) w->fuse_vehicle_solve = atoi(e) != 0; }
 	{ const char* e = getenv("SGP_COMPACT_ROWS_MIN"); if (e && atoll(e) >= 0) w->compact_rows_min = (uint32_t)atoll(e); }
 	{ const char* e = getenv("SGP_ROWS_MODE"); if (e && (atoi(e) == 1 || atoi(e) == 2)) w->rows_mode_large = (uint32_t)atoi(e); }
@@ -260,7 +241,6 @@ SGP_API int sgp_world_create(const sgp_world_desc* desc, sgp_world** out)
 	{ const char* e = getenv("SGP_ROWS_IN_SMALL_WORLDS"); if (e && e[0] == '1' && !w->use_small_world) w->rows_in_small_worlds = true; }
 	{ const char* e = getenv("SGP_ROWS_MODE2_MIN"); if (e && atoll(e) >= 0) w->rows_mode2_min = (uint32_t)atoll(e); }
 	{ const char* e = getenv("SGP_ROWS_MODE_DEFAULT"); if (e && atoi(e) >= 0 && atoi(e) <= 2) w->rows_mode_default = (uint32_t)atoi(e); }
-	{ const char* e = getenv("SGP_TS_MIN_CONSTRAINTS"); if (e && atoi(e) >= 0) w->ts_min_constraints = (uint32_t)atoi(e); }
 	{ const char* e = getenv("SGP_HC_BUDGET"); if (e) { const int v = atoi(e); if (v <= 0) w->use_components = false; else w->hc_budget = (uint32_t)v; } }
 	{ int dev = 0, cus = 0; if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) w->n_cus = (uint32_t)cus; }
 	{ const char* e = getenv("SGP_HC_MIN_COLOURS"); if (e && atoi(e) >= 0) w->hc_min_colours = (uint32_t)atoi(e); }
@@ -618,7 +598,6 @@ struct StepPlan {
 	uint32_t hc_est;             // their constraints (previous step)
 	int      hc_probe;           // >= 0: this step also computes the component sizes for hc_probe = hc_first - 1 (not used for solving)
 	uint32_t hc_probe_est;
-	int      tile_solver;        // all velocity iterations in the one resident launch of the tile solver (k_ts_solve)
 	int      small_pairs;        // ... with two lanes per constraint (the previous step had <= 384 constraints), else one thread per constraint
 	int      ev_reset;           // the first launch empties the device's event counters (the host pulled the lists after the previous step: every step of a caller that steps one
 	                             //   at a time); 0: they go on accumulating (the later steps of sgp_world_step_n, a step after edits that raised events)
@@ -691,11 +670,6 @@ static void make_plan(const sgp_world* w, StepPlan& p)
 		for (int c = k; c < SGP_OVERFLOW_COLOUR; ++c) used += w->plan_colour_count[c] != 0u;
 		if (used < (int)w->hc_min_colours) { p.hc_first = -1; p.hc_probe = -1; p.hc_est = 0; p.hc_probe_est = 0; p.tail_first = tf; }
 	}
-	// the tile solver: a pile large enough that its colour launches are bound by latency, small enough that a tile's bodies fit its LDS table
-	// (the table takes what fits and leaves the rest in global memory, so the bound is about speed, not correctness), no vehicle rows between
-	// the passes, and enough body slots for k_ts_label's grid to clear the (colour, tile) histogram
-	p.tile_solver = (w->use_tile_solver && w->dv.ts_nt && !p.small_world && w->n_vehicles == 0 && p.vel_iters > 0 && w->n_con >= w->ts_min_constraints &&
-	                 w->high >= SGP_MAX_COLOURS * w->dv.ts_nt && w->last_active <= w->dv.ts_nt * 1536u && !w->h_sp->compact_rows) ? w->use_tile_solver : 0;      // (2: debugging aid -- the tile order of the slots, solved by the colour launches)
 	p.ev_reset = w->ev_reset_pending ? 1 : 0;
 	p.sp = *w->h_sp;
 	p.sp.parity = 0u;        // (not part of a plan: the device flips its own)
@@ -739,13 +713,8 @@ static int enqueue_step(sgp_world* w, const StepPlan& p)
 		}
 		{ KScope k(w, KC_COLOUR_COMMIT); launch_colour_finish(d, p.rounds, 0, s); }
 	}
-	if (p.tile_solver) {
-		{ KScope k(w, KC_COLOUR_COUNT); launch_ts_label(d, nb, s); launch_colour_count_ts(d, p.est_man, s); }
-		{ KScope k(w, KC_SETUP); launch_setup_ts(d, p.est_man, s); }
-	} else {
-		{ KScope k(w, KC_COLOUR_COUNT); launch_colour_count(d, p.est_man, s); }
-		{ KScope k(w, KC_SETUP); launch_setup(d, p.est_man, s); }
-	}
+	{ KScope k(w, KC_COLOUR_COUNT); launch_colour_count(d, p.est_man, s); }
+	{ KScope k(w, KC_SETUP); launch_setup(d, p.est_man, s); }
 	if (p.hc_first >= 0 && p.hc_probe >= 0) { KScope k(w, KC_SETUP); launch_hc_probe(d, p.hc_probe, p.hc_probe_est, s); }
 	if (p.hc_first >= 0) { KScope k(w, KC_SETUP); launch_hc_build(d, p.hc_first, p.hc_est, s); }
 	STAGE_MARK(4);
@@ -765,15 +734,7 @@ static int enqueue_step(sgp_world* w, const StepPlan& p)
 			if (p.n_vehicles) { KScope k(w, KC_VEHICLE); launch_vehicle_solve(d, 0, s); }
 			{ KScope k(w, KC_WARM_START); launch_warm_bodies(d, nb, s); }
 		}
-		if (p.tile_solver == 1) { KScope k(w, KC_SOLVE_VELOCITY); launch_ts_solve(d, p.vel_iters, SGP_MAX_COLOURS, s); }
-		else if (p.tile_solver == 3 && p.hc_first >= 0) {
-			// the big colours of a pass in the resident tile launch, the sparse high colours by connected component (one launch each per pass)
-			for (int it = 0; it < p.vel_iters; ++it) {
-				{ KScope k(w, KC_SOLVE_VELOCITY); launch_ts_solve(d, 1, p.tail_first, s); }
-				{ KScope k(w, KC_SOLVE_VELOCITY); launch_solve_hc(d, p.hc_first, p.hc_est, 1, s, (int)p.sp.compact_rows); }
-			}
-		}
-		else for (int it = 0; it < p.vel_iters; ++it) solve_pass(1, KC_SOLVE_VELOCITY);
+		for (int it = 0; it < p.vel_iters; ++it) solve_pass(1, KC_SOLVE_VELOCITY);
 	}
 	STAGE_MARK(5);
 	// -- 6. the body-array sweep
@@ -878,7 +839,6 @@ static int step_impl(sgp_world* w, float dt, bool final_readback)
 	w->last_active = w->h_ctr->n_active;
 	const StepCounters c1 = *w->h_ctr;
 	const uint32_t n_con = c1.n_constraints;
-	if (plan.tile_solver && c1.ts_error) return fail(SGP_ERR_HIP, "sgp_world_step: the tile solver timed out waiting for a neighbouring tile (a workgroup of the resident launch was not running); set SGP_TILE_SOLVER=0");
 	w->n_con = n_con;
 	w->last_pairs = c1.n_pairs; w->last_manifolds = c1.n_manifolds;
 	w->plan_rounds = c1.rounds_used;
@@ -920,7 +880,6 @@ static int step_impl(sgp_world* w, float dt, bool final_readback)
 	st.num_cached_manifolds = c1.n_cached;
 	st.num_component_constraints = c1.hc_n; st.num_catch_all_constraints = c1.hc_n_big;
 	st.num_deferred_vehicles = c1.veh_deferred;
-	st.tile_solver = plan.tile_solver ? (c1.ts_all_adjacent ? 2u : 1u) : 0u;
 	st.pairs_dropped = c1.pairs_dropped; st.manifolds_dropped = c1.manifolds_dropped;
 	st.device_bytes = w->device_bytes;
 	st.num_active = c1.n_active;
@@ -990,38 +949,6 @@ SGP_API int sgp_world_step_profiled(sgp_world* w, float dt, sgp_step_profile* ou
 	out->num_contact_points = w->stats.num_contact_points;
 	out->num_colours = w->stats.num_colours;
 	out->row_layout = w->h_sp->compact_rows;
-	return SGP_OK;
-}
-
-// Timing probe (tools/solve_probe.py; not declared in include/sgp.h): average time of `reps` back-to-back launches of the velocity
-// iteration of one colour, full (variant 0) or with parts removed (see k_solve_probe).  Leaves the velocities of the world perturbed.
-// 1 when the library carries csrc/experiments/* (python -m substrata_amd.build --experiments); not declared in include/sgp.h
-SGP_API int sgp_debug_has_experiments(void)
-{
-#ifdef SGP_EXPERIMENTS
-	return 1;
-#else
-	return 0;
-#endif
-}
-SGP_API int sgp_debug_time_solve(sgp_world* w, int variant, int colour, int reps, float* us_out, uint32_t* count_out)
-{
-#ifndef SGP_EXPERIMENTS
-	return fail(SGP_ERR_INVALID, "sgp_debug_time_solve: this library was built without the experiments (python -m substrata_amd.build --experiments)");
-#endif
-	if (!w || !us_out || colour < 0 || colour >= SGP_OVERFLOW_COLOUR) return fail(SGP_ERR_INVALID, "sgp_debug_time_solve");
-	hipSetDevice(w->device);
-	hipEvent_t e0, e1; HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-	const uint32_t est = w->plan_colour_count[colour];
-	for (int r = 0; r < 3; ++r) launch_solve_probe(w->dv, variant, colour, est, w->stream);
-	HIP_TRY(hipEventRecord(e0, w->stream));
-	for (int r = 0; r < reps; ++r) launch_solve_probe(w->dv, variant, colour, est, w->stream);
-	HIP_TRY(hipEventRecord(e1, w->stream));
-	HIP_TRY(hipStreamSynchronize(w->stream));
-	float ms = 0.0f; HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-	hipEventDestroy(e0); hipEventDestroy(e1);
-	*us_out = 1000.0f * ms / (float)reps;
-	if (count_out) *count_out = est;
 	return SGP_OK;
 }
 

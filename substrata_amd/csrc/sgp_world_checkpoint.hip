@@ -154,7 +154,7 @@ static void for_each_array(sgp_world* w, const CkptCounts& c, std::vector<CkptAr
 	add(w->d_mesh_verts, 'S', 0, sizeof(float4) * w->cap_mesh_verts); add(w->d_mesh_tris, 'S', 0, sizeof(uint4) * w->cap_mesh_tris);
 	add(w->d_mesh_tri_mat, 'S', 0, sizeof(uint32_t) * w->cap_mesh_tri_mat); add(w->d_mesh_nodes, 'S', 0, sizeof(MeshNode) * w->cap_mesh_nodes);
 	add(w->d_mesh_field, 'S', 0, sizeof(uint32_t) * w->cap_mesh_field);
-	// arrays without a name here (the experiments' tile solver): whole, matched by address
+	// arrays without a name here (none today: a safety net for an allocation added without an entry above): whole, matched by address
 	uint32_t k = 0;
 	for (void* p : w->allocs) { if (!seen.count(p)) { auto it = w->alloc_bytes.find(p); if (it != w->alloc_bytes.end()) out.push_back(CkptArray{ CKPT_UNNAMED_BASE + k, p, it->second, it->second }); } ++k; }
 }
@@ -377,7 +377,7 @@ SGP_API int sgp_world_rollback(sgp_world* w, const sgp_checkpoint* cp)
 	return SGP_OK;
 }
 
-// Timing aid (tools/experiments/checkpoint_bench.py; not declared in include/sgp.h, like sgp_debug_time_solve): the copy kernel alone, `reps` launches back to back
+// Timing aid (tools/experiments/checkpoint_bench.py; not declared in include/sgp.h): the copy kernel alone, `reps` launches back to back
 // between two events on the world's stream, each moving the pieces of `cp` from the world into the checkpoint's buffer again (call it right after the capture,
 // before anything re-allocates an array: it captures the same state `reps` more times).  us_out: device time per launch; bytes_out: bytes one launch reads.
 SGP_API int sgp_debug_time_checkpoint_copy(sgp_world* w, sgp_checkpoint* cp, int reps, float* us_out, uint64_t* bytes_out)

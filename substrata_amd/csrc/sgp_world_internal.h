@@ -142,8 +142,6 @@ struct sgp_world {
 	uint32_t rows_mode2_min = 65536;       // ... and below this many constraints compact rows (1) where the default says none (2): a world of 20k constraints spends its passes in the component and tail kernels, which keep a constraint for ten iterations and have the rows' use ten times (config 2: 942 against 934 steps/s)
 	uint32_t rows_mode_large = 2;          // SGP_ROWS_MODE: the layout worlds of at least compact_rows_min constraints use -- 2 no rows (the lanes rebuild them from the lever arms), 1 compact rows (r x axis only)
 	uint32_t compact_rows_min = 1000000;   // SGP_COMPACT_ROWS_MIN: from this many contact constraints on, the velocity rows are stored compact (96 B per point)
-	int use_tile_solver = 0;            // SGP_TILE_SOLVER: 0 off, 1 on where the plan finds it applicable (k_ts_solve)
-	uint32_t ts_min_constraints = 16384;
 	// high colours by component: share of the constraints they may hold (per mille; SGP_HC_BUDGET, 0 = off), and the plan's correction of it
 	// hc_k: the first colour that goes to the components (-1: not chosen yet -> the budget rule).  One colour fewer after a step that left a
 	// component to the catch-all; one more after a probe (component sizes computed for hc_k - 1 without using them) found that it fits.

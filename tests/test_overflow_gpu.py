@@ -13,25 +13,35 @@ import parity
 pytestmark = pytest.mark.gpu
 
 
-def plate_scene():
-    """A 14 x 14 x 0.6 m dynamic plate lying on the ground with 12 x 12 small boxes and spheres dropped onto it."""
+def plate_scene(n=12, pitch=1.1, half_extent=7.0):
+    """A dynamic plate (half-extent 7 m: 14 x 14 x 0.6 m) lying on the ground with n x n small boxes and spheres dropped onto it."""
     plate = scenes.dynamic_bodies(1, mass=4000.0)
-    plate["shape"][0] = (7.0, 7.0, 0.3, 0.0)
+    plate["shape"][0] = (half_extent, half_extent, 0.3, 0.0)
     plate["pos"][0] = (0.0, 0.0, 0.31)
-    n = 12
     d = scenes.dynamic_bodies(n * n, mass=20.0)
     ij = np.arange(n * n)
-    d["pos"][:, 0] = (ij % n - (n - 1) / 2) * 1.1
-    d["pos"][:, 1] = (ij // n - (n - 1) / 2) * 1.1
+    d["pos"][:, 0] = (ij % n - (n - 1) / 2) * pitch
+    d["pos"][:, 1] = (ij // n - (n - 1) / 2) * pitch
     d["pos"][:, 2] = 1.0 + 0.02 * (ij % 7)
     d["shape"][:, :3] = 0.35
     d["shape_type"] = np.where(ij % 3 == 0, abi.SHAPE_SPHERE, abi.SHAPE_BOX)
     return np.concatenate([scenes.ground(), plate, d])
 
 
+# 20 x 20 bodies at pitch 0.8 m on a plate of half-extent 8.5 m (402 bodies): 401 constraints, 338 of them in the overflow colour, from step 13 to step 44 on the
+# oracle -- the previous step's count is within 385..512, so the small-world plan takes the kernel with one thread per constraint (k_solve_small_single), and the
+# overflow colour takes it through that kernel's general path and serial walk, which the 12 x 12 plate (about 150 constraints: the lane-pair kernel) does not reach
+SINGLE_THREAD_PLATE = dict(n=20, pitch=0.8, half_extent=8.5)
+
+
 @pytest.mark.parametrize("small_world", [True, False])
 def test_plate_with_more_than_63_contacts(oracle, small_world):
-    descs = plate_scene()
+    run_plate(oracle, small_world, plate_scene(), single_thread_steps=())
+    if small_world:      # (whether the general plan takes the component launch in the second scene has not been checked: the small-world plan only)
+        run_plate(oracle, small_world, plate_scene(**SINGLE_THREAD_PLATE), single_thread_steps=(20, 40))
+
+
+def run_plate(oracle, small_world, descs, single_thread_steps):
     old = os.environ.get("SGP_NO_SMALL_WORLD")
     os.environ["SGP_NO_SMALL_WORLD"] = "0" if small_world else "1"
     try:
@@ -49,6 +59,8 @@ def test_plate_with_more_than_63_contacts(oracle, small_world):
             sg, sc = tw.gpu.stats(), tw.cpu.stats()
             assert (sg.num_manifolds, sg.num_contact_points, sg.num_colours, sg.num_overflow_constraints) == \
                    (sc.num_manifolds, sc.num_contact_points, sc.num_colours, sc.num_overflow_constraints), s
+            if s in single_thread_steps:      # what makes the scene the case it claims to be
+                assert 385 <= sg.num_manifolds <= 512 and sg.num_overflow_constraints > 0, (s, sg.num_manifolds, sg.num_overflow_constraints)
             seen_overflow = max(seen_overflow, sg.num_overflow_constraints)
             by_component = max(by_component, sg.num_component_constraints)
             d = parity.compare(tw, len(descs))
