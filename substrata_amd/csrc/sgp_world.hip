@@ -106,13 +106,14 @@ SGP_API int sgp_init(void)
 // ---------------------------------------------------------------------------------------------------------------
 // world construction, PhysicsWorld.cpp:462-532
 
-static int alloc_constraints(sgp_world* w, ConstraintArrays& c, uint32_t cap)
+static int alloc_constraints(sgp_world* w, ConstraintArrays& c, uint32_t buffer, uint32_t cap)
 {
-	DEV_ALLOC(c.hdr, cap); DEV_ALLOC(c.n_fric, cap);
-	DEV_ALLOC(c.prec, (size_t)cap * PREC_F4);      // the body-pair contact cache's records: 64 bytes per slot
-	for (int k = 0; k < 4; ++k) {
-		DEV_ALLOC(c.r1b[k], cap); DEV_ALLOC(c.r2e[k], cap); DEV_ALLOC(c.lam[k], cap); DEV_ALLOC(c.efft[k], cap);
-		DEV_ALLOC(c.loc1[k], cap); DEV_ALLOC(c.loc2[k], cap);
+	const uint32_t a = A_CA + CA_IDS * buffer;      // (which of the two buffers is the contact cache changes with every step: a checkpoint decides from CkptCounts::cache_buf)
+	DEV_ALLOC(a + CA_HDR, AK_CACHE, 16, c.hdr, cap); DEV_ALLOC(a + CA_N_FRIC, AK_CACHE, 16, c.n_fric, cap);
+	DEV_ALLOC(a + CA_PREC, AK_CACHE, 16 * PREC_F4, c.prec, (size_t)cap * PREC_F4);      // the body-pair contact cache's records: 64 bytes per slot
+	for (uint32_t k = 0; k < 4; ++k) {
+		DEV_ALLOC(a + CA_R1B + 6 * k, AK_CACHE, 16, c.r1b[k], cap); DEV_ALLOC(a + CA_R2E + 6 * k, AK_CACHE, 16, c.r2e[k], cap); DEV_ALLOC(a + CA_LAM + 6 * k, AK_CACHE, 16, c.lam[k], cap);
+		DEV_ALLOC(a + CA_EFFT + 6 * k, AK_CACHE, 8, c.efft[k], cap); DEV_ALLOC(a + CA_LOC1 + 6 * k, AK_CACHE, 16, c.loc1[k], cap); DEV_ALLOC(a + CA_LOC2 + 6 * k, AK_CACHE, 16, c.loc2[k], cap);
 	}
 	return SGP_OK;
 }
@@ -146,21 +147,26 @@ SGP_API int sgp_world_create(const sgp_world_desc* desc, sgp_world** out)
 	DV& d = w->dv;
 	const uint32_t N = desc->max_bodies, P = w->desc.max_body_pairs, M = w->desc.max_manifolds;
 	d.cap_bodies = N; d.cap_pairs = P; d.cap_manifolds = M;
-	DEV_ALLOC(d.pose, POSE_F4 * (size_t)N); DEV_ALLOC(d.vel, VEL_F4 * (size_t)N); DEV_ALLOC(d.dyn, N);
-	DEV_ALLOC(d.force, N); DEV_ALLOC(d.torque, N);
-	DEV_ALLOC(d.flags, N); DEV_ALLOC(d.aabb_min, N); DEV_ALLOC(d.aabb_max, N);
-	for (int k = 0; k < 3; ++k) DEV_ALLOC(d.sleep_s[k], N);
-	DEV_ALLOC(d.sleep_timer, N); DEV_ALLOC(d.submerged, N); DEV_ALLOC(d.userdata, N);
-	DEV_ALLOC(d.colour_mask, N); DEV_ALLOC(d.warm, (size_t)N * SGP_MAX_COLOURS * 2); DEV_ALLOC(d.claim[0], N); DEV_ALLOC(d.claim[1], N);
-	DEV_ALLOC(d.veh_claim, N); DEV_ALLOC(d.veh_epoch, 1);
-	DEV_ALLOC(d.island, N); DEV_ALLOC(d.island_awake, N); DEV_ALLOC(d.awake_mark, N); DEV_ALLOC(d.export_counts, N / 256 + 2);
+	// (every array with its checkpoint id and what of it is state: ArrayKind, sgp_world_internal.h)
+	DEV_ALLOC(A_POSE, AK_BODY, 16 * POSE_F4, d.pose, POSE_F4 * (size_t)N); DEV_ALLOC(A_VEL, AK_BODY, 16 * VEL_F4, d.vel, VEL_F4 * (size_t)N); DEV_ALLOC(A_DYN, AK_BODY, 16, d.dyn, N);
+	DEV_ALLOC(A_FORCE, AK_BODY, 16, d.force, N); DEV_ALLOC(A_TORQUE, AK_BODY, 16, d.torque, N);
+	DEV_ALLOC(A_FLAGS, AK_BODY, 4, d.flags, N); DEV_ALLOC(A_AABB_MIN, AK_BODY, 16, d.aabb_min, N); DEV_ALLOC(A_AABB_MAX, AK_BODY, 16, d.aabb_max, N);
+	for (uint32_t k = 0; k < 3; ++k) DEV_ALLOC(A_SLEEP_S + k, AK_BODY, 16, d.sleep_s[k], N);
+	DEV_ALLOC(A_SLEEP_TIMER, AK_BODY, 4, d.sleep_timer, N); DEV_ALLOC(A_SUBMERGED, AK_BODY, 4, d.submerged, N); DEV_ALLOC(A_USERDATA, AK_BODY, 8, d.userdata, N);
+	DEV_ALLOC(A_COLOUR_MASK, AK_BODY, 8, d.colour_mask, N);
+	DEV_ALLOC(A_WARM, AK_SCRATCH, 0, d.warm, (size_t)N * SGP_MAX_COLOURS * 2);      // valid only where colour_mask has the bit, and k_step_begin zeroes the masks
+	DEV_ALLOC(A_CLAIM, AK_BODY, 8, d.claim[0], N); DEV_ALLOC(A_CLAIM + 1, AK_BODY, 8, d.claim[1], N);
+	DEV_ALLOC(A_VEH_CLAIM, AK_BODY, 8, d.veh_claim, N); DEV_ALLOC(A_VEH_EPOCH, AK_WHOLE, 0, d.veh_epoch, 1);      // (the step epoch and what is compared with it go back together: veh_claim, label_wake)
+	DEV_ALLOC(A_ISLAND, AK_BODY, 4, d.island, N); DEV_ALLOC(A_ISLAND_AWAKE, AK_BODY, 4, d.island_awake, N); DEV_ALLOC(A_AWAKE_MARK, AK_BODY, 4, d.awake_mark, N);
+	DEV_ALLOC(A_EXPORT_COUNTS, AK_WHOLE, 0, d.export_counts, N / 256 + 2);
 	// cells of the broad-phase grid: room for 16 per body slot (clearing and scanning follow the cells a step's grid really has, not this capacity).  The grid covers the bounds of all small bodies with cells of R_max + margin and coarsens them
 	// (x 1.5) until it fits this table: a pile that has spread out (config 2 after its tower fell: 60 x 60 x 10 m of 1 m cells) then lands in
 	// cells with several bodies each and k_bp_pairs scans hundreds of candidates per body (0.23 ms for 10k boxes with 2 cells per slot, 0.02 ms with 8 or more).
 	// the cell arrays: a slot of 64 cells per OCCUPIED tile of the paged grid (sgp_kernels.h), and there are never more occupied tiles than bodies
 	d.table_size = std::max(4096u, next_pow2(64u * N));
-	DEV_ALLOC(d.cell_hash, N);
-	DEV_ALLOC(d.cell_count, d.table_size + 4); DEV_ALLOC(d.cell_start, d.table_size + 4); DEV_ALLOC(d.cell_fill, d.table_size + 4);
+	DEV_ALLOC(A_CELL_HASH, AK_BODY, 4, d.cell_hash, N);
+	// (scratch, with the tile tables below: a rollback clears what the current grid dirtied -- launch_ckpt_grid_reset)
+	DEV_ALLOC(A_CELL_COUNT, AK_SCRATCH, 0, d.cell_count, d.table_size + 4); DEV_ALLOC(A_CELL_START, AK_SCRATCH, 0, d.cell_start, d.table_size + 4); DEV_ALLOC(A_CELL_FILL, AK_SCRATCH, 0, d.cell_fill, d.table_size + 4);
 	// the page table over the tiles of the bounding box: 8M tiles = 512M cells (a 4 km x 4 km x 70 m world at 1.5 m cells; 32 MB) before the cells have to grow
 	// (scaled with the world's capacity, advisor r03: a world of a few hundred bodies pays 256 KB - 1 MB for it, not 32; where a small world is spread
 	// so wide that its tiles do not fit, its cells grow -- with few bodies to a cell either way)
@@ -168,50 +174,55 @@ SGP_API int sgp_world_create(const sgp_world_desc* desc, sgp_world** out)
 		uint32_t dflt = 1u << 16; while (dflt < (1u << 23) && (uint64_t)dflt < 1024ull * (uint64_t)N) dflt <<= 1;
 		const char* e = getenv("SGP_GRID_TILE_TABLE"); d.tile_table_size = e && atoi(e) > 0 ? (uint32_t)atoi(e) : dflt;
 	}
-	DEV_ALLOC(d.tile_slot, d.tile_table_size); DEV_ALLOC(d.tile_of_slot, d.table_size / 64u + 4u);
+	DEV_ALLOC(A_TILE_SLOT, AK_SCRATCH, 0, d.tile_slot, d.tile_table_size); DEV_ALLOC(A_TILE_OF_SLOT, AK_SCRATCH, 0, d.tile_of_slot, d.table_size / 64u + 4u);
 	if (hipMemsetAsync(d.tile_slot, 0xFF, sizeof(uint32_t) * (size_t)d.tile_table_size, w->stream) != hipSuccess) return fail(SGP_ERR_HIP, "tile table init");
-	DEV_ALLOC(w->d_large, N); w->cap_large = N; d.large_ids = w->d_large;
-	DEV_ALLOC(w->d_lgrid, 1); DEV_ALLOC(w->d_lg_start, SGP_LG_MAX_CELLS + 1); w->cap_lg_items = 4096; DEV_ALLOC(w->d_lg_items, w->cap_lg_items);
+	DEV_ALLOC(A_LARGE, AK_BODY, 4, w->d_large, N); w->cap_large = N; d.large_ids = w->d_large;
+	DEV_ALLOC(A_LGRID, AK_WHOLE, 0, w->d_lgrid, 1); DEV_ALLOC(A_LG_START, AK_WHOLE, 0, w->d_lg_start, SGP_LG_MAX_CELLS + 1);
+	w->cap_lg_items = 4096; DEV_ALLOC(A_LG_ITEMS, AK_WHOLE, 0, w->d_lg_items, w->cap_lg_items);      // (grows: grow_lg_items)
 	HIP_TRY(hipMemset(w->d_lgrid, 0, sizeof(LargeGrid)));
 	d.lgrid = w->d_lgrid; d.lg_start = w->d_lg_start; d.lg_items = w->d_lg_items;
-	{ void* q = nullptr; w->cap_mesh_table = 256; HIP_TRY(hipMalloc(&q, sizeof(MeshHeader) * w->cap_mesh_table)); HIP_TRY(hipMemsetAsync(q, 0, sizeof(MeshHeader) * w->cap_mesh_table, w->stream)); w->d_meshes = (MeshHeader*)q; w->device_bytes += sizeof(MeshHeader) * w->cap_mesh_table; }
+	// (the shape tables and pools, sgp_world_shapes.hip: their host mirrors are the truth, uploaded again where the two differ -- scratch)
+	w->cap_mesh_table = 256; DEV_ALLOC(A_MESHES, AK_SCRATCH, 0, w->d_meshes, w->cap_mesh_table);
 	d.meshes = w->d_meshes; d.n_meshes = 1; w->meshes.push_back(MeshHeader{}); w->mesh_refs.push_back(0);
-	d.cap_mesh_pairs = P / 4 + 1024; DEV_ALLOC(d.mesh_pairs, 4 * (size_t)d.cap_mesh_pairs); DEV_ALLOC(d.mesh_big, d.cap_mesh_pairs);      // (four lists: one per shape of the other body)
-	{ void* q = nullptr; w->cap_hull_table = 64; HIP_TRY(hipMalloc(&q, sizeof(sgd_hull) * w->cap_hull_table)); HIP_TRY(hipMemsetAsync(q, 0, sizeof(sgd_hull) * w->cap_hull_table, w->stream)); w->d_hulls = (sgd_hull*)q; w->device_bytes += sizeof(sgd_hull) * w->cap_hull_table; }
+	d.cap_mesh_pairs = P / 4 + 1024; DEV_ALLOC(A_MESH_PAIRS, AK_SCRATCH, 0, d.mesh_pairs, 4 * (size_t)d.cap_mesh_pairs); DEV_ALLOC(A_MESH_BIG, AK_SCRATCH, 0, d.mesh_big, d.cap_mesh_pairs);      // (four lists: one per shape of the other body)
+	w->cap_hull_table = 64; DEV_ALLOC(A_HULLS, AK_SCRATCH, 0, w->d_hulls, w->cap_hull_table);
 	d.hulls = w->d_hulls;
-	d.cap_hull_pairs = P / 4 + 1024; DEV_ALLOC(d.hull_pairs, d.cap_hull_pairs);
-	{ void* hw = nullptr; const size_t bytes = (size_t)d.cap_hull_pairs * 64; HIP_TRY(hipMalloc(&hw, bytes)); w->allocs.push_back(hw); w->alloc_bytes[hw] = bytes; w->device_bytes += bytes; d.hull_work = (HullWork*)hw; }      // sizeof(HullWork) = 56
+	d.cap_hull_pairs = P / 4 + 1024; DEV_ALLOC(A_HULL_PAIRS, AK_SCRATCH, 0, d.hull_pairs, d.cap_hull_pairs);
+	{ int r = dev_alloc(w, A_HULL_WORK, AK_SCRATCH, 0, d.hull_work, d.cap_hull_pairs, 64); if (r != SGP_OK) return r; }      // 64 bytes per pair: sizeof(HullWork) = 56
 	{
 		sgd_hull cube; sgd_hull_cube_template(&cube);
 		w->hulls.push_back(cube); w->hull_refs.push_back(1);      // (the cube template is never destroyed)
 		HIP_TRY(hipMemcpyAsync(&w->d_hulls[0], &w->hulls[0], sizeof(sgd_hull), hipMemcpyHostToDevice, w->stream));
 		d.n_hulls = 1;
 	}
-	DEV_ALLOC(d.sorted_min, N); DEV_ALLOC(d.sorted_max, N); DEV_ALLOC(d.grid, 1); DEV_ALLOC(d.grid_cells_used, 1);
-	DEV_ALLOC(d.bounds_acc, 8); { const int init[8] = { 0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF, (int)0x80000000, (int)0x80000000, (int)0x80000000, 0, 0 }; if (hipMemcpyAsync(d.bounds_acc, init, sizeof(init), hipMemcpyHostToDevice, w->stream) != hipSuccess || hipStreamSynchronize(w->stream) != hipSuccess) return fail(SGP_ERR_HIP, "bounds_acc init"); } DEV_ALLOC(d.scan_block_sums, (d.table_size + 1) / 1024 + 2);
-	DEV_ALLOC(d.pairs, P);
-	d.cap_wake_pairs = P / 4 + 1024; DEV_ALLOC(d.wake_pairs, d.cap_wake_pairs);
-	DEV_ALLOC(d.sleep_label, N); DEV_ALLOC(d.label_wake, N); DEV_ALLOC(d.slot_gen, N);
+	DEV_ALLOC(A_SORTED_MIN, AK_SCRATCH, 0, d.sorted_min, N); DEV_ALLOC(A_SORTED_MAX, AK_SCRATCH, 0, d.sorted_max, N);      // (the grid of the last step or query: rollback drops grid_valid)
+	DEV_ALLOC(A_GRID, AK_WHOLE, 0, d.grid, 1); DEV_ALLOC(A_GRID_CELLS_USED, AK_SCRATCH, 0, d.grid_cells_used, 1);      // (count and bounds: launch_ckpt_grid_reset leaves them as a step finds them)
+	DEV_ALLOC(A_BOUNDS_ACC, AK_SCRATCH, 0, d.bounds_acc, 8); { const int init[8] = { 0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF, (int)0x80000000, (int)0x80000000, (int)0x80000000, 0, 0 }; if (hipMemcpyAsync(d.bounds_acc, init, sizeof(init), hipMemcpyHostToDevice, w->stream) != hipSuccess || hipStreamSynchronize(w->stream) != hipSuccess) return fail(SGP_ERR_HIP, "bounds_acc init"); } DEV_ALLOC(A_SCAN_BLOCK_SUMS, AK_SCRATCH, 0, d.scan_block_sums, (d.table_size + 1) / 1024 + 2);
+	DEV_ALLOC(A_PAIRS, AK_SCRATCH, 0, d.pairs, P);
+	d.cap_wake_pairs = P / 4 + 1024; DEV_ALLOC(A_WAKE_PAIRS, AK_SCRATCH, 0, d.wake_pairs, d.cap_wake_pairs);
+	DEV_ALLOC(A_SLEEP_LABEL, AK_BODY, 4, d.sleep_label, N); DEV_ALLOC(A_LABEL_WAKE, AK_BODY, 4, d.label_wake, N); DEV_ALLOC(A_SLOT_GEN, AK_BODY, 4, d.slot_gen, N);
 	HIP_TRY(hipMemsetAsync(d.label_wake, 0, sizeof(uint32_t) * N, w->stream));
 	HIP_TRY(hipMemsetAsync(d.slot_gen, 0, sizeof(uint32_t) * N, w->stream));
-	DEV_ALLOC(d.man_ab, M); DEV_ALLOC(d.man_n, M); DEV_ALLOC(d.man_colour, M); DEV_ALLOC(d.man_prio, M); DEV_ALLOC(d.man_prev, M); DEV_ALLOC(d.man_slot, M);
-	DEV_ALLOC(d.hc_root, N); DEV_ALLOC(d.hc_count, N); DEV_ALLOC(d.hc_base, N); DEV_ALLOC(d.hc_rank, M);
-	d.cap_hc_list = 2u * M + 4096u; DEV_ALLOC(d.hc_list, d.cap_hc_list); DEV_ALLOC(d.hc_entry, d.cap_hc_list); DEV_ALLOC(d.hc_big_list, 1024);
-	DEV_ALLOC(d.ulist[0], M); DEV_ALLOC(d.ulist[1], M);
-	for (int k = 0; k < 4; ++k) { DEV_ALLOC(d.man_p1[k], M); DEV_ALLOC(d.man_p2[k], M); }
-	DEV_ALLOC(d.rows, (size_t)48 * M);
-	{ int r = alloc_constraints(w, d.ca[0], M); if (r != SGP_OK) return r; }
-	{ int r = alloc_constraints(w, d.ca[1], M); if (r != SGP_OK) return r; }
+	DEV_ALLOC(A_MAN_AB, AK_SCRATCH, 0, d.man_ab, M); DEV_ALLOC(A_MAN_N, AK_SCRATCH, 0, d.man_n, M); DEV_ALLOC(A_MAN_COLOUR, AK_SCRATCH, 0, d.man_colour, M);
+	DEV_ALLOC(A_MAN_PRIO, AK_SCRATCH, 0, d.man_prio, M); DEV_ALLOC(A_MAN_PREV, AK_SCRATCH, 0, d.man_prev, M); DEV_ALLOC(A_MAN_SLOT, AK_SCRATCH, 0, d.man_slot, M);
+	DEV_ALLOC(A_HC_ROOT, AK_BODY, 4, d.hc_root, N); DEV_ALLOC(A_HC_COUNT, AK_BODY, 4, d.hc_count, N); DEV_ALLOC(A_HC_BASE, AK_BODY, 4, d.hc_base, N); DEV_ALLOC(A_HC_RANK, AK_SCRATCH, 0, d.hc_rank, M);
+	d.cap_hc_list = 2u * M + 4096u; DEV_ALLOC(A_HC_LIST, AK_SCRATCH, 0, d.hc_list, d.cap_hc_list); DEV_ALLOC(A_HC_ENTRY, AK_SCRATCH, 0, d.hc_entry, d.cap_hc_list); DEV_ALLOC(A_HC_BIG_LIST, AK_WHOLE, 0, d.hc_big_list, 1024);
+	DEV_ALLOC(A_ULIST, AK_SCRATCH, 0, d.ulist[0], M); DEV_ALLOC(A_ULIST + 1, AK_SCRATCH, 0, d.ulist[1], M);
+	for (uint32_t k = 0; k < 4; ++k) { DEV_ALLOC(A_MAN_P1 + 2 * k, AK_SCRATCH, 0, d.man_p1[k], M); DEV_ALLOC(A_MAN_P2 + 2 * k, AK_SCRATCH, 0, d.man_p2[k], M); }
+	DEV_ALLOC(A_ROWS, AK_SCRATCH, 0, d.rows, (size_t)48 * M);
+	{ int r = alloc_constraints(w, d.ca[0], 0, M); if (r != SGP_OK) return r; }
+	{ int r = alloc_constraints(w, d.ca[1], 1, M); if (r != SGP_OK) return r; }
 	w->ht_alloc = next_pow2(2u * M);
-	DEV_ALLOC(d.ht, w->ht_alloc);
+	DEV_ALLOC(A_HT, AK_TABLE, 16, d.ht, w->ht_alloc);
 	HIP_TRY(hipMemsetAsync(d.ht, 0xFF, sizeof(uint4) * w->ht_alloc, w->stream));      // empty contact cache (key ~0)
 	d.ht_size = w->ht_alloc;
-	DEV_ALLOC(d.ht_cur, 1);
-	DEV_ALLOC(d.cache_total, 2); HIP_TRY(hipMemsetAsync(d.cache_total, 0, sizeof(uint32_t) * 2, w->stream));
+	DEV_ALLOC(A_HT_CUR, AK_WHOLE, 0, d.ht_cur, 1);
+	DEV_ALLOC(A_CACHE_TOTAL, AK_WHOLE, 0, d.cache_total, 2); HIP_TRY(hipMemsetAsync(d.cache_total, 0, sizeof(uint32_t) * 2, w->stream));
 	{ static const uint32_t first = 1024u; HIP_TRY(hipMemcpyAsync(d.ht_cur, &first, sizeof(first), hipMemcpyHostToDevice, w->stream)); }      // (an empty table: any size will do)
-	DEV_ALLOC(d.cstarts, SGP_MAX_COLOURS + 2);
-	DEV_ALLOC(d.ctr, 1); DEV_ALLOC(d.evc, 1);
-	DEV_ALLOC(d.ev_activated, N); DEV_ALLOC(d.ev_deactivated, N); DEV_ALLOC(d.ev_water, N);
+	DEV_ALLOC(A_CSTARTS, AK_WHOLE, 0, d.cstarts, SGP_MAX_COLOURS + 2);
+	DEV_ALLOC(A_CTR, AK_WHOLE, 0, d.ctr, 1); DEV_ALLOC(A_EVC, AK_WHOLE, 0, d.evc, 1);
+	// (the event lists: a capture pulls the device's into the host's first)
+	DEV_ALLOC(A_EV_ACTIVATED, AK_SCRATCH, 0, d.ev_activated, N); DEV_ALLOC(A_EV_DEACTIVATED, AK_SCRATCH, 0, d.ev_deactivated, N); DEV_ALLOC(A_EV_WATER, AK_SCRATCH, 0, d.ev_water, N);
 	HIP_TRY(hipHostMalloc((void**)&w->h_ctr, sizeof(StepCounters), hipHostMallocMapped));
 	HIP_TRY(hipHostGetDevicePointer((void**)&w->h_ctr_dev, w->h_ctr, 0));
 	HIP_TRY(hipHostMalloc((void**)&w->h_evw, sizeof(EventWindow), hipHostMallocMapped));
@@ -222,7 +233,7 @@ SGP_API int sgp_world_create(const sgp_world_desc* desc, sgp_world** out)
 	{ const char* e = getenv("SGP_EVENT_WINDOW"); if (e && atoi(e) >= 0) d.ev_window = std::min((uint32_t)atoi(e), SGP_EVENT_WINDOW); }
 	HIP_TRY(hipHostMalloc((void**)&w->h_sp, sizeof(StepParams), hipHostMallocDefault));
 	memset(w->h_sp, 0, sizeof(StepParams));
-	DEV_ALLOC(w->d_sp, 1);
+	DEV_ALLOC(A_SP, AK_WHOLE, 0, w->d_sp, 1);
 	d.sp = w->d_sp;
 	// (the device's copy holds the parity of the LAST step -- k_step_begin flips it -- i.e. the opposite of h_sp's, which is the next step's)
 	{ StepParams init = *w->h_sp; init.parity = w->h_sp->parity ^ 1u; HIP_TRY(hipMemcpyAsync(w->d_sp, &init, sizeof(init), hipMemcpyHostToDevice, w->stream)); HIP_TRY(hipStreamSynchronize(w->stream)); }
@@ -260,18 +271,7 @@ SGP_API int sgp_world_destroy(sgp_world* w)
 	ray_server_stop(w);
 	if (w->stream) hipStreamSynchronize(w->stream);
 	if (w->ray_mb) hipHostFree(w->ray_mb);
-	for (void* p : w->allocs) hipFree(p);
-	if (w->stage_dev) hipFree(w->stage_dev);
-	if (w->d_meshes) hipFree(w->d_meshes);
-	if (w->d_hulls) hipFree(w->d_hulls);
-	if (w->d_mesh_verts) hipFree(w->d_mesh_verts);
-	if (w->d_mesh_tris) hipFree(w->d_mesh_tris);
-	if (w->d_mesh_tri_mat) hipFree(w->d_mesh_tri_mat);
-	if (w->d_mesh_nodes) hipFree(w->d_mesh_nodes);
-	if (w->d_mesh_field) hipFree(w->d_mesh_field);
-	if (w->d_vehicles) hipFree(w->d_vehicles);
-	if (w->d_veh_inputs) hipFree(w->d_veh_inputs);
-	hipFree(w->d_veh_rows); hipFree(w->d_veh_head);
+	dev_arrays_release(w);
 	if (w->stage_host) hipHostFree(w->stage_host);
 	if (w->view_host) hipHostFree(w->view_host);
 	if (w->h_ctr) hipHostFree(w->h_ctr);
@@ -302,6 +302,16 @@ static int upload_sp(sgp_world* w)
 	}
 	{ StepParams up = sp; up.parity = sp.parity ^ 1u; launch_set_params(w->dv, up, w->stream); }      // (device convention: the parity of the last step)
 	w->sp_uploaded = sp; w->sp_uploaded_valid = true;
+	return SGP_OK;
+}
+
+// The item list of the static large bodies' grid made larger, for a rebuild that has more items or a restore whose blob has (nothing of the old list is kept:
+// both write it anew).  The captured graphs carry the old pointer.
+int grow_lg_items(sgp_world* w, uint32_t cap)
+{
+	{ int r = dev_array_grow(w, A_LG_ITEMS, AK_WHOLE, 0, w->d_lg_items, sizeof(uint32_t) * (size_t)cap, 0, false); if (r != SGP_OK) return r; }
+	w->cap_lg_items = cap; w->dv.lg_items = w->d_lg_items;
+	invalidate_graphs(w);
 	return SGP_OK;
 }
 
@@ -391,18 +401,7 @@ static int rebuild_large_grid(sgp_world* w)
 	}
 	w->lg_static = g.n_items ? (uint32_t)stat.size() : 0u;
 	if (w->large_linear.size() > w->cap_large) return fail(SGP_ERR_CAPACITY, "large-body list full");
-	if (items.size() > w->cap_lg_items) {
-		// (the captured graphs carry the old pointer)
-		HIP_TRY(hipStreamSynchronize(w->stream));
-		w->cap_lg_items = (uint32_t)(items.size() + items.size() / 2);
-		uint32_t* ni = nullptr;
-		HIP_TRY(hipMalloc((void**)&ni, sizeof(uint32_t) * (size_t)w->cap_lg_items));
-		// (the previous buffer is freed here, after the synchronisation above: it used to be parked in `allocs` at every growth; advisor r03)
-		if (w->d_lg_items) { auto it = std::find(w->allocs.begin(), w->allocs.end(), (void*)w->d_lg_items); if (it != w->allocs.end()) w->allocs.erase(it); w->alloc_bytes.erase((void*)w->d_lg_items); hipFree(w->d_lg_items); }
-		w->allocs.push_back(ni); w->alloc_bytes[ni] = sizeof(uint32_t) * (size_t)w->cap_lg_items; w->device_bytes += sizeof(uint32_t) * (size_t)w->cap_lg_items;
-		w->d_lg_items = ni; d.lg_items = ni;
-		invalidate_graphs(w);
-	}
+	if (items.size() > w->cap_lg_items) { int r = grow_lg_items(w, (uint32_t)(items.size() + items.size() / 2)); if (r != SGP_OK) return r; }
 	if (!w->large_linear.empty()) HIP_TRY(hipMemcpyAsync(w->d_large, w->large_linear.data(), sizeof(uint32_t) * w->large_linear.size(), hipMemcpyHostToDevice, w->stream));
 	if (g.n_items) {
 		HIP_TRY(hipMemcpyAsync(w->d_lg_start, start.data(), sizeof(uint32_t) * start.size(), hipMemcpyHostToDevice, w->stream));
@@ -776,7 +775,7 @@ static int step_impl(sgp_world* w, float dt, bool final_readback)
 		const uint32_t nb_ = st.num_bodies;
 		uint32_t lc[SGP_NUM_LAYERS]; memcpy(lc, st.layer_counts, sizeof(lc));
 		memset(&st, 0, sizeof(st));
-		st.num_bodies = nb_; memcpy(st.layer_counts, lc, sizeof(lc)); st.device_bytes = w->device_bytes;
+		st.num_bodies = nb_; memcpy(st.layer_counts, lc, sizeof(lc)); st.device_bytes = w->arrays.bytes;
 		w->idle_steps++; w->last_step_idle = true; w->steps_taken++;
 		// (the contact cache stays as the last step with somebody awake left it: what wakes up later finds the contacts it fell asleep with)
 		return SGP_OK;
@@ -881,7 +880,7 @@ static int step_impl(sgp_world* w, float dt, bool final_readback)
 	st.num_component_constraints = c1.hc_n; st.num_catch_all_constraints = c1.hc_n_big;
 	st.num_deferred_vehicles = c1.veh_deferred;
 	st.pairs_dropped = c1.pairs_dropped; st.manifolds_dropped = c1.manifolds_dropped;
-	st.device_bytes = w->device_bytes;
+	st.device_bytes = w->arrays.bytes;
 	st.num_active = c1.n_active;
 	const double ts5 = timing ? now() : 0.0;
 	double ts6 = ts5;
@@ -957,7 +956,7 @@ SGP_API int sgp_world_stats(sgp_world* w, sgp_step_stats* out)
 	if (!w || !out) return fail(SGP_ERR_INVALID, "sgp_world_stats: NULL");
 	*out = w->stats;
 	out->num_bodies = w->n_alive;
-	out->device_bytes = w->device_bytes;
+	out->device_bytes = w->arrays.bytes;
 	return SGP_OK;
 }
 
@@ -991,8 +990,8 @@ SGP_API int sgp_world_set_contact_events(sgp_world* w, int enabled)
 	hipSetDevice(w->device);
 	if (enabled && !w->dv.ev_contacts_added) {
 		w->dv.cap_contact_events = w->dv.cap_manifolds;
-		DEV_ALLOC(w->dv.ev_contacts_added, w->dv.cap_contact_events);
-		DEV_ALLOC(w->dv.ev_contacts_persisted, w->dv.cap_contact_events);
+		DEV_ALLOC(A_EV_CONTACTS_ADDED, AK_SCRATCH, 0, w->dv.ev_contacts_added, w->dv.cap_contact_events);
+		DEV_ALLOC(A_EV_CONTACTS_PERSISTED, AK_SCRATCH, 0, w->dv.ev_contacts_persisted, w->dv.cap_contact_events);
 		for (auto& kv : w->graphs) hipGraphExecDestroy(kv.second);
 		w->graphs.clear();
 	}

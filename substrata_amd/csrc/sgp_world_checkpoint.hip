@@ -1,17 +1,11 @@
 // sgp_world_checkpoint.hip -- world checkpoints: capture, rollback, the blob and restore (JPH::PhysicsSystem::SaveState / RestoreState).
 //
 // STATE is everything the next step, query or getter can observe (docs/CONTRACT.md, "Checkpoints").  On the device that is a small part of what a world
-// allocates: for_each_array() below names every device array of a world and says how much of it is state --
-//   body      one record per body slot: the first `high` records
-//   cache     the constraint buffer that is the contact cache (the one the LAST step solved): the first cache_total[buffer] slots
-//   table     the contact cache's hash table: the first *ht_cur entries (look-ups mask with it; k_island_mark clears what a larger table adds before anything reads it)
-//   vehicles  the first n_vehicles records
-//   whole     scalars and small tables, copied whole
-//   scratch   rewritten by every step before it is read (decided by reading the kernels, and checked by the tests that restore into a fresh world and that roll
-//             back over a foreign history): not state
+// allocates: every device array says so where it is allocated (its ArrayKind and stride, sgp_world_internal.h), and for_each_array() below turns that into bytes.
+// What is scratch was decided by reading the kernels, and is checked by the tests that restore into a fresh world and that roll back over a foreign history.
 // The broad phase's "what the next step has to clear" is not copied either: rollback clears what the current grid dirtied and says so (launch_ckpt_grid_reset).
-// An array this list does not know is copied whole, so forgetting one costs time, not correctness.  SGP_CHECKPOINT_FULL=1 copies every array whole (scratch included) with the
-// runtime's copies: the obviously correct statement the lean path is measured and tested against.
+// SGP_CHECKPOINT_FULL=1 copies every array whole (scratch included; not the stage buffer) with the runtime's copies: the obviously correct statement the lean
+// path is measured and tested against.
 // On the host the state is the mirrors of sgp_world (CkptHost) and, shared between the checkpoints of one shape epoch, the shape tables and pools (CkptShapes).
 #include "sgp_world_internal.h"
 
@@ -66,7 +60,7 @@ struct sgp_checkpoint {
 	sgp_world_desc desc{};      // the owner's, kept here: a checkpoint may outlive its world
 	bool full = false;
 	void* dev = nullptr; size_t dev_cap = 0, dev_used = 0;
-	std::vector<CkptSeg> segs; std::vector<void*> seg_ptr;      // seg_ptr: where the piece came from (arrays this file has no name for are matched by address)
+	std::vector<CkptSeg> segs; std::vector<void*> seg_ptr;      // seg_ptr: where the piece came from (sgp_debug_time_checkpoint_copy copies it again)
 	CkptHost host;
 	std::shared_ptr<const CkptShapes> shapes;
 	CkptCounts counts{};
@@ -77,86 +71,27 @@ struct sgp_checkpoint {
 static inline size_t up16(size_t b) { return (b + 15) & ~size_t(15); }
 static inline size_t up256(size_t b) { return (b + 255) & ~size_t(255); }
 
-#define CKPT_UNNAMED_BASE 0x40000000u
-// Every device array of a world, in a fixed order with fixed ids (a blob names arrays by id).  kind: 'B' body, 'C' cache, 'T' table, 'V' vehicles, 'W' whole, 'S' scratch.
-struct CkptIds { uint32_t lg_items = 0, vehicles = 0; };      // the two arrays that may have to grow before a restore
-static void for_each_array(sgp_world* w, const CkptCounts& c, std::vector<CkptArray>& out, CkptIds* ids = nullptr)
+// Every device array of the world in the order of the ids (a blob names arrays by id), and how much of each is state under the counts `c`
+static void for_each_array(sgp_world* w, const CkptCounts& c, std::vector<CkptArray>& out)
 {
 	out.clear();
-	const DV& d = w->dv;
-	uint32_t id = 0;
-	std::unordered_map<void*, int> seen;
-	auto add = [&](const void* cp, char kind, size_t stride, size_t alloc_override = 0) {
-		++id;
-		void* p = const_cast<void*>(cp);
-		if (!p) return;
-		size_t alloc = alloc_override;
-		if (!alloc) { auto it = w->alloc_bytes.find(p); if (it == w->alloc_bytes.end()) return; alloc = it->second; }
-		seen[p] = 1;
+	for (const auto& kv : w->arrays.recs) {
+		const uint32_t id = kv.first; const DevArray& a = kv.second;
+		if (a.kind == AK_NEVER) continue;
+		const size_t alloc = a.bytes;
 		size_t lean = 0;
-		switch (kind) {
-		case 'B': lean = (size_t)c.high * stride; break;
-		case 'C': lean = (size_t)c.cache_n * stride; break;
-		case 'T': lean = (size_t)c.ht_n * stride; break;
-		case 'V': lean = (size_t)c.n_vehicles * stride; break;
-		case 'W': lean = alloc; break;
-		default: lean = 0; break;
+		switch (a.kind) {
+		case AK_BODY: lean = (size_t)c.high * a.stride; break;
+		case AK_CACHE: lean = (id >= A_CA + CA_IDS ? 1u : 0u) == c.cache_buf ? (size_t)c.cache_n * a.stride : 0; break;      // (the other buffer is where the next step writes its constraints)
+		case AK_TABLE: lean = (size_t)c.ht_n * a.stride; break;
+		case AK_VEHICLES: lean = (size_t)c.n_vehicles * a.stride; break;
+		case AK_WHOLE: lean = alloc; break;
+		default: break;
 		}
 		lean = std::min(up16(lean), alloc & ~size_t(15));      // (every array is allocated in whole 16-byte units or is copied up to its last whole one: hipMalloc aligns to 256)
-		if (kind == 'W' && (alloc & 15)) lean = alloc;         // a whole array of odd size: the runtime copies it (never the kernel)
-		out.push_back(CkptArray{ id, p, alloc, lean });
-	};
-	add(d.pose, 'B', 16 * POSE_F4); add(d.vel, 'B', 16 * VEL_F4); add(d.dyn, 'B', 16); add(d.force, 'B', 16); add(d.torque, 'B', 16);
-	add(d.flags, 'B', 4); add(d.aabb_min, 'B', 16); add(d.aabb_max, 'B', 16);
-	for (int k = 0; k < 3; ++k) add(d.sleep_s[k], 'B', 16);
-	add(d.sleep_timer, 'B', 4); add(d.submerged, 'B', 4); add(d.userdata, 'B', 8);
-	add(d.colour_mask, 'B', 8);
-	add(d.warm, 'S', 0);                 // valid only where colour_mask has the bit, and k_step_begin zeroes the masks
-	add(d.claim[0], 'B', 8); add(d.claim[1], 'B', 8);
-	add(d.veh_claim, 'B', 8); add(d.veh_epoch, 'W', 0);      // (the step epoch and what is compared with it go back together: veh_claim, label_wake)
-	add(d.island, 'B', 4); add(d.island_awake, 'B', 4); add(d.awake_mark, 'B', 4); add(d.export_counts, 'W', 0);
-	add(d.cell_hash, 'B', 4);
-	add(d.cell_count, 'S', 0); add(d.cell_start, 'S', 0); add(d.cell_fill, 'S', 0); add(d.tile_slot, 'S', 0); add(d.tile_of_slot, 'S', 0);      // (launch_ckpt_grid_reset)
-	add(w->d_large, 'B', 4); add(w->d_lgrid, 'W', 0); add(w->d_lg_start, 'W', 0); add(w->d_lg_items, 'W', 0); if (ids) ids->lg_items = id;
-	add(d.mesh_pairs, 'S', 0); add(d.mesh_big, 'S', 0); add(d.hull_pairs, 'S', 0); add(d.hull_work, 'S', 0);
-	add(d.sorted_min, 'S', 0); add(d.sorted_max, 'S', 0);      // (the grid of the last step or query: rollback drops grid_valid)
-	add(d.grid, 'W', 0); add(d.grid_cells_used, 'S', 0); add(d.bounds_acc, 'S', 0); add(d.scan_block_sums, 'S', 0);      // (count and bounds: launch_ckpt_grid_reset leaves them as a step finds them)
-	add(d.pairs, 'S', 0); add(d.wake_pairs, 'S', 0);
-	add(d.sleep_label, 'B', 4); add(d.label_wake, 'B', 4); add(d.slot_gen, 'B', 4);
-	add(d.man_ab, 'S', 0); add(d.man_n, 'S', 0); add(d.man_colour, 'S', 0); add(d.man_prio, 'S', 0); add(d.man_prev, 'S', 0); add(d.man_slot, 'S', 0);
-	add(d.hc_root, 'B', 4); add(d.hc_count, 'B', 4); add(d.hc_base, 'B', 4); add(d.hc_rank, 'S', 0);
-	add(d.hc_list, 'S', 0); add(d.hc_entry, 'S', 0); add(d.hc_big_list, 'W', 0);
-	add(d.ulist[0], 'S', 0); add(d.ulist[1], 'S', 0);
-	for (int k = 0; k < 4; ++k) { add(d.man_p1[k], 'S', 0); add(d.man_p2[k], 'S', 0); }
-	add(d.rows, 'S', 0);
-	for (uint32_t b = 0; b < 2; ++b) {
-		const ConstraintArrays& a = d.ca[b];
-		const char k = b == c.cache_buf ? 'C' : 'S';      // (the other buffer is where the next step writes its constraints)
-		add(a.hdr, k, 16); add(a.n_fric, k, 16); add(a.prec, k, 16 * PREC_F4);
-		for (int j = 0; j < 4; ++j) { add(a.r1b[j], k, 16); add(a.r2e[j], k, 16); add(a.lam[j], k, 16); add(a.efft[j], k, 8); add(a.loc1[j], k, 16); add(a.loc2[j], k, 16); }
+		if (a.kind == AK_WHOLE && (alloc & 15)) lean = alloc;  // a whole array of odd size: the runtime copies it (never the kernel)
+		out.push_back(CkptArray{ id, a.ptr, alloc, lean });
 	}
-	add(d.ht, 'T', 16); add(d.ht_cur, 'W', 0); add(d.cache_total, 'W', 0); add(d.cstarts, 'W', 0);
-	add(d.ctr, 'W', 0); add(d.evc, 'W', 0);
-	add(d.ev_activated, 'S', 0); add(d.ev_deactivated, 'S', 0); add(d.ev_water, 'S', 0);      // (a capture pulls the device's event lists into the host's first)
-	add(d.ev_contacts_added, 'S', 0); add(d.ev_contacts_persisted, 'S', 0);
-	add(w->d_sp, 'W', 0);
-	add(w->d_vehicles, 'V', sizeof(sgd_vehicle), w->cap_vehicles ? sizeof(sgd_vehicle) * (size_t)w->cap_vehicles : 0); if (ids) ids->vehicles = id;
-	// Not state on the device, so nothing of them in a lean checkpoint -- the vehicle inputs and the shape tables and pools have host mirrors that are the truth
-	// (uploaded again where they differ), the vehicle rows and heads (with the defer bits behind them) are rebuilt by every step's controller kernel -- but part of
-	// "every device allocation", which is what a full checkpoint copies: they go back where the array still has the size it had (a grown one was re-made from the mirrors).
-	if (w->cap_vehicles) {
-		const size_t nc = w->cap_vehicles;
-		add(w->d_veh_inputs, 'S', 0, sizeof(sgp_vehicle_input) * nc);
-		add(w->d_veh_rows, 'S', 0, sizeof(float4) * 16u * 4u * nc);
-		add(w->d_veh_head, 'S', 0, sizeof(float4) * 5u * nc + sizeof(uint32_t) * (nc / 32u + 4u));
-	} else id += 3;
-	add(w->d_meshes, 'S', 0, sizeof(MeshHeader) * w->cap_mesh_table); add(w->d_hulls, 'S', 0, sizeof(sgd_hull) * w->cap_hull_table);
-	add(w->d_mesh_verts, 'S', 0, sizeof(float4) * w->cap_mesh_verts); add(w->d_mesh_tris, 'S', 0, sizeof(uint4) * w->cap_mesh_tris);
-	add(w->d_mesh_tri_mat, 'S', 0, sizeof(uint32_t) * w->cap_mesh_tri_mat); add(w->d_mesh_nodes, 'S', 0, sizeof(MeshNode) * w->cap_mesh_nodes);
-	add(w->d_mesh_field, 'S', 0, sizeof(uint32_t) * w->cap_mesh_field);
-	// arrays without a name here (none today: a safety net for an allocation added without an entry above): whole, matched by address
-	uint32_t k = 0;
-	for (void* p : w->allocs) { if (!seen.count(p)) { auto it = w->alloc_bytes.find(p); if (it != w->alloc_bytes.end()) out.push_back(CkptArray{ CKPT_UNNAMED_BASE + k, p, it->second, it->second }); } ++k; }
 }
 
 // one launch (or a few, for more pieces than a table holds) of the segmented copy; to_checkpoint: world -> buffer, else back
@@ -304,7 +239,7 @@ SGP_API int sgp_world_checkpoint(sgp_world* w, sgp_checkpoint** io)
 		cp->dev = q; cp->dev_cap = nc;
 	}
 	*io = cp;
-	cp->full = full; cp->dev_used = total; cp->segs = segs; cp->seg_ptr = ptrs; cp->counts = c; cp->world_device_bytes = w->device_bytes;
+	cp->full = full; cp->dev_used = total; cp->segs = segs; cp->seg_ptr = ptrs; cp->counts = c; cp->world_device_bytes = w->arrays.bytes;
 	if (full) {
 		for (size_t i = 0; i < segs.size(); ++i) HIP_TRY(hipMemcpyAsync((char*)cp->dev + segs[i].offset, ptrs[i], bytes[i], hipMemcpyDeviceToDevice, w->stream));
 	} else {
@@ -340,7 +275,6 @@ SGP_API int sgp_world_rollback(sgp_world* w, const sgp_checkpoint* cp)
 	for (size_t i = 0; i < cp->segs.size(); ++i) {
 		auto it = by_id.find(cp->segs[i].id);
 		if (it == by_id.end()) continue;
-		if (cp->segs[i].id >= CKPT_UNNAMED_BASE && it->second->ptr != cp->seg_ptr[i]) continue;
 		if (!cp->segs[i].lean && cp->segs[i].bytes != it->second->alloc) continue;      // scratch (full checkpoints only) of an array that has been re-made since
 		ptrs[i] = it->second->ptr; bytes[i] = std::min<uint64_t>(cp->segs[i].bytes, it->second->alloc);
 	}
@@ -605,15 +539,7 @@ static bool same_desc(sgp_world_desc a, sgp_world_desc b) { a.device = 0; b.devi
 static int ensure_lg_items(sgp_world* w, size_t bytes)
 {
 	if (bytes <= sizeof(uint32_t) * (size_t)w->cap_lg_items) return SGP_OK;
-	HIP_TRY(hipStreamSynchronize(w->stream));
-	const uint32_t nc = (uint32_t)(bytes / sizeof(uint32_t));
-	uint32_t* ni = nullptr;
-	HIP_TRY(hipMalloc((void**)&ni, sizeof(uint32_t) * (size_t)nc));
-	if (w->d_lg_items) { auto it = std::find(w->allocs.begin(), w->allocs.end(), (void*)w->d_lg_items); if (it != w->allocs.end()) w->allocs.erase(it); w->device_bytes -= w->alloc_bytes[(void*)w->d_lg_items]; w->alloc_bytes.erase((void*)w->d_lg_items); hipFree(w->d_lg_items); }
-	w->allocs.push_back(ni); w->alloc_bytes[ni] = sizeof(uint32_t) * (size_t)nc; w->device_bytes += sizeof(uint32_t) * (size_t)nc;
-	w->cap_lg_items = nc; w->d_lg_items = ni; w->dv.lg_items = ni;
-	invalidate_graphs(w);
-	return SGP_OK;
+	return grow_lg_items(w, (uint32_t)(bytes / sizeof(uint32_t)));
 }
 
 SGP_API int sgp_world_set_contact_events(sgp_world* w, int enabled);
@@ -640,15 +566,14 @@ SGP_API int sgp_world_restore(sgp_world* w, const void* blob, uint64_t bytes)
 	if (n_seg) memcpy(table.data(), base + h.header_bytes + h.host_bytes + h.shape_bytes, h.table_bytes);
 	// first pass over the pieces against the arrays as they are: everything but the growable ones must fit NOW, or the world stays untouched
 	std::vector<CkptArray> arrays;
-	CkptCounts c = h.counts; CkptIds ids;
-	for_each_array(w, c, arrays, &ids);
-	const uint32_t id_lg_items = ids.lg_items, id_vehicles = ids.vehicles;
+	CkptCounts c = h.counts;
+	for_each_array(w, c, arrays);
 	std::unordered_map<uint32_t, const CkptArray*> by_id;
 	for (const CkptArray& a : arrays) by_id[a.id] = &a;
 	size_t lg_bytes = 0; bool want_events = host.s.h_sp.contact_events != 0;
 	for (const CkptSeg& s : table) {
-		if (s.id == id_lg_items) { lg_bytes = (size_t)s.bytes; if (s.bytes > (1ull << 32)) return fail(SGP_ERR_INVALID, "sgp_world_restore: a piece is larger than its array can be"); continue; }
-		if (s.id == id_vehicles) { if (s.bytes > up16(sizeof(sgd_vehicle) * (uint64_t)host.s.n_vehicles)) return fail(SGP_ERR_INVALID, "sgp_world_restore: a piece is larger than its array"); continue; }
+		if (s.id == A_LG_ITEMS) { lg_bytes = (size_t)s.bytes; if (s.bytes > (1ull << 32)) return fail(SGP_ERR_INVALID, "sgp_world_restore: a piece is larger than its array can be"); continue; }
+		if (s.id == A_VEHICLES) { if (s.bytes > up16(sizeof(sgd_vehicle) * (uint64_t)host.s.n_vehicles)) return fail(SGP_ERR_INVALID, "sgp_world_restore: a piece is larger than its array"); continue; }
 		auto it = by_id.find(s.id);
 		if (it == by_id.end()) return fail(SGP_ERR_INVALID, "sgp_world_restore: the blob names a device array this world does not have");
 		if (s.bytes > it->second->alloc) return fail(SGP_ERR_INVALID, "sgp_world_restore: a piece is larger than its array");

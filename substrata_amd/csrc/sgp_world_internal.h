@@ -78,21 +78,65 @@ struct CompoundRec { std::vector<uint32_t> ids; std::vector<sgp_compound_child> 
 
 struct ProfEvent { int kc; hipEvent_t a, b; };
 
+// ---- the device arrays of a world ---------------------------------------------------------------------------------------------------------------------------
+// Every device allocation of a sgp_world has one record in sgp_world::arrays, made at the line that allocates the array (DEV_ALLOC, dev_array_grow below): its
+// checkpoint id, what of it is state, where it is and how large.  Allocating, growing, freeing and sgp_step_stats::device_bytes all go through the records,
+// and sgp_world_checkpoint.hip walks them (for_each_array) -- a new array is an id here and the line that allocates it.
+// What of an array is state, by kind (`stride`: bytes per counted record; the counts: CkptCounts):
+//   body      one record per body slot: the first `high` records
+//   cache     a constraint buffer; the one the LAST step solved is the contact cache (its first cache_total[buffer] slots are state), the other one scratch
+//   table     the contact cache's hash table: the first *ht_cur entries (look-ups mask with it; k_island_mark clears what a larger table adds before anything reads it)
+//   vehicles  the first n_vehicles records
+//   whole     scalars and small tables, copied whole
+//   scratch   rewritten by every step before it is read, or re-made from a host mirror that is the truth: nothing of it in a lean checkpoint (a full one copies it whole)
+//   never     no part of any checkpoint (the stage buffer)
+enum ArrayKind : char { AK_BODY = 'B', AK_CACHE = 'C', AK_TABLE = 'T', AK_VEHICLES = 'V', AK_WHOLE = 'W', AK_SCRATCH = 'S', AK_NEVER = 'N' };
+// The ids: a checkpoint blob names arrays by them, so a number is never changed or used again, and a new array takes the next free one.
+// (Arrays a world does not have -- the contact-event lists before they are asked for, the vehicle arrays before the first vehicle -- leave their ids unused.)
+enum ArrayId : uint32_t {
+	A_POSE = 1, A_VEL = 2, A_DYN = 3, A_FORCE = 4, A_TORQUE = 5, A_FLAGS = 6, A_AABB_MIN = 7, A_AABB_MAX = 8,
+	A_SLEEP_S = 9,      // + k, k < 3
+	A_SLEEP_TIMER = 12, A_SUBMERGED = 13, A_USERDATA = 14, A_COLOUR_MASK = 15, A_WARM = 16,
+	A_CLAIM = 17,       // + k, k < 2
+	A_VEH_CLAIM = 19, A_VEH_EPOCH = 20, A_ISLAND = 21, A_ISLAND_AWAKE = 22, A_AWAKE_MARK = 23, A_EXPORT_COUNTS = 24, A_CELL_HASH = 25,
+	A_CELL_COUNT = 26, A_CELL_START = 27, A_CELL_FILL = 28, A_TILE_SLOT = 29, A_TILE_OF_SLOT = 30,
+	A_LARGE = 31, A_LGRID = 32, A_LG_START = 33, A_LG_ITEMS = 34,
+	A_MESH_PAIRS = 35, A_MESH_BIG = 36, A_HULL_PAIRS = 37, A_HULL_WORK = 38, A_SORTED_MIN = 39, A_SORTED_MAX = 40,
+	A_GRID = 41, A_GRID_CELLS_USED = 42, A_BOUNDS_ACC = 43, A_SCAN_BLOCK_SUMS = 44, A_PAIRS = 45, A_WAKE_PAIRS = 46,
+	A_SLEEP_LABEL = 47, A_LABEL_WAKE = 48, A_SLOT_GEN = 49,
+	A_MAN_AB = 50, A_MAN_N = 51, A_MAN_COLOUR = 52, A_MAN_PRIO = 53, A_MAN_PREV = 54, A_MAN_SLOT = 55,
+	A_HC_ROOT = 56, A_HC_COUNT = 57, A_HC_BASE = 58, A_HC_RANK = 59, A_HC_LIST = 60, A_HC_ENTRY = 61, A_HC_BIG_LIST = 62,
+	A_ULIST = 63,       // + k, k < 2
+	A_MAN_P1 = 65, A_MAN_P2 = 66,      // + 2 k, k < 4
+	A_ROWS = 73,
+	A_CA = 74,          // + CA_IDS * buffer + one of the offsets below (alloc_constraints)
+	CA_HDR = 0, CA_N_FRIC = 1, CA_PREC = 2, CA_R1B = 3, CA_R2E = 4, CA_LAM = 5, CA_EFFT = 6, CA_LOC1 = 7, CA_LOC2 = 8,      // the last six: + 6 k, k < 4
+	CA_IDS = 27,
+	A_HT = 128, A_HT_CUR = 129, A_CACHE_TOTAL = 130, A_CSTARTS = 131, A_CTR = 132, A_EVC = 133,
+	A_EV_ACTIVATED = 134, A_EV_DEACTIVATED = 135, A_EV_WATER = 136, A_EV_CONTACTS_ADDED = 137, A_EV_CONTACTS_PERSISTED = 138, A_SP = 139,
+	A_VEHICLES = 140, A_VEH_INPUTS = 141, A_VEH_ROWS = 142, A_VEH_HEAD = 143,
+	A_MESHES = 144, A_HULLS = 145, A_MESH_VERTS = 146, A_MESH_TRIS = 147, A_MESH_TRI_MAT = 148, A_MESH_NODES = 149, A_MESH_FIELD = 150,
+	A_STAGE = 151,
+};
+struct DevArray { void* ptr; size_t bytes, counted; char kind; size_t stride; };      // counted: its share of DevArrays::bytes (what it holds, but for the vehicle heads)
+struct DevArrays {
+	std::map<uint32_t, DevArray> recs;      // by id: a walk meets them in the order of their ids, which is the order of a checkpoint's pieces
+	uint64_t bytes = 0;                     // sgp_step_stats::device_bytes
+};
+
 struct sgp_world {
 	sgp_world_desc desc;
 	int device = 0;
 	hipStream_t stream = nullptr;
 	hipStream_t capture_stream = nullptr;      // launch plans are captured here while the step they belong to already runs, issued eagerly, on `stream`
 	DV dv;
-	std::vector<void*> allocs;
-	std::unordered_map<void*, size_t> alloc_bytes;      // size of every entry of `allocs` (checkpoints: what a full copy moves, and the bound of every lean piece)
+	DevArrays arrays;                                    // every device allocation of the world (checkpoints: a record's size is what a full copy moves, and the bound of its lean piece)
 	bool checkpoint_full = false;                        // SGP_CHECKPOINT_FULL=1
 	uint64_t serial = 0;                                 // which world of this process this is (a checkpoint names the world that made it)
 	uint64_t shape_epoch = 0, shape_epoch_counter = 0;   // every shape create / destroy gives the shape tables a new epoch (a number never used before in this world): a rollback
 	                                                     //   to a checkpoint of the current epoch leaves the shape pools alone; a rollback sets the epoch back, never the counter
 	std::shared_ptr<const struct CkptShapes> shape_snapshot;      // host copy of the shape tables and pools of `shape_epoch`, shared by the checkpoints of that epoch (made by the first of them)
 	uint32_t steps_taken = 0;
-	uint64_t device_bytes = 0;
 	// host mirrors
 	std::vector<HostBody> hb;
 	std::vector<uint32_t> free_list;
@@ -196,29 +240,47 @@ struct sgp_world {
 	bool stage_ev_ok = false;
 };
 
-template <typename T> inline int dev_alloc(sgp_world* w, T*& p, size_t n)
+// Array `id` of the world gets `bytes` bytes of its own: the new array is allocated, zeroed if asked, given the first `keep` bytes of the one it replaces, and
+// once the stream has finished with the old one that is freed and the record and `p` name the new one.  (A first allocation has nothing to wait for.)  How large,
+// how much to keep and whether to zero is the caller's; so is telling whoever holds the old pointer -- DV, and through it the captured graphs.
+// uncounted: bytes at the array's end that sgp_step_stats::device_bytes has never reported (the defer bits behind the vehicle heads).  A failure leaves the old array in place.
+template <typename T> inline int dev_array_grow(sgp_world* w, uint32_t id, char kind, size_t stride, T*& p, size_t bytes, size_t keep, bool zero, size_t uncounted = 0)
 {
+	auto it = w->arrays.recs.find(id);
+	void* old = it != w->arrays.recs.end() ? it->second.ptr : nullptr;
 	void* q = nullptr;
-	const size_t bytes = (std::max<size_t>(n, 1) * sizeof(T) + 15) & ~size_t(15);      // whole 16-byte units: the checkpoint copy moves 16 bytes per lane
 	hipError_t e = hipMalloc(&q, bytes);
 	if (e != hipSuccess) return fail(SGP_ERR_HIP, "hipMalloc", e);
-	e = hipMemsetAsync(q, 0, bytes, w->stream);
-	if (e != hipSuccess) return fail(SGP_ERR_HIP, "hipMemsetAsync", e);
-	w->allocs.push_back(q);
-	w->alloc_bytes[q] = bytes;
-	w->device_bytes += bytes;
+	if (zero) e = hipMemsetAsync(q, 0, bytes, w->stream);
+	if (e == hipSuccess && old && keep) e = hipMemcpyAsync(q, old, keep, hipMemcpyDeviceToDevice, w->stream);
+	if (e == hipSuccess && old) e = hipStreamSynchronize(w->stream);
+	if (e != hipSuccess || old) hipFree(e != hipSuccess ? q : old);
+	if (e != hipSuccess) return fail(SGP_ERR_HIP, "device array", e);
+	if (old) w->arrays.bytes -= it->second.counted;
+	w->arrays.recs[id] = DevArray{ q, bytes, bytes - uncounted, kind, stride };
+	w->arrays.bytes += bytes - uncounted;
 	p = (T*)q;
 	return SGP_OK;
 }
-#define DEV_ALLOC(ptr, n) do { int r_ = dev_alloc(w, ptr, n); if (r_ != SGP_OK) return r_; } while (0)
+// ... and the arrays that never grow: `n` records, in whole 16-byte units (the checkpoint copy moves 16 bytes per lane), zeroed on the world's stream
+template <typename T> inline int dev_alloc(sgp_world* w, uint32_t id, char kind, size_t stride, T*& p, size_t n, size_t record = sizeof(T))
+{
+	return dev_array_grow(w, id, kind, stride, p, (std::max<size_t>(n, 1) * record + 15) & ~size_t(15), 0, true);
+}
+#define DEV_ALLOC(id, kind, stride, ptr, n) do { int r_ = dev_alloc(w, id, kind, stride, ptr, n); if (r_ != SGP_OK) return r_; } while (0)
+// what sgp_world_destroy does with them (the stream has been waited for)
+inline void dev_arrays_release(sgp_world* w)
+{
+	for (auto& kv : w->arrays.recs) hipFree(kv.second.ptr);
+	w->arrays.recs.clear(); w->arrays.bytes = 0;
+}
 
 inline int ensure_stage(sgp_world* w, size_t bytes)
 {
 	if (bytes > w->stage_dev_bytes) {
-		if (w->stage_dev) { hipStreamSynchronize(w->stream); hipFree(w->stage_dev); w->device_bytes -= w->stage_dev_bytes; }
 		size_t nb = std::max<size_t>(bytes, 1 << 16); nb = nb + nb / 2;
-		HIP_TRY(hipMalloc(&w->stage_dev, nb));
-		w->stage_dev_bytes = nb; w->device_bytes += nb;
+		{ int r = dev_array_grow(w, A_STAGE, AK_NEVER, 0, w->stage_dev, nb, 0, false); if (r != SGP_OK) return r; }
+		w->stage_dev_bytes = nb;
 	}
 	if (bytes > w->stage_host_bytes) {
 		if (w->stage_host) { hipStreamSynchronize(w->stream); hipHostFree(w->stage_host); }
@@ -281,6 +343,7 @@ static inline uint32_t compound_id_of(const sgp_world* w, uint32_t id, uint32_t*
 // defined in sgp_world.hip
 void ray_server_stop(sgp_world* w);      // tells a resident ray server to leave (no wait: what is launched next runs after it); called by flush_cmds
 void invalidate_graphs(sgp_world* w);
+int grow_lg_items(sgp_world* w, uint32_t cap);      // a larger item list for the static large bodies' grid (empty; graphs invalidated)
 int flush_cmds(sgp_world* w);
 int collect_events(sgp_world* w, bool counters_fresh = false);
 int flush_event_reset(sgp_world* w);      // empties the device's event counters now if the host has pulled the lists (before edits are applied, before a checkpoint)

@@ -5,16 +5,14 @@
 // static triangle meshes (MeshShapeSettings::Create, PhysicsWorld.cpp:735-1166 with is_dynamic = false)
 
 
-template <typename T> static int grow_pool(sgp_world* w, T*& dev, size_t& cap, size_t need, size_t used_before)
+// The shape pools and tables on the device are scratch to a checkpoint: their host mirrors are the truth (shapes_upload_all).
+// A pool with room for `need` records: half as much again, the first `used_before` records kept
+template <typename T> static int grow_pool(sgp_world* w, uint32_t id, T*& dev, size_t& cap, size_t need, size_t used_before)
 {
 	if (need <= cap) return SGP_OK;
-	size_t nc = std::max<size_t>(need + need / 2, 4096);
-	T* nd = nullptr;
-	HIP_TRY(hipMalloc((void**)&nd, sizeof(T) * nc));
-	if (dev && used_before) HIP_TRY(hipMemcpyAsync(nd, dev, sizeof(T) * used_before, hipMemcpyDeviceToDevice, w->stream));
-	HIP_TRY(hipStreamSynchronize(w->stream));
-	if (dev) { hipFree(dev); w->device_bytes -= sizeof(T) * cap; }
-	dev = nd; cap = nc; w->device_bytes += sizeof(T) * nc;
+	const size_t nc = std::max<size_t>(need + need / 2, 4096);
+	{ int r = dev_array_grow(w, id, AK_SCRATCH, 0, dev, sizeof(T) * nc, sizeof(T) * used_before, false); if (r != SGP_OK) return r; }
+	cap = nc;
 	return SGP_OK;
 }
 
@@ -61,17 +59,13 @@ static void give_range(std::vector<std::pair<uint32_t, uint32_t>>& free_ranges, 
 		if (free_ranges[k].first + free_ranges[k].second == free_ranges[k + 1].first) { free_ranges[k].second += free_ranges[k + 1].second; free_ranges.erase(free_ranges.begin() + (long)k + 1); } else ++k;
 	}
 }
-template <typename T> static int grow_table(sgp_world* w, T*& dev, size_t& cap, size_t need)
+// A shape table with room for `need` entries: twice as many, the old ones kept and zeroes behind them
+template <typename T> static int grow_table(sgp_world* w, uint32_t id, T*& dev, size_t& cap, size_t need)
 {
 	if (need <= cap) return SGP_OK;
 	const size_t nc = std::max(need, 2 * cap);
-	T* nd = nullptr;
-	HIP_TRY(hipMalloc((void**)&nd, sizeof(T) * nc));
-	HIP_TRY(hipMemsetAsync(nd, 0, sizeof(T) * nc, w->stream));
-	HIP_TRY(hipMemcpyAsync(nd, dev, sizeof(T) * cap, hipMemcpyDeviceToDevice, w->stream));
-	HIP_TRY(hipStreamSynchronize(w->stream));
-	hipFree(dev); w->device_bytes += sizeof(T) * (nc - cap);
-	dev = nd; cap = nc;
+	{ int r = dev_array_grow(w, id, AK_SCRATCH, 0, dev, sizeof(T) * nc, sizeof(T) * cap, true); if (r != SGP_OK) return r; }
+	cap = nc;
 	return SGP_OK;
 }
 
@@ -172,10 +166,10 @@ SGP_API int sgp_mesh_create_with_materials(sgp_world* w, const float* verts, uin
 	// (uint4.w of a triangle: its index in the caller's order, and in the top three bits its active-edge flags: MESH_TRI_INDEX / MESH_TRI_EDGES)
 	for (uint32_t k = 0; k < nt; ++k) { const uint32_t t = order[k]; w->mesh_tris[mh.tri_off + k] = make_uint4(idx[3 * t], idx[3 * t + 1], idx[3 * t + 2], t | ((uint32_t)edge_flags[t] << 29)); w->mesh_tri_mat[mh.tri_off + k] = tri_mats ? tri_mats[t] : 0u; }
 	// upload (pools may move: captured graphs carry the old pointers)
-	{ int r = grow_pool(w, w->d_mesh_verts, w->cap_mesh_verts, w->mesh_verts.size(), w->cap_mesh_verts); if (r != SGP_OK) return r; }
-	{ int r = grow_pool(w, w->d_mesh_tris, w->cap_mesh_tris, w->mesh_tris.size(), w->cap_mesh_tris); if (r != SGP_OK) return r; }
-	{ int r = grow_pool(w, w->d_mesh_tri_mat, w->cap_mesh_tri_mat, w->mesh_tri_mat.size(), w->cap_mesh_tri_mat); if (r != SGP_OK) return r; }
-	{ int r = grow_pool(w, w->d_mesh_nodes, w->cap_mesh_nodes, w->mesh_nodes.size(), w->cap_mesh_nodes); if (r != SGP_OK) return r; }
+	{ int r = grow_pool(w, A_MESH_VERTS, w->d_mesh_verts, w->cap_mesh_verts, w->mesh_verts.size(), w->cap_mesh_verts); if (r != SGP_OK) return r; }
+	{ int r = grow_pool(w, A_MESH_TRIS, w->d_mesh_tris, w->cap_mesh_tris, w->mesh_tris.size(), w->cap_mesh_tris); if (r != SGP_OK) return r; }
+	{ int r = grow_pool(w, A_MESH_TRI_MAT, w->d_mesh_tri_mat, w->cap_mesh_tri_mat, w->mesh_tri_mat.size(), w->cap_mesh_tri_mat); if (r != SGP_OK) return r; }
+	{ int r = grow_pool(w, A_MESH_NODES, w->d_mesh_nodes, w->cap_mesh_nodes, w->mesh_nodes.size(), w->cap_mesh_nodes); if (r != SGP_OK) return r; }
 	HIP_TRY(hipMemcpyAsync(w->d_mesh_verts + mh.vert_off, w->mesh_verts.data() + mh.vert_off, sizeof(float4) * nv, hipMemcpyHostToDevice, w->stream));
 	HIP_TRY(hipMemcpyAsync(w->d_mesh_tris + mh.tri_off, w->mesh_tris.data() + mh.tri_off, sizeof(uint4) * nt, hipMemcpyHostToDevice, w->stream));
 	HIP_TRY(hipMemcpyAsync(w->d_mesh_tri_mat + mh.tri_off, w->mesh_tri_mat.data() + mh.tri_off, sizeof(uint32_t) * nt, hipMemcpyHostToDevice, w->stream));
@@ -184,7 +178,7 @@ SGP_API int sgp_mesh_create_with_materials(sgp_world* w, const float* verts, uin
 	if (!w->free_mesh_ids.empty()) { id = w->free_mesh_ids.back(); w->free_mesh_ids.pop_back(); w->meshes[id] = mh; w->mesh_refs[id] = 0; }
 	else { id = (uint32_t)w->meshes.size(); w->meshes.push_back(mh); w->mesh_refs.push_back(0); }
 	w->shape_epoch = ++w->shape_epoch_counter;
-	{ int r = grow_table(w, w->d_meshes, w->cap_mesh_table, w->meshes.size()); if (r != SGP_OK) return r; }
+	{ int r = grow_table(w, A_MESHES, w->d_meshes, w->cap_mesh_table, w->meshes.size()); if (r != SGP_OK) return r; }
 	w->dv.meshes = w->d_meshes;
 	HIP_TRY(hipMemcpyAsync(&w->d_meshes[id], &w->meshes[id], sizeof(MeshHeader), hipMemcpyHostToDevice, w->stream));
 	HIP_TRY(hipStreamSynchronize(w->stream));
@@ -266,13 +260,13 @@ SGP_API int sgp_heightfield_create(sgp_world* w, const sgp_heightfield_desc* hd,
 	mh.field_off = take_range(w->free_field_ranges, mh.field_words, w->mesh_field.size());
 	if (w->mesh_field.size() < (size_t)mh.field_off + mh.field_words) w->mesh_field.resize((size_t)mh.field_off + mh.field_words);
 	std::copy(words.begin(), words.end(), w->mesh_field.begin() + mh.field_off);
-	{ int r = grow_pool(w, w->d_mesh_field, w->cap_mesh_field, w->mesh_field.size(), w->cap_mesh_field); if (r != SGP_OK) return r; }
+	{ int r = grow_pool(w, A_MESH_FIELD, w->d_mesh_field, w->cap_mesh_field, w->mesh_field.size(), w->cap_mesh_field); if (r != SGP_OK) return r; }
 	HIP_TRY(hipMemcpyAsync(w->d_mesh_field + mh.field_off, words.data(), sizeof(uint32_t) * mh.field_words, hipMemcpyHostToDevice, w->stream));
 	uint32_t id;
 	if (!w->free_mesh_ids.empty()) { id = w->free_mesh_ids.back(); w->free_mesh_ids.pop_back(); w->meshes[id] = mh; w->mesh_refs[id] = 0; }
 	else { id = (uint32_t)w->meshes.size(); w->meshes.push_back(mh); w->mesh_refs.push_back(0); }
 	w->shape_epoch = ++w->shape_epoch_counter;
-	{ int r = grow_table(w, w->d_meshes, w->cap_mesh_table, w->meshes.size()); if (r != SGP_OK) return r; }
+	{ int r = grow_table(w, A_MESHES, w->d_meshes, w->cap_mesh_table, w->meshes.size()); if (r != SGP_OK) return r; }
 	w->dv.meshes = w->d_meshes;
 	HIP_TRY(hipMemcpyAsync(&w->d_meshes[id], &w->meshes[id], sizeof(MeshHeader), hipMemcpyHostToDevice, w->stream));
 	HIP_TRY(hipStreamSynchronize(w->stream));
@@ -331,7 +325,7 @@ SGP_API int sgp_hull_create_com(sgp_world* w, const float* pts, uint32_t n, cons
 	if (!w->free_hull_ids.empty()) { id = w->free_hull_ids.back(); w->free_hull_ids.pop_back(); w->hulls[id] = h; w->hull_refs[id] = 0; }
 	else { id = (uint32_t)w->hulls.size(); w->hulls.push_back(h); w->hull_refs.push_back(0); }
 	w->shape_epoch = ++w->shape_epoch_counter;
-	{ int r = grow_table(w, w->d_hulls, w->cap_hull_table, w->hulls.size()); if (r != SGP_OK) return r; }
+	{ int r = grow_table(w, A_HULLS, w->d_hulls, w->cap_hull_table, w->hulls.size()); if (r != SGP_OK) return r; }
 	w->dv.hulls = w->d_hulls;
 	HIP_TRY(hipMemcpyAsync(&w->d_hulls[id], &w->hulls[id], sizeof(sgd_hull), hipMemcpyHostToDevice, w->stream));
 	HIP_TRY(hipStreamSynchronize(w->stream));
@@ -527,26 +521,15 @@ static inline bool vehicle_live(const sgp_world* w, uint32_t id) { return w && i
 int ensure_vehicle_capacity(sgp_world* w, uint32_t need)
 {
 	while (need > w->cap_vehicles) {
-		const uint32_t nc = w->cap_vehicles ? w->cap_vehicles * 2 : 64;
-		sgd_vehicle* nv = nullptr; sgp_vehicle_input* ni = nullptr;
-		HIP_TRY(hipMalloc((void**)&nv, sizeof(sgd_vehicle) * nc));
-		HIP_TRY(hipMalloc((void**)&ni, sizeof(sgp_vehicle_input) * nc));
-		HIP_TRY(hipMemsetAsync(nv, 0, sizeof(sgd_vehicle) * nc, w->stream));
-		HIP_TRY(hipMemsetAsync(ni, 0, sizeof(sgp_vehicle_input) * nc, w->stream));
-		if (w->n_vehicles) HIP_TRY(hipMemcpyAsync(nv, w->d_vehicles, sizeof(sgd_vehicle) * w->n_vehicles, hipMemcpyDeviceToDevice, w->stream));
-		HIP_TRY(hipStreamSynchronize(w->stream));
-		// (the row export of the solver passes is rebuilt by every step's controller kernel: nothing to carry over)
-		const size_t row_bytes = sizeof(float4) * 16u * 4u * nc, head_bytes = sizeof(float4) * 5u * nc + sizeof(uint32_t) * (nc / 32u + 4u);      // (+ one bit per slot behind the heads: DV::veh_defer_bits)
-		float4* nr = nullptr; float4* nh = nullptr;
-		HIP_TRY(hipMalloc((void**)&nr, row_bytes));
-		HIP_TRY(hipMalloc((void**)&nh, head_bytes));
-		HIP_TRY(hipMemsetAsync(nr, 0, row_bytes, w->stream));
-		HIP_TRY(hipMemsetAsync(nh, 0, head_bytes, w->stream));
-		HIP_TRY(hipStreamSynchronize(w->stream));
-		const size_t per_vehicle = sizeof(sgd_vehicle) + sizeof(sgp_vehicle_input) + sizeof(float4) * (16u * 4u + 5u);
-		if (w->d_vehicles) { hipFree(w->d_vehicles); hipFree(w->d_veh_inputs); hipFree(w->d_veh_rows); hipFree(w->d_veh_head); w->device_bytes -= per_vehicle * w->cap_vehicles; }
-		w->d_vehicles = nv; w->d_veh_inputs = ni; w->d_veh_rows = nr; w->d_veh_head = nh; w->cap_vehicles = nc;
-		w->device_bytes += per_vehicle * nc;
+		const size_t nc = w->cap_vehicles ? (size_t)w->cap_vehicles * 2 : 64;
+		// Only the records are state and carried over: the inputs have a host mirror that is uploaded again (veh_inputs_dirty), and the rows and heads the
+		// solver passes read are rebuilt by every step's controller kernel, with one bit per slot behind the heads (DV::veh_defer_bits)
+		const size_t defer_bytes = sizeof(uint32_t) * (nc / 32u + 4u);
+		{ int r = dev_array_grow(w, A_VEHICLES, AK_VEHICLES, sizeof(sgd_vehicle), w->d_vehicles, sizeof(sgd_vehicle) * nc, sizeof(sgd_vehicle) * w->n_vehicles, true); if (r != SGP_OK) return r; }
+		{ int r = dev_array_grow(w, A_VEH_INPUTS, AK_SCRATCH, 0, w->d_veh_inputs, sizeof(sgp_vehicle_input) * nc, 0, true); if (r != SGP_OK) return r; }
+		{ int r = dev_array_grow(w, A_VEH_ROWS, AK_SCRATCH, 0, w->d_veh_rows, sizeof(float4) * 16u * 4u * nc, 0, true); if (r != SGP_OK) return r; }
+		{ int r = dev_array_grow(w, A_VEH_HEAD, AK_SCRATCH, 0, w->d_veh_head, sizeof(float4) * 5u * nc + defer_bytes, 0, true, defer_bytes); if (r != SGP_OK) return r; }
+		w->cap_vehicles = (uint32_t)nc;
 		w->veh_inputs_dirty = true;
 	}
 	w->dv.vehicles = w->d_vehicles; w->dv.vehicle_inputs = w->d_veh_inputs;
@@ -559,13 +542,13 @@ int ensure_vehicle_capacity(sgp_world* w, uint32_t need)
 // crosses a shape create / destroy, and by sgp_world_restore.  Pools and tables grow through the same helpers the create calls use.
 int shapes_upload_all(sgp_world* w)
 {
-	{ int r = grow_pool(w, w->d_mesh_verts, w->cap_mesh_verts, w->mesh_verts.size(), (size_t)0); if (r != SGP_OK) return r; }
-	{ int r = grow_pool(w, w->d_mesh_tris, w->cap_mesh_tris, w->mesh_tris.size(), (size_t)0); if (r != SGP_OK) return r; }
-	{ int r = grow_pool(w, w->d_mesh_tri_mat, w->cap_mesh_tri_mat, w->mesh_tri_mat.size(), (size_t)0); if (r != SGP_OK) return r; }
-	{ int r = grow_pool(w, w->d_mesh_nodes, w->cap_mesh_nodes, w->mesh_nodes.size(), (size_t)0); if (r != SGP_OK) return r; }
-	{ int r = grow_pool(w, w->d_mesh_field, w->cap_mesh_field, w->mesh_field.size(), (size_t)0); if (r != SGP_OK) return r; }
-	{ int r = grow_table(w, w->d_meshes, w->cap_mesh_table, w->meshes.size()); if (r != SGP_OK) return r; }
-	{ int r = grow_table(w, w->d_hulls, w->cap_hull_table, w->hulls.size()); if (r != SGP_OK) return r; }
+	{ int r = grow_pool(w, A_MESH_VERTS, w->d_mesh_verts, w->cap_mesh_verts, w->mesh_verts.size(), (size_t)0); if (r != SGP_OK) return r; }
+	{ int r = grow_pool(w, A_MESH_TRIS, w->d_mesh_tris, w->cap_mesh_tris, w->mesh_tris.size(), (size_t)0); if (r != SGP_OK) return r; }
+	{ int r = grow_pool(w, A_MESH_TRI_MAT, w->d_mesh_tri_mat, w->cap_mesh_tri_mat, w->mesh_tri_mat.size(), (size_t)0); if (r != SGP_OK) return r; }
+	{ int r = grow_pool(w, A_MESH_NODES, w->d_mesh_nodes, w->cap_mesh_nodes, w->mesh_nodes.size(), (size_t)0); if (r != SGP_OK) return r; }
+	{ int r = grow_pool(w, A_MESH_FIELD, w->d_mesh_field, w->cap_mesh_field, w->mesh_field.size(), (size_t)0); if (r != SGP_OK) return r; }
+	{ int r = grow_table(w, A_MESHES, w->d_meshes, w->cap_mesh_table, w->meshes.size()); if (r != SGP_OK) return r; }
+	{ int r = grow_table(w, A_HULLS, w->d_hulls, w->cap_hull_table, w->hulls.size()); if (r != SGP_OK) return r; }
 	if (!w->mesh_verts.empty()) HIP_TRY(hipMemcpyAsync(w->d_mesh_verts, w->mesh_verts.data(), sizeof(float4) * w->mesh_verts.size(), hipMemcpyHostToDevice, w->stream));
 	if (!w->mesh_tris.empty()) HIP_TRY(hipMemcpyAsync(w->d_mesh_tris, w->mesh_tris.data(), sizeof(uint4) * w->mesh_tris.size(), hipMemcpyHostToDevice, w->stream));
 	if (!w->mesh_tri_mat.empty()) HIP_TRY(hipMemcpyAsync(w->d_mesh_tri_mat, w->mesh_tri_mat.data(), sizeof(uint32_t) * w->mesh_tri_mat.size(), hipMemcpyHostToDevice, w->stream));
