@@ -415,6 +415,11 @@ int  sgp_world_dump_constraints(sgp_world* w, void* out, uint32_t cap, uint32_t*
 /* ---- queries --------------------------------------------------------------------------------- */
 /* traceRay / traceRayAgainstCollidableObs / doesRayHitAnything (PhysicsWorld.cpp:1668-1725), batched. */
 int  sgp_raycast(sgp_world* w, const sgp_ray* rays, uint32_t n, sgp_hit* hits_out);
+/* "Does this ray hit anything within max_t" (what doesRayHitAnything keeps of a ray: JPH::NarrowPhaseQuery::CastRay with the plain result, which may stop
+ * at the first hit), batched: hit_out[i] is 1 or 0 and equals (sgp_raycast's hits_out[i].id != SGP_INVALID_ID) for the same ray -- the same stages, filters
+ * (alive, ignore_id, collidable_only) and per-shape tests, leaving at the first accepted hit: no closest hit, normal, triangle or barycentrics.  One thread
+ * per ray whatever n is: like every query it flushes pending edits, and it tells a resident ray server to leave instead of using it. */
+int  sgp_raycast_any(sgp_world* w, const sgp_ray* rays, uint32_t n, uint8_t* hit_out);
 
 /* ---- convex hull shapes ---------------------------------------------------------
  * Replaces JPH::ConvexHullShapeSettings(points).Create() (+ OffsetCenterOfMassShape / the principal-axes decomposition Jolt does
@@ -1354,6 +1359,149 @@ int  sgp_proximity_rollback(sgp_proximity* pb, const sgp_batch_checkpoint* cp);
  * live and contains p; else the live zone of the lowest key that contains p; else SGP_INVALID_ID.  mins / maxs: n * 3 floats; live: n words. */
 int  sgp_proximity_test_point(const float mn[3], const float mx[3], const float p[3], float radius, uint32_t* near_out, float* dist2_out);
 int  sgp_proximity_pick_zone(const float* mins, const float* maxs, const uint32_t* keys, const uint32_t* live, uint32_t n, uint32_t current, const float p[3], uint32_t* zone_out);
+
+/* ---- batched audio sources: range, occlusion, muting (the two audio walks of GUIClient) ----
+ * A batch of audio sources and up to SGP_AUD_MAX_LISTENERS listeners that belongs to one world and lives on the device.  sgp_audibility_update
+ * runs, for every (source, listener) pair, the range walk of GUIClient.cpp:4512-4543 (checkForAudioRangeChanges) and, for the pairs in range,
+ * the occlusion and muting walk of GUIClient.cpp:6973-7034: one any-hit ray from the listener towards the source (sgp_raycast_any's search) and
+ * the mute ramp of AudioSource::startMuting / startUnmuting / updateCurrentMuteVolumeFactor (audio/AudioEngine.cpp:79-121).  Per pair the range
+ * bit, the occlusion bit, the five ramp variables and the last distance stay on the device between updates; only transitions become events.
+ * The arithmetic is written out in docs/CONTRACT.md 4m.  What is left out: docs/GAPS.md ("Audio sources").  A world checkpoint holds nothing
+ * of a batch (sgp_audibility_checkpoint / _rollback do, by the rule of the batch checkpoints above, with SGP_BATCH_AUDIBILITY); tiled worlds
+ * are refused. */
+typedef struct sgp_audibility sgp_audibility;
+#define SGP_BATCH_AUDIBILITY 6u
+#define SGP_AUD_MAX_LISTENERS 32
+#define SGP_AUDIBILITY_MAX_SOURCES (1u << 20)
+#define SGP_AUDIBILITY_MAX_PAIRS   (1u << 22)     /* source_capacity * listener_capacity                                                 */
+#define SGP_AUD_SRC_POINT 0u          /* the source is where the host puts it                                                  */
+#define SGP_AUD_SRC_BODY  1u          /* the source is the centroid of a body's world AABB (getCentroidWS), read on the device */
+#define SGP_AUD_LST_POINT 0u          /* the listener is where the host puts it                                                */
+#define SGP_AUD_LST_BODY  1u          /* the listener is a body's position plus a world-space offset, read on the device       */
+#define SGP_AUD_ONE_SHOT       1u     /* SourceType_NonStreaming && !looping: never muted (GUIClient.cpp:7010-7011)            */
+#define SGP_AUD_WANT_RANGE     2u     /* IN_RANGE / OUT_OF_RANGE are wanted                                                    */
+#define SGP_AUD_WANT_OCCLUSION 4u     /* OCCLUDED / UNOCCLUDED are wanted (sourceNumOcclusionsUpdated where the number changed) */
+#define SGP_AUD_WANT_VOLUME    8u     /* VOLUME is wanted (sourceVolumeUpdated)                                                */
+#define SGP_AUD_ST_BODY_GONE 1u       /* the body is no longer the one the source was added on: the source is frozen           */
+#define SGP_AUD_LST_ST_BODY_GONE 1u   /* a body-sourced listener whose body has gone: its pairs are frozen                     */
+#define SGP_AUD_EV_IN_RANGE     1u
+#define SGP_AUD_EV_OUT_OF_RANGE 2u
+#define SGP_AUD_EV_OCCLUDED     3u
+#define SGP_AUD_EV_UNOCCLUDED   4u
+#define SGP_AUD_EV_VOLUME       5u
+#define SGP_AUD_PAIR_IN_RANGE 1u      /* sgp_audibility_pair_state::bits                                                       */
+#define SGP_AUD_PAIR_OCCLUDED 2u
+typedef struct sgp_audibility_source {
+	uint32_t kind;                 /* SGP_AUD_SRC_POINT | SGP_AUD_SRC_BODY                                              */
+	uint32_t body;                 /* BODY: a live body (no compound, ghost or alias slot, no other source of the batch on it) */
+	float    pos[3];               /* POINT: where the source is                                                        */
+	float    volume;               /* finite, >= 0: audible up to 60 * volume metres                                    */
+	uint32_t zone_key;             /* AudioSource::userdata_1, the parcel the source belongs to; SGP_INVALID_ID: none   */
+	uint32_t flags;                /* SGP_AUD_ONE_SHOT | SGP_AUD_WANT_*                                                 */
+	uint64_t tag;                  /* the caller's AudioSource*: not interpreted, reported with every event             */
+} sgp_audibility_source;
+typedef struct sgp_audibility_listener {
+	uint32_t source;               /* SGP_AUD_LST_POINT | SGP_AUD_LST_BODY                                              */
+	uint32_t body;                 /* BODY: a live body (no compound, ghost or alias slot)                              */
+	float    pos[3];               /* POINT: where the listener is                                                      */
+	float    offset[3];            /* BODY: added to the body's position, in world space                                */
+	uint32_t ignore_body;          /* the rays' ignore_id; SGP_INVALID_ID: nothing (the reference ignores nothing)      */
+	uint32_t zone_key;             /* the parcel the listener stands in, SGP_INVALID_ID: none (a proximity batch attached: taken from its observer) */
+	uint32_t mute_outside;         /* that parcel has MUTE_OUTSIDE_AUDIO_FLAG (a proximity batch attached: looked up in the muting keys) */
+	uint32_t reserved_;
+} sgp_audibility_listener;
+typedef struct sgp_audibility_event {
+	uint32_t kind;                 /* SGP_AUD_EV_*                                                                      */
+	uint32_t source;               /* the source's id                                                                   */
+	uint32_t listener;
+	float    factor;               /* VOLUME: the pair's new mute_volume_factor; else 0                                 */
+	uint64_t tag;                  /* the source's                                                                      */
+	uint32_t update_index;         /* the update of the batch that raised it, counted from 0                            */
+	uint32_t reserved_;
+} sgp_audibility_event;
+typedef struct sgp_audibility_state {
+	uint32_t status;               /* SGP_AUD_ST_*                                                                      */
+	float    pos[3];               /* the position the last update used                                                 */
+	uint32_t in_range_mask;        /* bit l: in audio range of listener l (in_audio_proximity)                          */
+	uint32_t occluded_mask;        /* bit l: num_occlusions == 1 for listener l                                         */
+} sgp_audibility_state;
+typedef struct sgp_audibility_pair_state {
+	uint32_t bits;                 /* SGP_AUD_PAIR_*                                                                    */
+	float    mute_volume_factor;   /* 1 until the pair's ramp has run                                                   */
+	float    dist;                 /* of the last update that traced the pair; 0 before                                 */
+} sgp_audibility_pair_state;
+typedef struct sgp_audibility_listener_state {
+	float    pos[3];               /* where the last update found the listener                                          */
+	uint32_t zone_key;             /* the key it used                                                                   */
+	uint32_t mute_outside;
+	uint32_t update_index;         /* updates this listener has run                                                     */
+	uint32_t status;               /* SGP_AUD_LST_ST_*                                                                  */
+} sgp_audibility_listener_state;
+typedef struct sgp_audibility_ramp {      /* the five ramp variables of AudioSource (AudioEngine.h:136-140)            */
+	double   mute_change_start_time;
+	double   mute_change_end_time;
+	float    mute_volume_factor;
+	float    mute_vol_fac_start;
+	float    mute_vol_fac_end;
+	uint32_t reserved_;
+} sgp_audibility_ramp;
+/* source_capacity in 1 .. SGP_AUDIBILITY_MAX_SOURCES, listener_capacity in 1 .. SGP_AUD_MAX_LISTENERS, their product at most
+ * SGP_AUDIBILITY_MAX_PAIRS, event_capacity >= 1: event records the batch holds between two drains.  SGP_ERR_INVALID for a world that holds
+ * ghost bodies. */
+int  sgp_audibility_create(sgp_world* w, uint32_t source_capacity, uint32_t listener_capacity, uint32_t event_capacity, sgp_audibility** out);
+/* After sgp_world_destroy of its world this still frees the batch and returns SGP_OK; every other call on such a batch is SGP_ERR_INVALID. */
+int  sgp_audibility_destroy(sgp_audibility* ab);
+/* n sources at once, all or none: ids_out[i] is the id of descs[i].  A new source starts as AudioSource's constructor leaves it, for every
+ * listener: out of range, not occluded, factor 1, start time -2, end time -1, start and end factor 1.  SGP_ERR_INVALID, with nothing added,
+ * for an unknown kind or flag, a volume or position that is not finite (or a volume < 0), a body that does not qualify, carries a source of
+ * the batch already or is named twice; SGP_ERR_CAPACITY when the n do not all fit. */
+int  sgp_audibility_add(sgp_audibility* ab, const sgp_audibility_source* descs, uint32_t n, uint32_t* ids_out);
+int  sgp_audibility_remove(sgp_audibility* ab, uint32_t id);      /* fires nothing */
+/* Moves POINT sources first .. first + n - 1 (all must be live POINT sources): a host write, uploaded by the next update. */
+int  sgp_audibility_set_points(sgp_audibility* ab, uint32_t first, uint32_t n, const float* xyz);
+int  sgp_audibility_set_volume(sgp_audibility* ab, uint32_t id, float volume);
+/* SGP_AUD_ONE_SHOT | SGP_AUD_WANT_* of a live source.  The pairs' state is not touched: a transition that passed while a flag was off is not replayed. */
+int  sgp_audibility_set_flags(sgp_audibility* ab, uint32_t id, uint32_t flags);
+/* Listener k < listener_capacity.  A slot that held no listener gets a NEW one: every pair of it starts as the constructor leaves it.  On a
+ * slot that holds one, everything but the pairs' state changes.  SGP_ERR_INVALID for a non-finite value, an unknown source, a body that does
+ * not qualify. */
+int  sgp_audibility_set_listener(sgp_audibility* ab, uint32_t k, const sgp_audibility_listener* in);
+/* Forgets every pair of the listener; fires no events. */
+int  sgp_audibility_remove_listener(sgp_audibility* ab, uint32_t k);
+/* Moves POINT listeners first .. first + n - 1 (all must be live POINT listeners). */
+int  sgp_audibility_set_listener_points(sgp_audibility* ab, uint32_t first, uint32_t n, const float* xyz);
+/* The parcel listener k stands in and whether it mutes outside audio: what holds while no proximity batch is attached. */
+int  sgp_audibility_set_listener_zone(sgp_audibility* ab, uint32_t k, uint32_t zone_key, uint32_t mute_outside);
+/* The transition period of startMuting / startUnmuting in seconds, finite and >= 0 (the reference passes 1, the default). */
+int  sgp_audibility_set_transition(sgp_audibility* ab, double seconds);
+/* With a proximity batch of the same world attached, listener k takes its zone_key on the device from observer k of that batch -- the key its
+ * last launched update left (SGP_INVALID_ID while that observer has run no update) -- and mute_outside is "the key is one of the muting keys".
+ * Both batches enqueue on the world's stream: enqueue order is the order.  NULL detaches; destroying an attached proximity batch is the
+ * caller's error.  Configuration: not part of a batch checkpoint, like the muting keys. */
+int  sgp_audibility_attach_proximity(sgp_audibility* ab, sgp_proximity* pb_or_null);
+/* The zone keys whose parcel has MUTE_OUTSIDE_AUDIO_FLAG: strictly ascending, none SGP_INVALID_ID, at most SGP_PROXIMITY_MAX_ZONES. */
+int  sgp_audibility_set_muting_keys(sgp_audibility* ab, const uint32_t* keys, uint32_t n);
+/* One update at the caller's clock `cur_time` (finite): flushes pending body edits, makes the query grid valid, uploads what the host
+ * changed and enqueues eight launches on the world's stream -- no wait, no copy to the host, no allocation.  Nothing is launched, and the
+ * update index stays, while the batch has no live source or no live listener.  No body and nothing a step reads is altered. */
+int  sgp_audibility_update(sgp_audibility* ab, double cur_time);
+/* The events since the last drain in the order of the updates that raised them; within one update by ascending source id, then ascending
+ * listener, then kind: IN_RANGE or OUT_OF_RANGE, OCCLUDED or UNOCCLUDED, VOLUME.  Waits.  *n_out = records held (<= cap are written; all are
+ * consumed), *n_dropped = events that did not fit event_capacity since the last drain: always the LAST of that order. */
+int  sgp_audibility_drain_events(sgp_audibility* ab, sgp_audibility_event* out, uint32_t cap, uint32_t* n_out, uint32_t* n_dropped);
+/* Wait for the updates in flight.  Slots that are not live read as zeroes.  get_pair_states: n sources from `first`, listener_capacity
+ * records each (source-major); a pair without a live listener or source reads as bits 0, factor 1, dist 0. */
+int  sgp_audibility_get_states(sgp_audibility* ab, uint32_t first, uint32_t n, sgp_audibility_state* out);
+int  sgp_audibility_get_pair_states(sgp_audibility* ab, uint32_t first, uint32_t n, sgp_audibility_pair_state* out);
+int  sgp_audibility_get_listeners(sgp_audibility* ab, uint32_t first, uint32_t n, sgp_audibility_listener_state* out);
+int  sgp_audibility_checkpoint(sgp_audibility* ab, sgp_batch_checkpoint** io);
+int  sgp_audibility_rollback(sgp_audibility* ab, const sgp_batch_checkpoint* cp);
+/* The arithmetic of an update on the host, bit-equal to the device (no world, no device; CONTRACT 4m steps 1-3).  pair_ray: one pair's range
+ * decision from `in_range_before` and, where the pair is traced (*traced_out = 1), its distance, unit direction and trace length (else those
+ * three are 0).  ramp_step: startMuting (mute != 0) or startUnmuting, then updateCurrentMuteVolumeFactor; *changed_out = the factor changed. */
+int  sgp_audibility_pair_ray(const float source_pos[3], const float listener_pos[3], float volume, uint32_t in_range_before,
+                             uint32_t* in_range_out, uint32_t* traced_out, float* dist_out, float dir_out[3], float* trace_out);
+int  sgp_audibility_ramp_step(sgp_audibility_ramp* io, uint32_t mute, double cur_time, double transition, uint32_t* changed_out);
 
 #ifdef __cplusplus
 }

@@ -376,6 +376,49 @@ class ProximityObserverState(C.Structure):
     _fields_ = [("pos", f32 * 3), ("zone_key", u32), ("update_index", u32), ("status", u32)]
 
 
+AUD_MAX_LISTENERS, AUDIBILITY_MAX_SOURCES, AUDIBILITY_MAX_PAIRS = 32, 1 << 20, 1 << 22      # SGP_AUD_MAX_LISTENERS, SGP_AUDIBILITY_MAX_*
+AUD_SRC_POINT, AUD_SRC_BODY = 0, 1                                        # SGP_AUD_SRC_*
+AUD_LST_POINT, AUD_LST_BODY = 0, 1                                        # SGP_AUD_LST_*
+AUD_ONE_SHOT, AUD_WANT_RANGE, AUD_WANT_OCCLUSION, AUD_WANT_VOLUME = 1, 2, 4, 8
+AUD_ST_BODY_GONE, AUD_LST_ST_BODY_GONE = 1, 1
+AUD_PAIR_IN_RANGE, AUD_PAIR_OCCLUDED = 1, 2                               # SGP_AUD_PAIR_*
+AUD_EV = {"IN_RANGE": 1, "OUT_OF_RANGE": 2, "OCCLUDED": 3, "UNOCCLUDED": 4, "VOLUME": 5}      # SGP_AUD_EV_*
+
+
+class AudibilitySource(C.Structure):
+    """sgp_audibility_source: one audio source of an audibility batch."""
+    _fields_ = [("kind", u32), ("body", u32), ("pos", f32 * 3), ("volume", f32), ("zone_key", u32), ("flags", u32), ("tag", u64)]
+
+
+class AudibilityListener(C.Structure):
+    """sgp_audibility_listener: where a listener is, what its rays ignore, the parcel it stands in."""
+    _fields_ = [("source", u32), ("body", u32), ("pos", f32 * 3), ("offset", f32 * 3), ("ignore_body", u32), ("zone_key", u32), ("mute_outside", u32),
+                ("reserved_", u32)]
+
+
+class AudibilityEvent(C.Structure):
+    """sgp_audibility_event: a range, occlusion or volume transition of one (source, listener) pair."""
+    _fields_ = [("kind", u32), ("source", u32), ("listener", u32), ("factor", f32), ("tag", u64), ("update_index", u32), ("reserved_", u32)]
+
+
+class AudibilityState(C.Structure):
+    _fields_ = [("status", u32), ("pos", f32 * 3), ("in_range_mask", u32), ("occluded_mask", u32)]
+
+
+class AudibilityPairState(C.Structure):
+    _fields_ = [("bits", u32), ("mute_volume_factor", f32), ("dist", f32)]
+
+
+class AudibilityListenerState(C.Structure):
+    _fields_ = [("pos", f32 * 3), ("zone_key", u32), ("mute_outside", u32), ("update_index", u32), ("status", u32)]
+
+
+class AudibilityRamp(C.Structure):
+    """sgp_audibility_ramp: the five ramp variables of AudioSource."""
+    _fields_ = [("mute_change_start_time", C.c_double), ("mute_change_end_time", C.c_double), ("mute_volume_factor", f32), ("mute_vol_fac_start", f32),
+                ("mute_vol_fac_end", f32), ("reserved_", u32)]
+
+
 class CompoundChild(C.Structure):
     _fields_ = [("shape_type", i32), ("shape", f32 * 4), ("pos", f32 * 3), ("rot", f32 * 4)]
 
@@ -397,6 +440,7 @@ class CheckpointInfo(C.Structure):
 
 
 BATCH_CHARACTERS, BATCH_PARTICLES, BATCH_CRAFTS, BATCH_MOVERS, BATCH_PROXIMITY = 1, 2, 3, 4, 5
+BATCH_AUDIBILITY = 6
 
 
 class BatchCheckpointInfo(C.Structure):
@@ -423,7 +467,9 @@ ABI_SIZEOF_APPENDED = ["sgp_shape_query", None, "sgp_shape_cast", "sgp_cast_hit"
                        None, "sgp_path_waypoint", "sgp_path_segment", "sgp_path_progress", "sgp_mover_desc", "sgp_mover_state",      # (37 likewise)
                        None, "sgp_batch_checkpoint_info",      # (43 likewise)
                        None, "sgp_proximity_object", "sgp_proximity_observer", "sgp_proximity_event", "sgp_proximity_state",      # (45 likewise)
-                       "sgp_proximity_observer_state"]
+                       "sgp_proximity_observer_state",
+                       None, "sgp_audibility_source", "sgp_audibility_listener", "sgp_audibility_event", "sgp_audibility_state",      # (51 likewise)
+                       "sgp_audibility_pair_state", "sgp_audibility_listener_state", "sgp_audibility_ramp"]
 ABI_SIZEOF_ALL = ABI_SIZEOF_ORDER + ABI_SIZEOF_APPENDED
 
 STRUCTS = {"sgp_settings": Settings, "sgp_world_desc": WorldDesc, "sgp_body_desc": BodyDesc,
@@ -440,7 +486,10 @@ STRUCTS = {"sgp_settings": Settings, "sgp_world_desc": WorldDesc, "sgp_body_desc
            "sgp_path_waypoint": PathWaypoint, "sgp_path_segment": PathSegment, "sgp_path_progress": PathProgress,
            "sgp_mover_desc": MoverDesc, "sgp_mover_state": MoverState, "sgp_batch_checkpoint_info": BatchCheckpointInfo,
            "sgp_proximity_object": ProximityObject, "sgp_proximity_observer": ProximityObserver, "sgp_proximity_event": ProximityEvent,
-           "sgp_proximity_state": ProximityState, "sgp_proximity_observer_state": ProximityObserverState}
+           "sgp_proximity_state": ProximityState, "sgp_proximity_observer_state": ProximityObserverState,
+           "sgp_audibility_source": AudibilitySource, "sgp_audibility_listener": AudibilityListener, "sgp_audibility_event": AudibilityEvent,
+           "sgp_audibility_state": AudibilityState, "sgp_audibility_pair_state": AudibilityPairState,
+           "sgp_audibility_listener_state": AudibilityListenerState, "sgp_audibility_ramp": AudibilityRamp}
 
 body_desc_dtype = np.dtype(BodyDesc)
 body_state_dtype = np.dtype(BodyState)
@@ -475,6 +524,11 @@ proximity_object_dtype = np.dtype(ProximityObject)
 proximity_event_dtype = np.dtype(ProximityEvent)
 proximity_state_dtype = np.dtype(ProximityState)
 proximity_observer_state_dtype = np.dtype(ProximityObserverState)
+audibility_source_dtype = np.dtype(AudibilitySource)
+audibility_event_dtype = np.dtype(AudibilityEvent)
+audibility_state_dtype = np.dtype(AudibilityState)
+audibility_pair_state_dtype = np.dtype(AudibilityPairState)
+audibility_listener_state_dtype = np.dtype(AudibilityListenerState)
 compound_child_dtype = np.dtype(CompoundChild)
 migration_dtype = np.dtype(Migration)
 
@@ -538,6 +592,7 @@ PROTOTYPES = {
     "world_num_bodies": (C.c_int, [vp, P(u32)]),
     "world_body_counts": (C.c_int, [vp, P(BodyCounts)]),
     "raycast": (C.c_int, [vp, vp, u32, vp]),
+    "raycast_any": (C.c_int, [vp, vp, u32, vp]),      # rays, n, one byte per ray out (1 = hits something within max_t)
     "collide_capsules": (C.c_int, [vp, vp, u32, vp, u32, P(u32)]),
     "spherecast": (C.c_int, [vp, vp, vp, u32, vp]),
     "collide_shapes": (C.c_int, [vp, vp, u32, vp, u32, P(u32)]),
@@ -654,6 +709,29 @@ PROTOTYPES = {
     "proximity_rollback": (C.c_int, [vp, vp]),
     "proximity_test_point": (C.c_int, [P(f32), P(f32), P(f32), f32, P(u32), P(f32)]),
     "proximity_pick_zone": (C.c_int, [vp, vp, vp, vp, u32, u32, P(f32), P(u32)]),
+    "audibility_create": (C.c_int, [vp, u32, u32, u32, P(vp)]),
+    "audibility_destroy": (C.c_int, [vp]),
+    "audibility_add": (C.c_int, [vp, vp, u32, vp]),
+    "audibility_remove": (C.c_int, [vp, u32]),
+    "audibility_set_points": (C.c_int, [vp, u32, u32, vp]),
+    "audibility_set_volume": (C.c_int, [vp, u32, f32]),
+    "audibility_set_flags": (C.c_int, [vp, u32, u32]),
+    "audibility_set_listener": (C.c_int, [vp, u32, P(AudibilityListener)]),
+    "audibility_remove_listener": (C.c_int, [vp, u32]),
+    "audibility_set_listener_points": (C.c_int, [vp, u32, u32, vp]),
+    "audibility_set_listener_zone": (C.c_int, [vp, u32, u32, u32]),
+    "audibility_set_transition": (C.c_int, [vp, C.c_double]),
+    "audibility_attach_proximity": (C.c_int, [vp, vp]),
+    "audibility_set_muting_keys": (C.c_int, [vp, vp, u32]),
+    "audibility_update": (C.c_int, [vp, C.c_double]),
+    "audibility_drain_events": (C.c_int, [vp, vp, u32, P(u32), P(u32)]),
+    "audibility_get_states": (C.c_int, [vp, u32, u32, vp]),
+    "audibility_get_pair_states": (C.c_int, [vp, u32, u32, vp]),
+    "audibility_get_listeners": (C.c_int, [vp, u32, u32, vp]),
+    "audibility_checkpoint": (C.c_int, [vp, P(vp)]),
+    "audibility_rollback": (C.c_int, [vp, vp]),
+    "audibility_pair_ray": (C.c_int, [P(f32), P(f32), f32, u32, P(u32), P(u32), P(f32), P(f32), P(f32)]),
+    "audibility_ramp_step": (C.c_int, [P(AudibilityRamp), u32, C.c_double, C.c_double, P(u32)]),
     "movers_checkpoint": (C.c_int, [vp, P(vp)]),
     "movers_rollback": (C.c_int, [vp, vp]),
     "batch_checkpoint_destroy": (C.c_int, [vp]),

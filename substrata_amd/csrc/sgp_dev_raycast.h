@@ -225,3 +225,167 @@ SGP_DEV sgp_hit raycast_one(const DV& d, const sgp_ray& ry)
 	h.userdata = 0;
 	return h;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// any-hit rays (JPH::NarrowPhaseQuery::CastRay with the plain result, which PhysicsWorld::doesRayHitAnything calls): "does this ray hit anything
+// within max_t".  The same three stages in the same order, the same filters and the same per-shape expressions as ray_body / ray_test_body /
+// raycast_one above, every one of them under the cut-off max_t (the closest-hit search runs them under a cut-off it shrinks from max_t; each
+// test accepts under a larger cut-off what it accepts under a smaller one, docs/GAPS.md), leaving at the first accepted hit: no normal, no
+// RaySub, no best-so-far.  raycast_any_one(d, ry) == (raycast_one(d, ry).id != SGP_INVALID_ID).
+
+SGP_DEV bool ray_body_any(const DV& d, uint32_t type, float4 sh, v3 pos, quat q, v3 o, v3 dir, float max_t)
+{
+	const m33 R = quat_to_m33(q);
+	const v3 ol = m33_tmul(R, v3_sub(o, pos)), dl = m33_tmul(R, dir);
+	if (type == SGP_SHAPE_MESH) {
+		const MeshHeader mh = d.meshes[(uint32_t)sh.x];
+		// a height field goes through field_cast as it is (its walk keeps a closest hit; only the answer's presence is used)
+		if (mh.kind == MESH_KIND_FIELD) return field_cast(d.mesh_field, mh, ol, dl, 0.0f, max_t, true).tri != 0xFFFFFFFFu;
+		const v3 inv = V3(fabsf(dl.x) > 1.0e-12f ? 1.0f / dl.x : 3.0e38f, fabsf(dl.y) > 1.0e-12f ? 1.0f / dl.y : 3.0e38f, fabsf(dl.z) > 1.0e-12f ? 1.0f / dl.z : 3.0e38f);
+		uint32_t stack[48]; int sp = 0;
+		stack[sp++] = 0;
+		while (sp > 0) {
+			const MeshNode nd = d.mesh_nodes[mh.node_off + stack[--sp]];
+			// the slab test of ray_body's walk, under max_t
+			const float g = 1.0e-4f * (1.0f + fabsf(nd.mxx) + fabsf(nd.mxy) + fabsf(nd.mxz) + fabsf(nd.mnx) + fabsf(nd.mny) + fabsf(nd.mnz));
+			float t0 = 0.0f, t1 = max_t; bool miss = false;
+			const float lo3[3] = { nd.mnx - g, nd.mny - g, nd.mnz - g }, hi3[3] = { nd.mxx + g, nd.mxy + g, nd.mxz + g };
+			const float o3[3] = { ol.x, ol.y, ol.z }, d3[3] = { dl.x, dl.y, dl.z }, i3[3] = { inv.x, inv.y, inv.z };
+			for (int a = 0; a < 3 && !miss; ++a) {
+				if (fabsf(d3[a]) <= 1.0e-12f) { if (o3[a] < lo3[a] || o3[a] > hi3[a]) miss = true; }
+				else { float ta = (lo3[a] - o3[a]) * i3[a], tb = (hi3[a] - o3[a]) * i3[a]; if (ta > tb) { const float tmp = ta; ta = tb; tb = tmp; } t0 = fmaxf(t0, ta - g); t1 = fminf(t1, tb + g); if (t0 > t1) miss = true; }
+			}
+			if (miss) continue;
+			if (nd.count == 0) { if (sp + 2 <= 48) { stack[sp++] = nd.left; stack[sp++] = nd.right; } continue; }
+			for (uint32_t k = 0; k < nd.count; ++k) {
+				const MeshTri tr = mesh_tri(d, mh, nd.left + k);
+				if (sgd_ray_tri_uv(ol, dl, tr.a, tr.b, tr.c, max_t, (float*)0) >= 0.0f) return true;      // the first triangle that answers
+			}
+		}
+		return false;
+	}
+	if (type == SGP_SHAPE_HULL) {
+		v3 nl;
+		return sgd_ray_hull(body_hull(d, sh), ol, dl, max_t, 0.0f, &nl) >= 0.0f;
+	}
+	if (type == SGP_SHAPE_SPHERE) {
+		const float r = sh.x;
+		const float B = v3_dot(ol, dl), C = v3_len_sq(ol) - r * r;
+		if (C <= 0.0f) return true;
+		const float disc = B * B - C;
+		if (disc < 0.0f) return false;
+		const float t = -B - sqrtf(disc);
+		return !(t < 0.0f || t > max_t);
+	}
+	if (type == SGP_SHAPE_BOX) {
+		const v3 h = V3(sh.x, sh.y, sh.z);
+		float t0 = 0.0f, t1 = max_t;
+		for (int k = 0; k < 3; ++k) {
+			const float ok = v3_get(ol, k), dk = v3_get(dl, k), hk = v3_get(h, k);
+			if (fabsf(dk) < 1.0e-12f) { if (ok < -hk || ok > hk) return false; continue; }
+			float ta = (-hk - ok) / dk, tb = (hk - ok) / dk;
+			if (ta > tb) { const float tmp = ta; ta = tb; tb = tmp; }
+			if (ta > t0) t0 = ta;
+			if (tb < t1) t1 = tb;
+			if (t0 > t1) return false;
+		}
+		return true;
+	}
+	{
+		const float r = sh.x, hh = sh.y;
+		{
+			const v3 qq = sgd_closest_on_segment(V3(0.0f, 0.0f, -hh), V3(0.0f, 0.0f, hh), ol);
+			if (v3_len_sq(v3_sub(ol, qq)) <= r * r) return true;
+		}
+		const float a = dl.x * dl.x + dl.y * dl.y;
+		const float bq = ol.x * dl.x + ol.y * dl.y, c = ol.x * ol.x + ol.y * ol.y - r * r;
+		if (a > 1.0e-12f) {
+			const float disc = bq * bq - a * c;
+			if (disc >= 0.0f) {
+				const float t = (-bq - sqrtf(disc)) / a;
+				const float z = ol.z + dl.z * t;
+				if (t >= 0.0f && t <= max_t && fabsf(z) <= hh) return true;
+			}
+		}
+		for (int sgn = -1; sgn <= 1; sgn += 2) {
+			const v3 oc = V3(ol.x, ol.y, ol.z - (float)sgn * hh);
+			const float B = v3_dot(oc, dl), C = v3_len_sq(oc) - r * r;
+			const float disc = B * B - C;
+			if (disc < 0.0f) continue;
+			const float t = -B - sqrtf(disc);
+			if (t < 0.0f || t > max_t) continue;
+			return true;
+		}
+		return false;
+	}
+}
+
+// body i: the filters and the bounds test of ray_test_body, then the shape
+SGP_DEV bool ray_any_test_body(const DV& d, const sgp_ray& ry, v3 o, v3 dir, uint32_t i)
+{
+	if (i == ry.ignore_id) return false;
+	const uint32_t f = d.flags[i];
+	if (!(f & BF_ALIVE) || (f & BF_ALIAS)) return false;
+	const uint32_t layer = f_layer(f);
+	if (ry.collidable_only && !(layer == SGP_LAYER_NON_MOVING || layer == SGP_LAYER_MOVING)) return false;
+	if (!ray_aabb(o, dir, d.aabb_min[i], d.aabb_max[i], ry.max_t)) return false;
+	return ray_body_any(d, f_shape(f), d.pose[POSE_F4 * (size_t)i + 3], V3(d.pose[POSE_F4 * (size_t)i]), Q4(d.pose[POSE_F4 * (size_t)i + 1]), o, dir, ry.max_t);
+}
+
+// one ray against the world, first hit wins: large bodies, the static large bodies' grid, then the DDA walk of the cell grid (raycast_one's walk with
+// its cut-off held at max_t)
+SGP_DEV bool raycast_any_one(const DV& d, const sgp_ray& ry)
+{
+	const v3 o = V3(ry.origin[0], ry.origin[1], ry.origin[2]), dir = V3(ry.dir[0], ry.dir[1], ry.dir[2]);
+	for (uint32_t l = 0; l < d.sp->n_large; ++l) if (ray_any_test_body(d, ry, o, dir, d.large_ids[l])) return true;
+	{
+		// (large_grid_ray walks up to *cut, which a hit pulls below every cell's entry distance: the walk ends at its next cell)
+		float cut = ry.max_t; bool hit = false;
+		large_grid_ray(d, o, dir, &cut, [&](uint32_t i) { if (!hit && ray_any_test_body(d, ry, o, dir, i)) { hit = true; cut = -3.0e38f; } });
+		if (hit) return true;
+	}
+	const BpGrid g = *d.grid;
+	if (!(g.n_cells > 0 && g.min_x <= g.max_x)) return false;
+	const float c = g.cell;
+	const v3 lo = V3(g.ox - c, g.oy - c, g.oz - c);
+	const v3 hi = V3(g.ox + ((float)g.nx + 1.0f) * c, g.oy + ((float)g.ny + 1.0f) * c, g.oz + ((float)g.nz + 1.0f) * c);
+	float t0 = 0.0f, t1 = ry.max_t;
+	const float oo[3] = { o.x, o.y, o.z }, dd[3] = { dir.x, dir.y, dir.z };
+	const float bl[3] = { lo.x, lo.y, lo.z }, bh[3] = { hi.x, hi.y, hi.z };
+	for (int a = 0; a < 3; ++a) {
+		if (fabsf(dd[a]) < 1.0e-12f) { if (oo[a] < bl[a] || oo[a] > bh[a]) return false; }
+		else {
+			float ta = (bl[a] - oo[a]) / dd[a], tb = (bh[a] - oo[a]) / dd[a];
+			if (ta > tb) { const float tmp = ta; ta = tb; tb = tmp; }
+			t0 = fmaxf(t0, ta); t1 = fminf(t1, tb);
+			if (t0 > t1) return false;
+		}
+	}
+	const v3 p0 = v3_add(o, v3_scale(dir, t0));
+	int cx = (int)floorf((p0.x - g.ox) * g.inv_cell), cy = (int)floorf((p0.y - g.oy) * g.inv_cell), cz = (int)floorf((p0.z - g.oz) * g.inv_cell);
+	cx = min(max(cx, -1), g.nx); cy = min(max(cy, -1), g.ny); cz = min(max(cz, -1), g.nz);
+	const int sx = dir.x > 0.0f ? 1 : -1, sy = dir.y > 0.0f ? 1 : -1, sz = dir.z > 0.0f ? 1 : -1;
+	const float inf = 3.0e38f;
+	const float tdx = fabsf(dir.x) > 1.0e-12f ? c / fabsf(dir.x) : inf, tdy = fabsf(dir.y) > 1.0e-12f ? c / fabsf(dir.y) : inf, tdz = fabsf(dir.z) > 1.0e-12f ? c / fabsf(dir.z) : inf;
+	float tmx = fabsf(dir.x) > 1.0e-12f ? ((g.ox + (float)(cx + (sx > 0 ? 1 : 0)) * c) - o.x) / dir.x : inf;
+	float tmy = fabsf(dir.y) > 1.0e-12f ? ((g.oy + (float)(cy + (sy > 0 ? 1 : 0)) * c) - o.y) / dir.y : inf;
+	float tmz = fabsf(dir.z) > 1.0e-12f ? ((g.oz + (float)(cz + (sz > 0 ? 1 : 0)) * c) - o.z) / dir.z : inf;
+	float t_enter = t0;
+	for (int iter = 0; iter < 100000; ++iter) {
+		if (t_enter - 2.0f * c > ry.max_t) break;
+		for (int dz = -1; dz <= 1; ++dz) for (int dy = -1; dy <= 1; ++dy) {
+			const int y = cy + dy, z = cz + dz;
+			if (y < 0 || y >= g.ny || z < 0 || z >= g.nz) continue;
+			const int xa = max(cx - 1, 0), xb = min(cx + 1, g.nx - 1);
+			if (xa > xb) continue;
+			bool hit = false;
+			grid_row_runs(d, g, xa, xb, y, z, [&](uint32_t q0, uint32_t q1) { for (uint32_t q = q0; q < q1 && !hit; ++q) hit = ray_any_test_body(d, ry, o, dir, __float_as_uint(d.sorted_max[q].w)); });
+			if (hit) return true;
+		}
+		if (tmx <= tmy && tmx <= tmz) { t_enter = tmx; tmx += tdx; cx += sx; if (cx < -1 || cx > g.nx) break; }
+		else if (tmy <= tmz) { t_enter = tmy; tmy += tdy; cy += sy; if (cy < -1 || cy > g.ny) break; }
+		else { t_enter = tmz; tmz += tdz; cz += sz; if (cz < -1 || cz > g.nz) break; }
+		if (t_enter > t1) break;
+	}
+	return false;
+}

@@ -11,6 +11,14 @@ __global__ void __launch_bounds__(64) k_raycast(DV d, const sgp_ray* rays, uint3
 	hits[k] = raycast_one(d, rays[k]);
 }
 
+// doesRayHitAnything (PhysicsWorld.cpp:1668-1725 with the plain CastRay), batched: one thread per ray, one byte per answer (raycast_any_one, sgp_dev_raycast.h)
+__global__ void __launch_bounds__(64) k_raycast_any(DV d, const sgp_ray* rays, uint32_t n, uint8_t* hit)
+{
+	const uint32_t k = blockIdx.x * 64 + threadIdx.x;
+	if (k >= n) return;
+	hit[k] = raycast_any_one(d, rays[k]) ? (uint8_t)1 : (uint8_t)0;
+}
+
 // The same ray by all 64 lanes of a wave together (the resident server's form of raycast_one): the candidates are dealt to the lanes -- the large bodies
 // by index, the bodies of the static large bodies' grid in the order it yields them, the nine neighbour rows of a visited cell one row per lane -- and
 // every lane keeps its own closest hit.  The answer is the lexicographic minimum of (t, body id) over the lanes: ray_test_body breaks ties by body id
@@ -247,5 +255,6 @@ __global__ void __launch_bounds__(64) k_spherecast(DV d, const sgp_ray* rays, co
 }
 void launch_ray_server(const DV& d, RayMailbox* mb, uint32_t first_seq, uint32_t generation, uint64_t idle_ticks, uint64_t max_ticks, hipStream_t s) { hipLaunchKernelGGL(k_ray_server, dim3(1), dim3(64), 0, s, d, mb, first_seq, generation, idle_ticks, max_ticks); }
 void launch_raycast(const DV& d, const sgp_ray* rays, uint32_t n, sgp_hit* hits, hipStream_t s) { if (n) hipLaunchKernelGGL(k_raycast, dim3((n + 63) / 64), dim3(64), 0, s, d, rays, n, hits); }
+void launch_raycast_any(const DV& d, const sgp_ray* rays, uint32_t n, uint8_t* hit, hipStream_t s) { if (n) hipLaunchKernelGGL(k_raycast_any, dim3((n + 63) / 64), dim3(64), 0, s, d, rays, n, hit); }
 void launch_collide_capsules(const DV& d, const sgp_capsule_query* q, uint32_t n, sgp_query_contact* out, uint32_t cap, uint32_t* count, hipStream_t s) { if (n) hipLaunchKernelGGL(k_collide_capsules, dim3(n), dim3(64), 0, s, d, q, n, out, cap, count); }      // a wave per query
 void launch_spherecast(const DV& d, const sgp_ray* rays, const float* radii, uint32_t n, sgp_hit* hits, hipStream_t s) { if (n) hipLaunchKernelGGL(k_spherecast, dim3((n + 63) / 64), dim3(64), 0, s, d, rays, radii, n, hits); }

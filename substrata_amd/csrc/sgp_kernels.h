@@ -12,13 +12,14 @@
 //   sgp_k_solve_hc.hip     K7     k_solve_hc (high colours by connected component: the launch that solves them)
 //   sgp_k_sweep.hip        K8/K1/K9/A3  the body-array sweep k_pre_solve + k_integrate_pose + k_finalize, k_island_*, k_sleep_apply, k_buoyancy (PhysicsWorld.cpp:1367-1442)
 //   sgp_k_vehicle.hip      (f)1   k_vehicle_cast / controller, the vehicle rows inside the solver passes (k_solve_colour_veh)
-//   sgp_k_queries.hip      A7     k_raycast, k_collide_capsules, k_spherecast
+//   sgp_k_queries.hip      A7     k_raycast, k_raycast_any, k_collide_capsules, k_spherecast
 //   sgp_k_shapequery.hip   A7     k_sq_wave, k_sq_candidates + k_sq_pairs_prim / k_sq_pairs_hull / k_sq_mesh (sgp_collide_shapes)
 //   sgp_k_shapecast.hip    A7     k_sc_candidates + k_sc_pairs_prim / k_sc_pairs_hull / k_sc_mesh (sgp_cast_shapes)
 //   sgp_k_characters.hip   A7     k_characters_update (a wave per character: the whole Update / ExtendedUpdate), k_characters_push, k_characters_sync (sgp_characters_*)
 //   sgp_k_particles.hip    A7     k_particles_update (a lane per particle: raycast_one + ParticleManager::think), k_particles_scan, k_particles_scatter (stable compaction + events), k_particles_append (sgp_particles_*)
 //   sgp_k_crafts.hip       A7     k_crafts_update (a lane per craft: HoverCarPhysics::update / BoatPhysics::update, forces into the accumulators), k_crafts_scan, k_crafts_compact (particle hand-over) (sgp_crafts_*)
 //   sgp_k_movers.hip       A5     k_movers_update (a lane per mover: ObjectPathController::update / ObjectMoveToController::update, MoveKinematic on the body), k_movers_follow (the carriages) (sgp_movers_*)
+//   sgp_k_audibility.hip   A7     k_aud_listeners, k_aud_range (a lane per audio source: range bits, pairs to trace counted), k_aud_scan_rays, k_aud_list, k_aud_rays (a lane per listed pair: raycast_any_one), k_aud_fold (occlusion bits, mute ramps, events counted), k_aud_scan_events, k_aud_emit (sgp_audibility_*)
 //   sgp_k_proximity.hip    A7     k_prox_observers (a workgroup per observer: its position and zone), k_prox_test (a lane per watched object: near bits, zone events counted), k_prox_scan, k_prox_emit (sgp_proximity_*)
 //   sgp_k_edits.hip        A5/A6  k_apply_cmds, k_ghost_refresh, read-back
 //   sgp_k_tiles.hip        (e)    tile export / routing, re-tiling histograms
@@ -443,6 +444,7 @@ struct RayMailbox {
 static_assert(sizeof(RayMailbox) == 128 && sizeof(sgp_ray) == 36 && sizeof(sgp_hit) == 48, "RayMailbox: two 64-byte lines");
 void launch_ray_server(const DV& d, RayMailbox* mb, uint32_t first_seq, uint32_t generation, uint64_t idle_ticks, uint64_t max_ticks, hipStream_t s);
 void launch_raycast(const DV& d, const sgp_ray* rays, uint32_t n, sgp_hit* hits, hipStream_t s);
+void launch_raycast_any(const DV& d, const sgp_ray* rays, uint32_t n, uint8_t* hit, hipStream_t s);      // one byte per ray, 1 or 0: hit[k] == (launch_raycast's hits[k].id != SGP_INVALID_ID)
 void launch_collide_capsules(const DV& d, const sgp_capsule_query* q, uint32_t n, sgp_query_contact* out, uint32_t cap, uint32_t* count, hipStream_t s);
 void launch_spherecast(const DV& d, const sgp_ray* rays, const float* radii, uint32_t n, sgp_hit* hits, hipStream_t s);
 // sgp_collide_shapes (sgp_k_shapequery.hip): the buffers of one call, all of them in the world's stage buffer.  ctr: SQ_N_OUT contacts found (all of them: what
@@ -615,6 +617,44 @@ struct ProxBufs {
 };
 static_assert(sizeof(ProxObsRun) == 96 && sizeof(ProxObsRec) == 48 && sizeof(ProxObsDyn) == 48 && sizeof(ProxZone) == 32 && sizeof(sgp_proximity_event) == 32, "proximity records: whole 16-byte units");
 void launch_proximity_update(const DV& d, const ProxBufs& b, hipStream_t s);      // k_prox_observers, k_prox_test, k_prox_scan, k_prox_emit
+// ---- batched audio sources: range, occlusion, muting (sgp_k_audibility.hip, sgp_dev_audibility.h, sgp_audibility_math.h) ---------------------------------------
+// The host owns the sources' records and tags, the listeners' records and the muting keys (uploaded when they change); the device owns, per source, the
+// in-range, occluded and valid masks (bit l: listener l), per pair the ramp and the last distance (valid bit clear: as AudioSource's constructor leaves
+// them, whatever the table holds), the listeners' last positions and keys and the pending events.  New sources are known by their serial, as in the
+// proximity batch; a removed listener's bits leave every mask with the next launch.  Nothing is placed by an atomic: the pairs to trace and the events
+// are counted per workgroup, scanned by one workgroup and written in slot order.
+#define AUD_WG 64                      // lanes per workgroup of the per-source launches (a wave: a lane walks up to 32 listeners) and of the ray launch
+#define AUD_SCAN_WG 256                // lanes of the single workgroup of the two scans
+#define AUD_SCAN_PASS AUD_SCAN_WG      // counts it takes in one pass of its loop: AUD_WG * AUD_SCAN_PASS sources need one pass
+#define AUD_RAY_WGS 2048u              // workgroups of the ray launch at most (its lanes stride over the ray list)
+#define AUD_ALIVE (1u << 31)           // AudRec::flags beside SGP_AUD_ONE_SHOT / SGP_AUD_WANT_*
+#define AUD_GONE  (1u << 30)           //   the body is no longer the one the source was added on
+#define AUD_BODY  (1u << 29)           //   SGP_AUD_SRC_BODY
+#define AUD_ST_SERIAL_SHIFT 8          // st[source].x: SGP_AUD_ST_* in the low byte, the record's serial (16 bits) above it
+struct AudRec { uint32_t body; float pos[3]; float volume; uint32_t zone_key, flags, serial; };             // 32 bytes: two loads
+struct AudLstRec { uint32_t alive, serial, source, body; float pos[3]; uint32_t gone; float off[3]; uint32_t ignore_body; uint32_t zone_key, mute_outside, pad_[2]; };
+struct AudLstDyn { float pos[3]; uint32_t zone_key, mute_outside, update_index, status, serial; };
+struct AudLstRun { float p[3]; uint32_t live, zone_key, mute_outside, ignore_body, pad_; };                    // what k_aud_listeners leaves of a listener for the update's other launches
+struct AudPair { double start, end; float factor, fac_start, fac_end, dist; };                                  // the five ramp variables and the last distance
+struct AudState { uint32_t n_events, update_index, cur_update, n_rays; };      // n_events: raised since the last drain (what did not fit included); n_rays: pairs the running update traces
+struct AudBufs {
+	const AudRec* rec; const uint64_t* tag; uint4* st;      // st[source]: (status | serial << AUD_ST_SERIAL_SHIFT, in-range mask, occluded mask, valid mask)
+	float4* pos;                 // [source]: the position the last update used
+	uint2* scr;                  // [source] of the running update: (range bits that changed, pairs to trace)
+	uint4* evw;                  // [source] of the running update, where the workgroup has events: (range bits, occlusion bits, volume bits to report, 0)
+	uint32_t* wg_rays; uint32_t* wg_ray_off;      // [workgroup of k_aud_range]: its pairs to trace, and where they start in the ray list
+	uint32_t* wg_counts; uint32_t* wg_off;        // [workgroup of k_aud_fold]: its events, and where they start in `events`
+	uint32_t* ray_list; uint32_t* ray_hit;        // [ray]: source << 5 | listener in slot order; the any-hit answer
+	const AudLstRec* lst; AudLstDyn* lst_dyn; AudLstRun* run; AudPair* pairs; AudState* state;
+	sgp_audibility_event* events;
+	const ProxObsDyn* prox_dyn;                   // the attached proximity batch's observers, or NULL
+	const uint32_t* mute_keys; uint32_t n_mute_keys;
+	uint32_t n, lcap, ev_cap, ray_cap;            // source slots in use (high-water mark), listener capacity (the pair table's row), event records held, entries of the ray list
+	uint32_t live_lst, clear_lst;                 // listeners that are alive; listeners removed since the last launch (their bits leave every mask)
+	double cur_time, transition;
+};
+static_assert(sizeof(AudRec) == 32 && sizeof(AudLstRec) == 64 && sizeof(AudLstDyn) == 32 && sizeof(AudLstRun) == 32 && sizeof(AudPair) == 32 && sizeof(sgp_audibility_event) == 32, "audibility records: whole 16-byte units");
+void launch_audibility_update(const DV& d, const AudBufs& b, hipStream_t s);      // k_aud_listeners, k_aud_range, k_aud_scan_rays, k_aud_list, k_aud_rays, k_aud_fold, k_aud_scan_events, k_aud_emit
 void launch_export_boundary(const DV& d, uint32_t nb, float3 lo, float3 hi, float margin, sgp_ghost_record* out, uint32_t cap, uint32_t* count, hipStream_t s);
 
 // ---- tile exchange with the routing on the device (sgp_tiles_*) ----------------------------------------------------

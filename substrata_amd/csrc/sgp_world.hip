@@ -89,6 +89,9 @@ SGP_API int sgp_abi_sizeof(int which)
 	case 44: return (int)sizeof(sgp_batch_checkpoint_info);      // (43 stays -1 likewise)
 	case 46: return (int)sizeof(sgp_proximity_object); case 47: return (int)sizeof(sgp_proximity_observer); case 48: return (int)sizeof(sgp_proximity_event);      // (45 stays -1 likewise)
 	case 49: return (int)sizeof(sgp_proximity_state); case 50: return (int)sizeof(sgp_proximity_observer_state);
+	case 52: return (int)sizeof(sgp_audibility_source); case 53: return (int)sizeof(sgp_audibility_listener); case 54: return (int)sizeof(sgp_audibility_event);      // (51 stays -1 likewise)
+	case 55: return (int)sizeof(sgp_audibility_state); case 56: return (int)sizeof(sgp_audibility_pair_state); case 57: return (int)sizeof(sgp_audibility_listener_state);
+	case 58: return (int)sizeof(sgp_audibility_ramp);
 	default: return -1;
 	}
 }

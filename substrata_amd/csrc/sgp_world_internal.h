@@ -361,6 +361,10 @@ struct sgp_particles;
 uint32_t particles_capacity(const sgp_particles* ps);
 bool particles_of_world(const sgp_particles* ps, const sgp_world* w);      // usable, and of this world
 int particles_append_device(sgp_particles* ps, const sgp_particle* d_recs, const uint32_t* d_count, uint32_t bound);
+// defined in sgp_world_proximity.hip (struct sgp_proximity is private to it): what sgp_world_audibility.hip needs of a proximity batch
+struct sgp_proximity;
+bool proximity_of_world(const sgp_proximity* pb, const sgp_world* w);      // usable, and of this world
+const ProxObsDyn* proximity_obs_dyn(const sgp_proximity* pb);               // the observers' device records (SGP_PROX_MAX_OBSERVERS of them)
 // defined in sgp_world_bodies.hip
 int add_one(sgp_world* w, const sgp_body_desc* d, uint32_t* id_out, bool ghost);
 int book_record_body(sgp_world* w, uint32_t* flags_io, uint64_t userdata, float radius, float volume, bool ghost, uint32_t* id_out);      // (the host's share of add_one for a body created on the device from a record)

@@ -43,6 +43,9 @@ static ProxBufs proximity_bufs(const sgp_proximity* pb)
 	return b;
 }
 
+bool proximity_of_world(const sgp_proximity* pb, const sgp_world* w) { return batch_usable(pb) && pb->w == w; }
+const ProxObsDyn* proximity_obs_dyn(const sgp_proximity* pb) { return pb->d_obs_dyn; }
+
 SGP_API int sgp_proximity_test_point(const float mn[3], const float mx[3], const float p[3], float radius, uint32_t* near_out, float* dist2_out)
 {
 	if (!mn || !mx || !p || !near_out || !dist2_out) return fail(SGP_ERR_INVALID, "sgp_proximity_test_point: NULL");

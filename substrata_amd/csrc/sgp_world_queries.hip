@@ -93,6 +93,32 @@ SGP_API int sgp_raycast(sgp_world* w, const sgp_ray* rays, uint32_t n, sgp_hit* 
 	return SGP_OK;
 }
 
+// doesRayHitAnything, batched (k_raycast_any): one byte per ray.  Always the launch path, n = 1 included: query_prelude tells a resident ray server to leave
+SGP_API int sgp_raycast_any(sgp_world* w, const sgp_ray* rays, uint32_t n, uint8_t* hit_out)
+{
+	if (!w || (!rays && n) || (!hit_out && n)) return fail(SGP_ERR_INVALID, "sgp_raycast_any: NULL");
+	if (!n) { hipSetDevice(w->device); int r = flush_cmds(w); return r; }
+	{ int r = query_prelude(w); if (r != SGP_OK) return r; }
+	StageCarve c;
+	const size_t rays_off = c.add(sizeof(sgp_ray) * n), hit_off = c.add(n);
+	{ int r = ensure_stage(w, c.total); if (r != SGP_OK) return r; }
+	uint8_t* hh = stage_h<uint8_t>(w, hit_off);
+	memcpy(stage_h<sgp_ray>(w, rays_off), rays, sizeof(sgp_ray) * n);
+	if (n <= 64) {
+		// (as sgp_raycast: a handful of rays are read from, and answered into, the pinned host buffer directly)
+		launch_raycast_any(w->dv, stage_h<sgp_ray>(w, rays_off), n, hh, w->stream);
+		HIP_TRY(hipStreamSynchronize(w->stream));
+	} else {
+		HIP_TRY(hipMemcpyAsync(stage_d<sgp_ray>(w, rays_off), stage_h<sgp_ray>(w, rays_off), sizeof(sgp_ray) * n, hipMemcpyHostToDevice, w->stream));
+		uint8_t* dh = stage_d<uint8_t>(w, hit_off);
+		launch_raycast_any(w->dv, stage_d<sgp_ray>(w, rays_off), n, dh, w->stream);
+		HIP_TRY(hipMemcpyAsync(hh, dh, n, hipMemcpyDeviceToHost, w->stream));
+		HIP_TRY(hipStreamSynchronize(w->stream));
+	}
+	memcpy(hit_out, hh, n);
+	return SGP_OK;
+}
+
 // What every query needs before its launch (all entry points of this file, sgp_characters_update, sgp_particles_update): pending body edits flushed -- which also tells
 // a resident ray server to leave --, and the broad-phase grid valid for the poses as they are.  Nothing waits unless an edit was pending.
 int query_prelude(sgp_world* w)

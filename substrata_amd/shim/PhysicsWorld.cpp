@@ -935,6 +935,19 @@ bool PhysicsWorld::doesRayHitAnything(const Vec4f& origin, const Vec4f& dir, flo
 	sgp_hit h;
 	return sgp_raycast(world, &r, 1, &h) == SGP_OK && h.id != SGP_INVALID_ID;
 }
+void PhysicsWorld::doRaysHitAnything(const std::vector<Vec4f>& origins, const std::vector<Vec4f>& dirs, const std::vector<float>& max_ts, std::vector<uint8_t>& results_out) const
+{
+	const size_t n = std::min(origins.size(), std::min(dirs.size(), max_ts.size()));
+	results_out.assign(n, 0);
+	if (!n) return;
+	std::vector<sgp_ray> rs(n);
+	memset(rs.data(), 0, sizeof(sgp_ray) * n);
+	for (size_t k = 0; k < n; ++k) {
+		for (int i = 0; i < 3; ++i) { rs[k].origin[i] = origins[k][i]; rs[k].dir[i] = dirs[k][i]; }
+		rs[k].max_t = max_ts[k]; rs[k].ignore_id = SGP_INVALID_ID;
+	}
+	checkSGP(sgp_raycast_any(world, rs.data(), (uint32_t)n, results_out.data()), "doRaysHitAnything");
+}
 
 
 // ---------------------------------------------------------------------------------------------------------------

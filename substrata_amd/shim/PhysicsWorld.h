@@ -299,6 +299,9 @@ public:
 	// up to 2048 per frame, so its loop should collect the rays, call this once and then react to the results.
 	struct RayQuery { Vec4f origin, dir; float max_t; JPH::BodyID ignore_body_id; bool collidable_only; };
 	void traceRays(const std::vector<RayQuery>& rays, std::vector<RayTraceResult>& results_out) const;
+	// Extension: doesRayHitAnything for many rays in ONE device launch (sgp_raycast_any: the search leaves at the first hit; nothing is ignored, every layer).
+	// results_out[i] != 0 where doesRayHitAnything(origins[i], dirs[i], max_ts[i]) is true.  The three inputs have one length.
+	void doRaysHitAnything(const std::vector<Vec4f>& origins, const std::vector<Vec4f>& dirs, const std::vector<float>& max_ts, std::vector<uint8_t>& results_out) const;
 
 	// Extension (not in the reference, which never needed NarrowPhaseQuery::CollideShape outside CharacterVirtual): what is inside these volumes?  Any number
 	// of spheres, boxes, capsules and convex hulls in ONE call (sgp_collide_shapes); the contacts come back sorted by (query, object, point).

@@ -267,6 +267,105 @@ class Proximity(_Batch):
         return out[:min(n.value, cap)].copy(), int(dropped.value)
 
 
+class Audibility(_Batch):
+    """A batch of audio sources and listeners of one world (sgp_audibility): numpy in, numpy out.  update(cur_time) enqueues and returns; states(),
+    pair_states(), listeners() and drain_events() wait."""
+    _stem, _state_dtype = "audibility", abi.audibility_state_dtype
+
+    def __init__(self, world, source_capacity, listener_capacity=1, event_capacity=4096):
+        super().__init__(world, source_capacity, listener_capacity, event_capacity)
+        self.listener_capacity, self.event_capacity = int(listener_capacity), int(event_capacity)
+        self._prox = None
+
+    def update(self, cur_time):
+        self._w._check(self._update(self._h, float(cur_time)), "audibility_update")
+
+    def add(self, descs):
+        """descs: array of abi.audibility_source_dtype.  Returns the ids (uint32)."""
+        d = np.ascontiguousarray(descs, dtype=abi.audibility_source_dtype).reshape(-1)
+        ids = np.zeros(len(d), dtype=np.uint32)
+        self._w._check(self._w._fn("audibility_add")(self._h, d.ctypes.data, len(d), ids.ctypes.data), "audibility_add")
+        return ids
+
+    def add_points(self, pos, volume=1.0, zone_key=abi.INVALID_ID, flags=abi.AUD_WANT_RANGE | abi.AUD_WANT_OCCLUSION | abi.AUD_WANT_VOLUME, tags=None):
+        pos = np.ascontiguousarray(pos, dtype=np.float32).reshape(-1, 3)
+        d = np.zeros(len(pos), dtype=abi.audibility_source_dtype)
+        d["kind"], d["pos"], d["volume"], d["zone_key"], d["flags"] = abi.AUD_SRC_POINT, pos, volume, zone_key, flags
+        d["tag"] = 0 if tags is None else tags
+        return self.add(d)
+
+    def add_bodies(self, bodies, volume=1.0, zone_key=abi.INVALID_ID, flags=abi.AUD_WANT_RANGE | abi.AUD_WANT_OCCLUSION | abi.AUD_WANT_VOLUME, tags=None):
+        bodies = np.ascontiguousarray(bodies, dtype=np.uint32).reshape(-1)
+        d = np.zeros(len(bodies), dtype=abi.audibility_source_dtype)
+        d["kind"], d["body"], d["volume"], d["zone_key"], d["flags"] = abi.AUD_SRC_BODY, bodies, volume, zone_key, flags
+        d["tag"] = 0 if tags is None else tags
+        return self.add(d)
+
+    def remove(self, i):
+        self._w._check(self._w._fn("audibility_remove")(self._h, int(i)), "audibility_remove")
+
+    def set_points(self, first, xyz):
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        self._w._check(self._w._fn("audibility_set_points")(self._h, int(first), len(xyz), xyz.ctypes.data), "audibility_set_points")
+
+    def set_volume(self, i, volume):
+        self._w._check(self._w._fn("audibility_set_volume")(self._h, int(i), float(volume)), "audibility_set_volume")
+
+    def set_flags(self, i, flags):
+        self._w._check(self._w._fn("audibility_set_flags")(self._h, int(i), int(flags)), "audibility_set_flags")
+
+    def set_listener(self, k, pos=None, body=None, offset=(0.0, 0.0, 0.0), ignore_body=abi.INVALID_ID, zone_key=abi.INVALID_ID, mute_outside=False):
+        """Listener k at `pos`, or riding `body` at the world-space `offset`."""
+        o = abi.AudibilityListener(source=abi.AUD_LST_POINT if body is None else abi.AUD_LST_BODY, body=0 if body is None else int(body),
+                                   ignore_body=int(ignore_body), zone_key=int(zone_key), mute_outside=1 if mute_outside else 0)
+        o.pos[:] = [float(x) for x in ((0.0, 0.0, 0.0) if pos is None else pos)]
+        o.offset[:] = [float(x) for x in offset]
+        self._w._check(self._w._fn("audibility_set_listener")(self._h, int(k), C.byref(o)), "audibility_set_listener")
+
+    def remove_listener(self, k):
+        self._w._check(self._w._fn("audibility_remove_listener")(self._h, int(k)), "audibility_remove_listener")
+
+    def set_listener_points(self, first, xyz):
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        self._w._check(self._w._fn("audibility_set_listener_points")(self._h, int(first), len(xyz), xyz.ctypes.data), "audibility_set_listener_points")
+
+    def set_listener_zone(self, k, zone_key, mute_outside):
+        self._w._check(self._w._fn("audibility_set_listener_zone")(self._h, int(k), int(zone_key), 1 if mute_outside else 0), "audibility_set_listener_zone")
+
+    def set_transition(self, seconds):
+        self._w._check(self._w._fn("audibility_set_transition")(self._h, float(seconds)), "audibility_set_transition")
+
+    def attach_proximity(self, proximity=None):
+        """Listener k takes its zone key from observer k of `proximity` on the device; None detaches."""
+        self._w._check(self._w._fn("audibility_attach_proximity")(self._h, proximity._h if proximity is not None else None), "audibility_attach_proximity")
+        self._prox = proximity
+
+    def set_muting_keys(self, keys):
+        keys = np.ascontiguousarray(keys, dtype=np.uint32).reshape(-1)
+        self._w._check(self._w._fn("audibility_set_muting_keys")(self._h, keys.ctypes.data, len(keys)), "audibility_set_muting_keys")
+
+    def pair_states(self, first=0, n=None):
+        """abi.audibility_pair_state_dtype, shape (n, listener_capacity)."""
+        n = self.capacity - first if n is None else int(n)
+        out = np.zeros((n, self.listener_capacity), dtype=abi.audibility_pair_state_dtype)
+        self._w._check(self._w._fn("audibility_get_pair_states")(self._h, int(first), n, out.ctypes.data), "audibility_get_pair_states")
+        return out
+
+    def listeners(self, first=0, n=None):
+        n = self.listener_capacity - first if n is None else int(n)
+        out = np.zeros(n, dtype=abi.audibility_listener_state_dtype)
+        self._w._check(self._w._fn("audibility_get_listeners")(self._h, int(first), n, out.ctypes.data), "audibility_get_listeners")
+        return out
+
+    def drain_events(self, cap=None):
+        """(events since the last drain as abi.audibility_event_dtype, in their order; how many more did not fit event_capacity)"""
+        cap = self.event_capacity if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), dtype=abi.audibility_event_dtype)
+        n, dropped = C.c_uint32(0), C.c_uint32(0)
+        self._w._check(self._w._fn("audibility_drain_events")(self._h, out.ctypes.data, cap, C.byref(n), C.byref(dropped)), "audibility_drain_events")
+        return out[:min(n.value, cap)].copy(), int(dropped.value)
+
+
 class Crafts(_Batch):
     """A batch of hover cars and boats of one world (sgp_crafts): update() enqueues and returns; states() waits."""
     _stem, _state_dtype = "crafts", abi.craft_state_dtype
@@ -604,6 +703,13 @@ class CWorld:
         self._check(self._fn("raycast")(self._h, rays.ctypes.data, len(rays), hits.ctypes.data), "raycast")
         return hits
 
+    def raycast_any(self, rays):
+        """doesRayHitAnything, batched: one bool per ray, equal to `raycast(rays)["id"] != INVALID_ID` (the search leaves at the first hit)."""
+        rays = np.ascontiguousarray(rays, dtype=abi.ray_dtype)
+        hit = np.zeros(len(rays), dtype=np.uint8)
+        self._check(self._fn("raycast_any")(self._h, rays.ctypes.data, len(rays), hit.ctypes.data), "raycast_any")
+        return hit.astype(bool)
+
     # -- static triangle meshes -------------------------------------------------------------------------------------
     def mesh_create(self, vertices, triangles, materials=None):
         """MeshShapeSettings(vertices, triangles).Create(): returns abi.MeshInfo (mesh_id for static body descs).  `materials`: one
@@ -720,6 +826,10 @@ class CWorld:
     def movers(self, capacity, path_capacity=16):
         """A batch of up to `capacity` path and move-to controllers over `path_capacity` shared paths that belongs to this world (close it before the world)."""
         return Movers(self, capacity, path_capacity)
+
+    def audibility(self, source_capacity, listener_capacity=1, event_capacity=4096):
+        """A batch of audio sources and listeners of this world (sgp_audibility)."""
+        return Audibility(self, source_capacity, listener_capacity, event_capacity)
 
     def proximity(self, object_capacity, zone_capacity=16, event_capacity=4096):
         """A batch of up to `object_capacity` watched objects, `zone_capacity` zones and 32 observers that belongs to this world (close it before the world)."""
