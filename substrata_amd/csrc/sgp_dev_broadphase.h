@@ -54,46 +54,71 @@ template <class F> SGP_DEV void large_grid_query(const DV& d, v3 lo, v3 hi, F fn
 		}
 	}
 }
-// fn(body) for the bodies of the cells a ray (origin o, unit direction dir) crosses up to *max_t (which fn may shorten); a body may come more than once
-template <class F> SGP_DEV void large_grid_ray(const DV& d, v3 o, v3 dir, const float* max_t, F fn)
+// ---- a ray's walk over the cells of a uniform grid (BpGrid, LargeGrid: ox oy oz, cell, inv_cell, nx ny nz) ---------------------------------------------
+// start() clips the ray (origin o, direction dir, up to max_t) to the caller's box [lo, hi] -- the grid's box with a cell of slack, in the caller's own
+// expression: its rounding is part of the answer -- and sets up a 3D DDA from the cell of the entry point; false: the ray misses the box.  Cell coordinates run
+// one cell outside the grid on each side (-1 .. n).  An axis the ray is parallel to (|dir| < 1e-12) is never stepped along.  advance() steps to the next cell;
+// false once the walk has left those cells or the clipped segment.  t_enter is where the ray enters the current cell: the caller ends the walk by its own
+// look-ahead rule (how many cells beyond its own a body can reach) and says what a visit does.
+struct CellWalk {
+	int cx, cy, cz, sx, sy, sz, nx, ny, nz; float tdx, tdy, tdz, tmx, tmy, tmz, t_enter, t1;
+	template <class G> SGP_DEV bool start(const G& g, v3 o, v3 dir, v3 lo, v3 hi, float max_t)
+	{
+		const float c = g.cell;
+		const float oo[3] = { o.x, o.y, o.z }, dd[3] = { dir.x, dir.y, dir.z };
+		const float bl[3] = { lo.x, lo.y, lo.z }, bh[3] = { hi.x, hi.y, hi.z };
+		float t0 = 0.0f; t1 = max_t;
+		for (int a = 0; a < 3; ++a) {
+			if (fabsf(dd[a]) < 1.0e-12f) { if (oo[a] < bl[a] || oo[a] > bh[a]) return false; }
+			else {
+				float ta = (bl[a] - oo[a]) / dd[a], tb = (bh[a] - oo[a]) / dd[a];
+				if (ta > tb) { const float tmp = ta; ta = tb; tb = tmp; }
+				t0 = fmaxf(t0, ta); t1 = fminf(t1, tb);
+				if (t0 > t1) return false;
+			}
+		}
+		const v3 p0 = v3_add(o, v3_scale(dir, t0));
+		nx = g.nx; ny = g.ny; nz = g.nz;
+		cx = (int)floorf((p0.x - g.ox) * g.inv_cell); cy = (int)floorf((p0.y - g.oy) * g.inv_cell); cz = (int)floorf((p0.z - g.oz) * g.inv_cell);
+		cx = min(max(cx, -1), nx); cy = min(max(cy, -1), ny); cz = min(max(cz, -1), nz);
+		sx = dir.x > 0.0f ? 1 : -1; sy = dir.y > 0.0f ? 1 : -1; sz = dir.z > 0.0f ? 1 : -1;
+		const float inf = 3.0e38f;
+		tdx = fabsf(dir.x) > 1.0e-12f ? c / fabsf(dir.x) : inf; tdy = fabsf(dir.y) > 1.0e-12f ? c / fabsf(dir.y) : inf; tdz = fabsf(dir.z) > 1.0e-12f ? c / fabsf(dir.z) : inf;
+		tmx = fabsf(dir.x) > 1.0e-12f ? ((g.ox + (float)(cx + (sx > 0 ? 1 : 0)) * c) - o.x) / dir.x : inf;
+		tmy = fabsf(dir.y) > 1.0e-12f ? ((g.oy + (float)(cy + (sy > 0 ? 1 : 0)) * c) - o.y) / dir.y : inf;
+		tmz = fabsf(dir.z) > 1.0e-12f ? ((g.oz + (float)(cz + (sz > 0 ? 1 : 0)) * c) - o.z) / dir.z : inf;
+		t_enter = t0;
+		return true;
+	}
+	SGP_DEV bool advance()
+	{
+		if (tmx <= tmy && tmx <= tmz) { t_enter = tmx; tmx += tdx; cx += sx; if (cx < -1 || cx > nx) return false; }
+		else if (tmy <= tmz) { t_enter = tmy; tmy += tdy; cy += sy; if (cy < -1 || cy > ny) return false; }
+		else { t_enter = tmz; tmz += tdz; cz += sz; if (cz < -1 || cz > nz) return false; }
+		return !(t_enter > t1);
+	}
+};
+
+// fn(body) for the bodies of the cells a ray (origin o, unit direction dir) crosses up to *max_t (which fn may shorten); a body may come more than once.
+// fn returns true to end the walk there, and then so does this.
+template <class F> SGP_DEV bool large_grid_ray(const DV& d, v3 o, v3 dir, const float* max_t, F fn)
 {
 	const LargeGrid g = *d.lgrid;
-	if (!g.n_items) return;
+	if (!g.n_items) return false;
 	const float c = g.cell;
-	const float oo[3] = { o.x, o.y, o.z }, dd[3] = { dir.x, dir.y, dir.z };
-	const float bl[3] = { g.ox, g.oy, g.oz }, bh[3] = { g.ox + (float)g.nx * c, g.oy + (float)g.ny * c, g.oz + (float)g.nz * c };
-	float t0 = 0.0f, t1 = *max_t;
-	for (int a = 0; a < 3; ++a) {
-		if (fabsf(dd[a]) < 1.0e-12f) { if (oo[a] < bl[a] - c || oo[a] > bh[a] + c) return; }
-		else {
-			float ta = (bl[a] - c - oo[a]) / dd[a], tb = (bh[a] + c - oo[a]) / dd[a];      // (one cell of slack: bounds outside the grid box sit in its border cells)
-			if (ta > tb) { const float tmp = ta; ta = tb; tb = tmp; }
-			t0 = fmaxf(t0, ta); t1 = fminf(t1, tb);
-			if (t0 > t1) return;
-		}
-	}
-	const v3 p0 = v3_add(o, v3_scale(dir, t0));
-	int cx = (int)floorf((p0.x - g.ox) * g.inv_cell), cy = (int)floorf((p0.y - g.oy) * g.inv_cell), cz = (int)floorf((p0.z - g.oz) * g.inv_cell);
-	cx = min(max(cx, -1), g.nx); cy = min(max(cy, -1), g.ny); cz = min(max(cz, -1), g.nz);
-	const int sx = dir.x > 0.0f ? 1 : -1, sy = dir.y > 0.0f ? 1 : -1, sz = dir.z > 0.0f ? 1 : -1;
-	const float inf = 3.0e38f;
-	const float tdx = fabsf(dir.x) > 1.0e-12f ? c / fabsf(dir.x) : inf, tdy = fabsf(dir.y) > 1.0e-12f ? c / fabsf(dir.y) : inf, tdz = fabsf(dir.z) > 1.0e-12f ? c / fabsf(dir.z) : inf;
-	float tmx = fabsf(dir.x) > 1.0e-12f ? ((g.ox + (float)(cx + (sx > 0 ? 1 : 0)) * c) - o.x) / dir.x : inf;
-	float tmy = fabsf(dir.y) > 1.0e-12f ? ((g.oy + (float)(cy + (sy > 0 ? 1 : 0)) * c) - o.y) / dir.y : inf;
-	float tmz = fabsf(dir.z) > 1.0e-12f ? ((g.oz + (float)(cz + (sz > 0 ? 1 : 0)) * c) - o.z) / dir.z : inf;
-	float t_enter = t0;
+	const float bh[3] = { g.ox + (float)g.nx * c, g.oy + (float)g.ny * c, g.oz + (float)g.nz * c };
+	CellWalk w;      // (one cell of slack: bounds outside the grid box sit in its border cells)
+	if (!w.start(g, o, dir, V3(g.ox - c, g.oy - c, g.oz - c), V3(bh[0] + c, bh[1] + c, bh[2] + c), *max_t)) return false;
 	for (int iter = 0; iter < 100000; ++iter) {
-		if (t_enter - c > *max_t) break;
+		if (w.t_enter - c > *max_t) break;
 		// (the cell and, against rounding at cell faces, nothing else: a body is in every cell its bounds touch; cells one step outside the box are its border cells)
-		const int x = min(max(cx, 0), g.nx - 1), y = min(max(cy, 0), g.ny - 1), z = min(max(cz, 0), g.nz - 1);
+		const int x = min(max(w.cx, 0), g.nx - 1), y = min(max(w.cy, 0), g.ny - 1), z = min(max(w.cz, 0), g.nz - 1);
 		const uint32_t cell = ((uint32_t)z * (uint32_t)g.ny + (uint32_t)y) * (uint32_t)g.nx + (uint32_t)x;
 		const uint32_t q0 = d.lg_start[cell], q1 = d.lg_start[cell + 1];
-		for (uint32_t q = q0; q < q1; ++q) fn(d.lg_items[q]);
-		if (tmx <= tmy && tmx <= tmz) { t_enter = tmx; tmx += tdx; cx += sx; if (cx < -1 || cx > g.nx) break; }
-		else if (tmy <= tmz) { t_enter = tmy; tmy += tdy; cy += sy; if (cy < -1 || cy > g.ny) break; }
-		else { t_enter = tmz; tmz += tdz; cz += sz; if (cz < -1 || cz > g.nz) break; }
-		if (t_enter > t1) break;
+		for (uint32_t q = q0; q < q1; ++q) if (fn(d.lg_items[q])) return true;
+		if (!w.advance()) break;
 	}
+	return false;
 }
 
 // large bodies (ground quad, PhysicsWorld.cpp:1123) against every body

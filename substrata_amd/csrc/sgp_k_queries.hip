@@ -21,7 +21,7 @@ __global__ void __launch_bounds__(64) k_raycast_any(DV d, const sgp_ray* rays, u
 
 // The same ray by all 64 lanes of a wave together (the resident server's form of raycast_one): the candidates are dealt to the lanes -- the large bodies
 // by index, the bodies of the static large bodies' grid in the order it yields them, the nine neighbour rows of a visited cell one row per lane -- and
-// every lane keeps its own closest hit.  The answer is the lexicographic minimum of (t, body id) over the lanes: ray_test_body breaks ties by body id
+// every lane keeps its own closest hit.  The answer is the lexicographic minimum of (t, body id) over the lanes: ray_test breaks ties by body id
 // precisely so that the result does not depend on the order of the tests, so this is raycast_one's answer bit for bit.  `tmin` (the wave's closest t so
 // far, refreshed after every cell) bounds the walk for all lanes alike, which keeps the control flow -- and the dealing -- uniform.
 SGP_DEV float wave_min_f(float x) { for (int off = 32; off >= 1; off >>= 1) x = fminf(x, __shfl_xor(x, off, 64)); return x; }
@@ -54,16 +54,15 @@ SGP_DEV sgp_hit raycast_wave(const DV& d, const sgp_ray& ry, const RayServerCach
 {
 	const int lane = (int)(threadIdx.x & 63u);
 	const v3 o = V3(ry.origin[0], ry.origin[1], ry.origin[2]), dir = V3(ry.dir[0], ry.dir[1], ry.dir[2]);
-	RayBest best; best.t = ry.max_t; best.id = SGP_INVALID_ID; best.n = V3(0.0f, 0.0f, 0.0f);
-	best.sub.tri = SGP_INVALID_ID; best.sub.mat = 0; best.sub.u = best.sub.v = 0.0f;
+	RayBest best = ray_best_none(ry.max_t);
 	float tmin = ry.max_t;
 	if (C.n_large <= RAY_CACHE_LARGE) { if ((uint32_t)lane < C.n_large) ray_test_loaded(d, ry, o, dir, C.id[lane], C.f[lane], C.amin[lane], C.amax[lane], C.prop1[lane], C.pose0[lane], C.pose1[lane], best); }
-	else for (uint32_t l = (uint32_t)lane; l < C.n_large; l += 64u) ray_test_body(d, ry, o, dir, d.large_ids[l], best);
+	else for (uint32_t l = (uint32_t)lane; l < C.n_large; l += 64u) ray_test_body<false>(d, ry, o, dir, d.large_ids[l], best);
 	ray_share_bound(best, tmin);
 	if (C.lg.n_items) {
 		uint32_t dealt = 0;
 		const float bound = tmin;      // (fixed for the walk: every lane walks the same cells and counts the same candidates)
-		large_grid_ray(d, o, dir, &bound, [&](uint32_t i) { if ((int)(dealt++ & 63u) == lane) ray_test_body_eager(d, ry, o, dir, i, best); });
+		large_grid_ray(d, o, dir, &bound, [&](uint32_t i) { if ((int)(dealt++ & 63u) == lane) ray_test_body_eager(d, ry, o, dir, i, best); return false; });
 		ray_share_bound(best, tmin);
 	}
 	const BpGrid g = C.g;
@@ -71,29 +70,8 @@ SGP_DEV sgp_hit raycast_wave(const DV& d, const sgp_ray& ry, const RayServerCach
 		const float c = g.cell;
 		const v3 lo = V3(g.ox - c, g.oy - c, g.oz - c);
 		const v3 hi = V3(g.ox + ((float)g.nx + 1.0f) * c, g.oy + ((float)g.ny + 1.0f) * c, g.oz + ((float)g.nz + 1.0f) * c);
-		float t0 = 0.0f, t1 = tmin; bool miss = false;
-		const float oo[3] = { o.x, o.y, o.z }, dd[3] = { dir.x, dir.y, dir.z };
-		const float bl[3] = { lo.x, lo.y, lo.z }, bh[3] = { hi.x, hi.y, hi.z };
-		for (int a = 0; a < 3 && !miss; ++a) {
-			if (fabsf(dd[a]) < 1.0e-12f) { if (oo[a] < bl[a] || oo[a] > bh[a]) miss = true; }
-			else {
-				float ta = (bl[a] - oo[a]) / dd[a], tb = (bh[a] - oo[a]) / dd[a];
-				if (ta > tb) { const float tmp = ta; ta = tb; tb = tmp; }
-				t0 = fmaxf(t0, ta); t1 = fminf(t1, tb);
-				if (t0 > t1) miss = true;
-			}
-		}
-		if (!miss) {
-			const v3 p0 = v3_add(o, v3_scale(dir, t0));
-			int cx = (int)floorf((p0.x - g.ox) * g.inv_cell), cy = (int)floorf((p0.y - g.oy) * g.inv_cell), cz = (int)floorf((p0.z - g.oz) * g.inv_cell);
-			cx = min(max(cx, -1), g.nx); cy = min(max(cy, -1), g.ny); cz = min(max(cz, -1), g.nz);
-			const int sx = dir.x > 0.0f ? 1 : -1, sy = dir.y > 0.0f ? 1 : -1, sz = dir.z > 0.0f ? 1 : -1;
-			const float inf = 3.0e38f;
-			const float tdx = fabsf(dir.x) > 1.0e-12f ? c / fabsf(dir.x) : inf, tdy = fabsf(dir.y) > 1.0e-12f ? c / fabsf(dir.y) : inf, tdz = fabsf(dir.z) > 1.0e-12f ? c / fabsf(dir.z) : inf;
-			float tmx = fabsf(dir.x) > 1.0e-12f ? ((g.ox + (float)(cx + (sx > 0 ? 1 : 0)) * c) - o.x) / dir.x : inf;
-			float tmy = fabsf(dir.y) > 1.0e-12f ? ((g.oy + (float)(cy + (sy > 0 ? 1 : 0)) * c) - o.y) / dir.y : inf;
-			float tmz = fabsf(dir.z) > 1.0e-12f ? ((g.oz + (float)(cz + (sz > 0 ? 1 : 0)) * c) - o.z) / dir.z : inf;
-			float t_enter = t0;
+		CellWalk w;
+		if (w.start(g, o, dir, lo, hi, tmin)) {
 			// The walk, RAY_WAVE_AHEAD cells at a time: the cells of the walk follow from arithmetic alone, so the wave works out the next seven, lane l takes
 			// neighbour row l % 9 of cell l / 9 of them, and the fetches of seven cells (page table -> cell table -> body records) are in flight together where the
 			// cell-by-cell walk paid them one after the other (a 20 m ray: 23 -> see profiles/NOTES_r05.md section 2).  A cell beyond the one where raycast_one stops
@@ -101,16 +79,13 @@ SGP_DEV sgp_hit raycast_wave(const DV& d, const sgp_ray& ry, const RayServerCach
 			const int my_step = lane / 9, row = lane % 9, dy = row % 3 - 1, dz = row / 3 - 1;
 			bool done = false;
 			for (int iter = 0; iter < 100000 && !done; ++iter) {
-				if (t_enter - 2.0f * c > tmin) break;
+				if (w.t_enter - 2.0f * c > tmin) break;
 				int mx = 0, my = 0, mz = 0; bool mine = false;
 #pragma unroll
 				for (int k = 0; k < RAY_WAVE_AHEAD; ++k) {
 					if (!done) {
-						if (k == my_step && !(t_enter - 2.0f * c > tmin)) { mx = cx; my = cy; mz = cz; mine = true; }
-						if (tmx <= tmy && tmx <= tmz) { t_enter = tmx; tmx += tdx; cx += sx; if (cx < -1 || cx > g.nx) done = true; }
-						else if (tmy <= tmz) { t_enter = tmy; tmy += tdy; cy += sy; if (cy < -1 || cy > g.ny) done = true; }
-						else { t_enter = tmz; tmz += tdz; cz += sz; if (cz < -1 || cz > g.nz) done = true; }
-						if (t_enter > t1) done = true;
+						if (k == my_step && !(w.t_enter - 2.0f * c > tmin)) { mx = w.cx; my = w.cy; mz = w.cz; mine = true; }
+						done = !w.advance();
 					}
 				}
 				if (mine && lane < 9 * RAY_WAVE_AHEAD) {

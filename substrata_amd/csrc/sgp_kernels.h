@@ -12,7 +12,7 @@
 //   sgp_k_solve_hc.hip     K7     k_solve_hc (high colours by connected component: the launch that solves them)
 //   sgp_k_sweep.hip        K8/K1/K9/A3  the body-array sweep k_pre_solve + k_integrate_pose + k_finalize, k_island_*, k_sleep_apply, k_buoyancy (PhysicsWorld.cpp:1367-1442)
 //   sgp_k_vehicle.hip      (f)1   k_vehicle_cast / controller, the vehicle rows inside the solver passes (k_solve_colour_veh)
-//   sgp_k_queries.hip      A7     k_raycast, k_raycast_any, k_collide_capsules, k_spherecast
+//   sgp_k_queries.hip      A7     k_raycast, k_raycast_any (a lane per ray: raycast_world<closest | any>, sgp_dev_raycast.h), k_ray_server (a wave per ray: raycast_wave), k_collide_capsules, k_spherecast
 //   sgp_k_shapequery.hip   A7     k_sq_wave, k_sq_candidates + k_sq_pairs_prim / k_sq_pairs_hull / k_sq_mesh (sgp_collide_shapes)
 //   sgp_k_shapecast.hip    A7     k_sc_candidates + k_sc_pairs_prim / k_sc_pairs_hull / k_sc_mesh (sgp_cast_shapes)
 //   sgp_k_characters.hip   A7     k_characters_update (a wave per character: the whole Update / ExtendedUpdate), k_characters_push, k_characters_sync (sgp_characters_*)
@@ -25,6 +25,8 @@
 //   sgp_k_tiles.hip        (e)    tile export / routing, re-tiling histograms
 //   sgp_k_checkpoint.hip          k_ckpt_copy: the segmented copy of sgp_world_checkpoint / sgp_world_rollback
 //   sgp_dev_*.h            device-inline functions shared between stage files (sgp_dev_all.h includes them in dependency order)
+//                          (the rays: one cell walk, CellWalk in sgp_dev_broadphase.h, under large_grid_ray and raycast_wave -- raycast_world keeps it written out --; one per-shape, one per-body test and
+//                          one world walk in sgp_dev_raycast.h, which the query, particle, craft and audibility files include for raycast_one / raycast_any_one)
 // All body state is SoA float4 / 32-byte records in HBM; every per-body kernel is a coalesced 16 B/lane sweep.
 #pragma once
 #include <hip/hip_runtime.h>
