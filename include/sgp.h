@@ -696,6 +696,53 @@ int  sgp_characters_get_states(sgp_characters* cs, uint32_t first, uint32_t n, s
  * (<= cap are written; all are consumed).  A character holds at most 32 between drains. */
 int  sgp_characters_drain_contacts(sgp_characters* cs, sgp_character_contact* out, uint32_t cap, uint32_t* n_out);
 
+/* ---- driven characters: PlayerPhysics::update's velocity rule on the device (gui_client/PlayerPhysics.cpp:251-469) ----
+ * A character with SGP_DRIVE_ON gets the velocity of its update from the rule PlayerPhysics::update applies before SetLinearVelocity --
+ * walking at the desired velocity plus the ground's, air control capped at max_air_speed, swimming in the world's water, flying, gravity,
+ * the 100 m/s falling cap, the jump through the ground normal -- computed inside sgp_characters_update's launch from what the previous
+ * update left on the device (velocity, ground state, ground normal) and from a fresh UpdateGroundVelocity (a contact query at the
+ * current position, made where the character has a ground body and is not flying, as PlayerPhysics.cpp:269 makes it).  The caller sends
+ * what the player asks for and never reads a state back to move a character.  docs/CONTRACT.md 4n writes the rule out.
+ * A driven character still honours sgp_character_input: `velocity` is SetLinearVelocity when it is set (a teleport's velocity,
+ * addToLinearVel, a bounce pad), and the rule starts from it; ignore_id, SGP_CHAR_EXTENDED and SGP_CHAR_DISABLED act as before;
+ * SGP_CHAR_NO_SLIDE is replaced by the rule's own !allow_sliding (allow_sliding = the desired velocity is not zero).
+ * An undriven character (the default) moves exactly as before. */
+#define SGP_DRIVE_ON            1u   /* the character's velocity comes from the rule, not from sgp_character_input::velocity alone */
+#define SGP_DRIVE_FLY           2u   /* fly_mode */
+#define SGP_DRIVE_GRAVITY       4u   /* gravity_enabled */
+#define SGP_DRIVE_FREE_CAMERA   8u   /* CameraMode_FreeCamera: move_up is honoured as when flying */
+#define SGP_DRIVE_SMOOTH_STAIRS 16u  /* camera height: the reference reads pre_stair_walk_position AFTER ExtendedUpdate (its `#if 1` branch), so its dz is 0,
+                                        campos_z_delta stays 0 and the camera sits at pos.z + eye_height -- the default here.  With this flag dz is taken against the
+                                        position just before the stair walk of the update: the reference's intent (its disabled branch), not its behaviour */
+typedef struct sgp_character_drive {
+	float    move_desired_vel[3];   /* what processMoveForwards / processStrafeRight summed, in m/s */
+	float    move_up;               /* processMoveUp's factor * move_speed * run factor; the device adds (0,0,move_up) if flying, free camera or submerged > 0.3 */
+	uint32_t flags;                 /* SGP_DRIVE_* */
+	float    jump_speed, max_air_speed, eye_height;   /* 4.5, 8, 1.67 */
+} sgp_character_drive;              /* 32 bytes */
+typedef struct sgp_character_drive_state {
+	float    cam_pos[3];            /* campos_out */
+	float    campos_z_delta;
+	float    last_xy_plane_vel_rel_ground[3];
+	float    fraction_submerged;    /* of the last update */
+	uint32_t on_ground, jumped;     /* of the last update */
+	uint32_t num_jumps, pad_;       /* jumps since the slot's character was added */
+} sgp_character_drive_state;        /* 48 bytes */
+/* jump_speed 4.5, max_air_speed 8, eye_height 1.67, flags = SGP_DRIVE_GRAVITY, the rest 0 */
+void sgp_default_character_drive(sgp_character_drive* out);
+/* The drive of characters [first, first + n); it stays in force until set again.  All or nothing: a non-finite value, an unknown flag, a
+ * negative jump_speed or max_air_speed, an eye_height not > 0 or a range beyond the live slots is SGP_ERR_INVALID and changes nothing. */
+int  sgp_characters_set_drive(sgp_characters* cs, uint32_t first, uint32_t n, const sgp_character_drive* drives);
+/* processJump: last_jump_time = cur_time for the characters named.  The jump fires in the first sgp_characters_update_at whose clock is
+ * less than 0.1 s past cur_time and that finds the character supported.  A non-finite cur_time or an id that is not live: SGP_ERR_INVALID. */
+int  sgp_characters_jump(sgp_characters* cs, const uint32_t* ids, uint32_t n, double cur_time);
+/* sgp_characters_update with the caller's clock (PlayerPhysics::update's cur_time), which the jump window is measured against.
+ * sgp_characters_update(cs, dt) is this call with a clock for which no jump window is open: a pending jump stays pending. */
+int  sgp_characters_update_at(sgp_characters* cs, float dt, double cur_time);
+/* Waits for the updates in flight.  Slots that are not live read as zeros; a character never driven has zeros too, but for cam_pos, which is its
+ * position at the time it was added, an eye height up. */
+int  sgp_characters_get_drive_states(sgp_characters* cs, uint32_t first, uint32_t n, sgp_character_drive_state* out);
+
 /* ---- batched point particles (ParticleManager, gui_client/ParticleManager.cpp) -----------------------
  * A batch of point particles that belongs to one world and lives on the device.  sgp_particles_update runs ParticleManager::think
  * (ParticleManager.cpp:145-274) for every live particle on the world's stream -- one ray along the velocity for dt, answered by the very
@@ -1229,7 +1276,7 @@ int  sgp_checkpoint_blob_info(const void* blob, uint64_t bytes, sgp_checkpoint_i
  * batch's high-water slot did; for particles, the host's bound of the live count).  Host edits that no update has carried yet go to the device
  * first; the copy is enqueued on the world's stream and the call returns without waiting for it.  It changes nothing any later call returns.
  * Rollback: the batch becomes exactly what it was at the capture -- the device's state (for particles: the live ones, their count, the
- * replacement cursor, undrained events and the dropped count; for characters: undrained contact and push records too), the host's records and
+ * replacement cursor, undrained events and the dropped count; for characters: undrained contact and push records, the drives and the drive states with a pending jump too), the host's records and
  * inputs, tags, the movers' paths with their reference counts, and the slot tables with the free list's order, so that the next *_add returns
  * the id it would have.  Not touched: which particle batch a craft batch is attached to.
  * A craft or mover that was attached to its body at the capture is attached to the same body id again if that is now a live body the batch

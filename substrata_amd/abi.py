@@ -261,6 +261,20 @@ class CharacterContact(C.Structure):
                 ("point", f32 * 3), ("normal", f32 * 3)]
 
 
+DRIVE_ON, DRIVE_FLY, DRIVE_GRAVITY, DRIVE_FREE_CAMERA, DRIVE_SMOOTH_STAIRS = 1, 2, 4, 8, 16    # SGP_DRIVE_*
+
+
+class CharacterDrive(C.Structure):
+    """sgp_character_drive: what a driven character's player asks for (PlayerPhysics' move_desired_vel, modes and constants)."""
+    _fields_ = [("move_desired_vel", f32 * 3), ("move_up", f32), ("flags", u32), ("jump_speed", f32), ("max_air_speed", f32), ("eye_height", f32)]
+
+
+class CharacterDriveState(C.Structure):
+    """sgp_character_drive_state: what PlayerPhysics::update leaves besides the character's own state."""
+    _fields_ = [("cam_pos", f32 * 3), ("campos_z_delta", f32), ("last_xy_plane_vel_rel_ground", f32 * 3), ("fraction_submerged", f32),
+                ("on_ground", u32), ("jumped", u32), ("num_jumps", u32), ("pad_", u32)]
+
+
 PARTICLE_DIE_ON_HIT = 1                                                  # SGP_PARTICLE_DIE_ON_HIT
 PARTICLE_EV_DIED, PARTICLE_EV_FOAM, PARTICLE_EV_REPLACED = 1, 2, 4       # SGP_PARTICLE_EV_*
 PARTICLES_MAX_CAPACITY = 1 << 20
@@ -469,7 +483,8 @@ ABI_SIZEOF_APPENDED = ["sgp_shape_query", None, "sgp_shape_cast", "sgp_cast_hit"
                        None, "sgp_proximity_object", "sgp_proximity_observer", "sgp_proximity_event", "sgp_proximity_state",      # (45 likewise)
                        "sgp_proximity_observer_state",
                        None, "sgp_audibility_source", "sgp_audibility_listener", "sgp_audibility_event", "sgp_audibility_state",      # (51 likewise)
-                       "sgp_audibility_pair_state", "sgp_audibility_listener_state", "sgp_audibility_ramp"]
+                       "sgp_audibility_pair_state", "sgp_audibility_listener_state", "sgp_audibility_ramp",
+                       None, "sgp_character_drive", "sgp_character_drive_state"]      # (59 likewise)
 ABI_SIZEOF_ALL = ABI_SIZEOF_ORDER + ABI_SIZEOF_APPENDED
 
 STRUCTS = {"sgp_settings": Settings, "sgp_world_desc": WorldDesc, "sgp_body_desc": BodyDesc,
@@ -489,7 +504,8 @@ STRUCTS = {"sgp_settings": Settings, "sgp_world_desc": WorldDesc, "sgp_body_desc
            "sgp_proximity_state": ProximityState, "sgp_proximity_observer_state": ProximityObserverState,
            "sgp_audibility_source": AudibilitySource, "sgp_audibility_listener": AudibilityListener, "sgp_audibility_event": AudibilityEvent,
            "sgp_audibility_state": AudibilityState, "sgp_audibility_pair_state": AudibilityPairState,
-           "sgp_audibility_listener_state": AudibilityListenerState, "sgp_audibility_ramp": AudibilityRamp}
+           "sgp_audibility_listener_state": AudibilityListenerState, "sgp_audibility_ramp": AudibilityRamp,
+           "sgp_character_drive": CharacterDrive, "sgp_character_drive_state": CharacterDriveState}
 
 body_desc_dtype = np.dtype(BodyDesc)
 body_state_dtype = np.dtype(BodyState)
@@ -511,6 +527,8 @@ cast_hit_dtype = np.dtype(CastHit)
 character_input_dtype = np.dtype(CharacterInput)
 character_state_dtype = np.dtype(CharacterState)
 character_contact_dtype = np.dtype(CharacterContact)
+character_drive_dtype = np.dtype(CharacterDrive)
+character_drive_state_dtype = np.dtype(CharacterDriveState)
 particle_dtype = np.dtype(Particle)
 particle_state_dtype = np.dtype(ParticleState)
 particle_event_dtype = np.dtype(ParticleEvent)
@@ -610,6 +628,11 @@ PROTOTYPES = {
     "characters_update": (C.c_int, [vp, f32]),
     "characters_get_states": (C.c_int, [vp, u32, u32, vp]),
     "characters_drain_contacts": (C.c_int, [vp, vp, u32, P(u32)]),
+    "default_character_drive": (None, [P(CharacterDrive)]),
+    "characters_set_drive": (C.c_int, [vp, u32, u32, vp]),
+    "characters_jump": (C.c_int, [vp, vp, u32, C.c_double]),
+    "characters_update_at": (C.c_int, [vp, f32, C.c_double]),
+    "characters_get_drive_states": (C.c_int, [vp, u32, u32, vp]),
     # batched point particles (handle: void*)
     "default_particle": (None, [P(Particle)]),
     "particles_create": (C.c_int, [vp, u32, u32, P(vp)]),

@@ -278,16 +278,19 @@ __device__ __noinline__ v3 char_move_shape(const DV& d, MeshPairLds<64>& L, Char
 	return pos;
 }
 
-// CharacterVirtual::updateSupportingContact(S.cur, store = true): the ground of the character at `position`
-SGP_DEV CharGround char_supporting_contact(CharLds& S, const CharRec* rc, v3 position, v3 previous_ground_position)
+// CharacterVirtual::updateSupportingContact(S.cur, store): the ground of the character at `position`.  store = false is UpdateGroundVelocity's call: the active
+// contacts stay those of the previous update, which CancelVelocityTowardsSteepSlopes and CanWalkStairs of the update that follows read.
+SGP_DEV CharGround char_supporting_contact(CharLds& S, const CharRec* rc, v3 position, v3 previous_ground_position, bool store = true)
 {
 	const uint32_t lane = threadIdx.x;
 	const v3 up = ch_v3(rc->up), svn = ch_v3(rc->sv_n);
 	const uint32_t n = S.n_cur;
-	__syncthreads();
-	if (lane < n) S.act[lane] = S.cur[lane];
-	if (lane == 0) S.n_act = n;
-	__syncthreads();
+	if (store) {
+		__syncthreads();
+		if (lane < n) S.act[lane] = S.cur[lane];
+		if (lane == 0) S.n_act = n;
+		__syncthreads();
+	}
 	int best = -1; bool best_steep = true; float best_up = -2.0f; bool touching = false;
 	for (uint32_t i = 0; i < n; ++i) {
 		const CharContact& c = S.cur[i];

@@ -16,6 +16,7 @@
 //   sgp_k_shapequery.hip   A7     k_sq_wave, k_sq_candidates + k_sq_pairs_prim / k_sq_pairs_hull / k_sq_mesh (sgp_collide_shapes)
 //   sgp_k_shapecast.hip    A7     k_sc_candidates + k_sc_pairs_prim / k_sc_pairs_hull / k_sc_mesh (sgp_cast_shapes)
 //   sgp_k_characters.hip   A7     k_characters_update (a wave per character: the whole Update / ExtendedUpdate), k_characters_push, k_characters_sync (sgp_characters_*)
+//   sgp_k_characters_driven.hip   A7     k_characters_update<true> (the same with PlayerPhysics::update's rule in front: a batch with driven characters)
 //   sgp_k_particles.hip    A7     k_particles_update (a lane per particle: raycast_one + ParticleManager::think), k_particles_scan, k_particles_scatter (stable compaction + events), k_particles_append (sgp_particles_*)
 //   sgp_k_crafts.hip       A7     k_crafts_update (a lane per craft: HoverCarPhysics::update / BoatPhysics::update, forces into the accumulators), k_crafts_scan, k_crafts_compact (particle hand-over) (sgp_crafts_*)
 //   sgp_k_movers.hip       A5     k_movers_update (a lane per mover: ObjectPathController::update / ObjectMoveToController::update, MoveKinematic on the body), k_movers_follow (the carriages) (sgp_movers_*)
@@ -501,6 +502,16 @@ struct CharState {
 	float pos[3], vel[3]; uint32_t ground_state; float gn[3], gv[3], gp[3]; uint32_t ground_body, overflow;
 	uint32_t n_active, n_seen, reset_serial, pose_serial, in_serial, pad_[3];
 };
+// A driven character (SGP_DRIVE_ON: PlayerPhysics::update's rule in front of the update, sgp_player_rule.h).  CharDrive is the host's record, uploaded when it
+// changed, with a serial for the jump: a jump serial the state has not seen makes the next launch take jump_time as last_jump_time.  CharDriveState lives on the
+// device alone; its reset serial is its own (the drive state of an undriven character is not touched by an update, so it may learn of a new character later than
+// CharState does).  CharState and CharIn keep their layouts.
+struct CharDrive { float move[3], move_up; uint32_t flags; float jump_speed, max_air_speed, eye_height; uint32_t serial, jump_serial; double jump_time; };
+struct CharDriveState {
+	double last_jump_time; uint32_t jump_serial, reset_serial;
+	float campos_z_delta, cam_pos[3], last_xy[3], fraction_submerged; uint32_t on_ground, jumped, num_jumps; float pre_stairs_z;      // pre_stairs_z: the update's pre_stair_walk_position
+};
+static_assert(sizeof(CharDrive) == 48 && sizeof(CharDriveState) == 64, "CharDrive / CharDriveState: the double first or last, no padding inside");
 struct CharPush { uint32_t body; float f[3], p[3]; uint32_t pad_; };
 struct CharAdded { uint32_t body, pad_; float p[3], n[3]; };
 struct CharBufs {
@@ -512,9 +523,14 @@ struct CharBufs {
 	CharAdded* added; uint32_t* n_added;     // [character][SGP_CHAR_MAX_ADDED]; emptied by the host's drain
 	uint32_t n;               // slots in use (high-water mark)
 };
-void launch_characters_update(const DV* d_dev, const CharBufs& b, float dt, hipStream_t s);      // d_dev: a copy of the world's DV in device memory (the phases are functions of their own: they read it through a pointer)
+// what only a driven character's update reads: the drive records and states, the caller's clock, the world's water.  A batch without a driven slot is updated by
+// k_characters_update<false>, whose code is what it was before there were driven characters (the arguments arrive and are not read); one with, by
+// k_characters_update<true> (drive != NULL).
+struct CharDriveArgs { const CharDrive* drive; CharDriveState* dst; double cur_time; int water_enabled; float water_z; };
+void launch_characters_update(const DV* d_dev, const CharBufs& b, float dt, const CharDriveArgs* drive, hipStream_t s);      // d_dev: a copy of the world's DV in device memory (the phases are functions of their own: they read it through a pointer); drive: NULL = no slot has SGP_DRIVE_ON
+void launch_characters_update_driven(const DV* d_dev, const CharBufs& b, float dt, const CharDriveArgs& drive, hipStream_t s);      // (sgp_k_characters_driven.hip; called by launch_characters_update)
 void launch_characters_push(const DV& d, const CharBufs& b, hipStream_t s);
-void launch_characters_sync(const CharBufs& b, hipStream_t s);
+void launch_characters_sync(const CharBufs& b, const CharDrive* drive, CharDriveState* dst, hipStream_t s);
 // ---- batched point particles (sgp_k_particles.hip, sgp_dev_particles.h) ---------------------------------------------------------------------------------
 // Everything lives on the device, the counts included: the host learns them only when it reads.  A particle is a hot half (two float4: pos xyz + width,
 // vel xyz + opacity) that the update reads and writes, and a cold half (two uint4: area, mass, restitution, dwidth_dt | dopacity_dt, flags, tag) that it

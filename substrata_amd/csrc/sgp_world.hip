@@ -92,6 +92,7 @@ SGP_API int sgp_abi_sizeof(int which)
 	case 52: return (int)sizeof(sgp_audibility_source); case 53: return (int)sizeof(sgp_audibility_listener); case 54: return (int)sizeof(sgp_audibility_event);      // (51 stays -1 likewise)
 	case 55: return (int)sizeof(sgp_audibility_state); case 56: return (int)sizeof(sgp_audibility_pair_state); case 57: return (int)sizeof(sgp_audibility_listener_state);
 	case 58: return (int)sizeof(sgp_audibility_ramp);
+	case 60: return (int)sizeof(sgp_character_drive); case 61: return (int)sizeof(sgp_character_drive_state);      // (59 stays -1 likewise)
 	default: return -1;
 	}
 }

@@ -2,20 +2,23 @@
 // The host keeps the descriptions and inputs (uploaded when they change) and the slot bookkeeping; positions, ground states, active contacts and the bodies
 // already reported live on the device and are touched by the kernels of sgp_k_characters.hip alone.  An update enqueues and returns.
 #include "sgp_world_internal.h"
+#include <limits>
 
 struct sgp_characters : WorldBatch {
 	BatchSlots slots;
 	// the copy of the world's DV the update kernel reads through a pointer: a mirror of `one` record, brought up to date by every update (dv_valid: it has been the world's once)
 	Mirror<DV> dv; bool dv_valid = false; const uint32_t one = 1;
-	Mirror<CharRec> rec; Mirror<CharIn> in;
+	Mirror<CharRec> rec; Mirror<CharIn> in; Mirror<CharDrive> drive;
+	uint32_t n_driven = 0;      // slots whose drive has SGP_DRIVE_ON (sgp_character_remove clears it): 0 picks the update kernel without the drive
+	void count_driven() { n_driven = 0; for (uint32_t i = 0; i < slots.high; ++i) if (drive[i].flags & SGP_DRIVE_ON) ++n_driven; }
 	// device
-	CharState* d_st = nullptr; CharContact* d_active = nullptr; uint32_t* d_seen = nullptr;
+	CharState* d_st = nullptr; CharDriveState* d_dst = nullptr; CharContact* d_active = nullptr; uint32_t* d_seen = nullptr;
 	CharPush* d_push = nullptr; uint32_t* d_n_push = nullptr; CharAdded* d_added = nullptr; uint32_t* d_n_added = nullptr;
-	// what a checkpoint holds beyond the rec and in mirrors (d_n_push whole: the push_any word sits behind its last slot)
+	// what a checkpoint holds beyond the rec, in and drive mirrors (d_n_push whole: the push_any word sits behind its last slot)
 	void ckpt_layout(BatchCkptLayout& l)
 	{
 		const uint32_t* n = &slots.high;
-		l.device(d_st, n); l.device(d_active, n, SGP_CHAR_MAX_CONTACTS); l.device(d_seen, n, SGP_CHAR_MAX_CONTACTS);
+		l.device(d_st, n); l.device(d_dst, n); l.device(d_active, n, SGP_CHAR_MAX_CONTACTS); l.device(d_seen, n, SGP_CHAR_MAX_CONTACTS);
 		l.device(d_push, n, SGP_CHAR_MAX_PUSHES); l.device_whole(d_n_push, slots.cap + 1u); l.device(d_added, n, SGP_CHAR_MAX_ADDED); l.device(d_n_added, n);
 		l.table(slots);
 		l.capacity = slots.cap; l.high = slots.high; l.n_alive = slots.n_alive;
@@ -58,10 +61,10 @@ SGP_API int sgp_characters_create(sgp_world* w, uint32_t capacity, sgp_character
 	sgp_characters* cs = new sgp_characters();
 	const size_t n = capacity;
 	cs->slots.cap = capacity;
-	cs->dv.shape(1, &cs->one); cs->dv.state = false; cs->rec.shape(n, &cs->slots.high); cs->in.shape(n, &cs->slots.high);
+	cs->dv.shape(1, &cs->one); cs->dv.state = false; cs->rec.shape(n, &cs->slots.high); cs->in.shape(n, &cs->slots.high); cs->drive.shape(n, &cs->slots.high);
 	for (uint32_t i = 0; i < capacity; ++i) cs->in[i].ignore = SGP_INVALID_ID;
-	bool ok = cs->adopt(w) && cs->create_mirrors({ &cs->dv, &cs->rec, &cs->in });
-	ok = ok && cs->alloc(cs->d_st, n)
+	bool ok = cs->adopt(w) && cs->create_mirrors({ &cs->dv, &cs->rec, &cs->in, &cs->drive });
+	ok = ok && cs->alloc(cs->d_st, n) && cs->alloc(cs->d_dst, n)
 	        && cs->alloc(cs->d_active, n * SGP_CHAR_MAX_CONTACTS) && cs->alloc(cs->d_seen, n * SGP_CHAR_MAX_CONTACTS)
 	        && cs->alloc(cs->d_push, n * SGP_CHAR_MAX_PUSHES) && cs->alloc(cs->d_n_push, n + 1) && cs->alloc(cs->d_added, n * SGP_CHAR_MAX_ADDED) && cs->alloc(cs->d_n_added, n);
 	return batch_created(cs, ok, out, "sgp_characters_create");
@@ -107,7 +110,15 @@ SGP_API int sgp_character_add(sgp_characters* cs, const sgp_character_desc* desc
 	CharIn& in = cs->in[id];
 	const uint32_t in_serial = in.serial + 1u;
 	memset(&in, 0, sizeof(in)); in.ignore = SGP_INVALID_ID; in.serial = in_serial;
-	cs->rec.dirty = cs->in.dirty = true;
+	// nothing of the slot's previous character is driven on: the default drive with SGP_DRIVE_ON unset, and no jump pending
+	CharDrive& dr = cs->drive[id];
+	const uint32_t drive_serial = dr.serial + 1u, jump_serial = dr.jump_serial + 1u;
+	sgp_character_drive dd; sgp_default_character_drive(&dd);
+	if (dr.flags & SGP_DRIVE_ON) cs->n_driven--;
+	memset(&dr, 0, sizeof(dr));
+	dr.flags = dd.flags; dr.jump_speed = dd.jump_speed; dr.max_air_speed = dd.max_air_speed; dr.eye_height = dd.eye_height;
+	dr.serial = drive_serial; dr.jump_serial = jump_serial; dr.jump_time = -1.0;
+	cs->rec.dirty = cs->in.dirty = cs->drive.dirty = true;
 	*id_out = id;
 	return SGP_OK;
 }
@@ -120,6 +131,7 @@ SGP_API int sgp_character_remove(sgp_characters* cs, uint32_t id)
 	hipSetDevice(cs->w->device);
 	HIP_TRY(hipMemsetAsync(cs->d_n_added + id, 0, sizeof(uint32_t), cs->w->stream));      // (its pending contact records go with it: the slot's next character starts with none)
 	cs->rec[id].alive = 0; cs->rec.dirty = true;
+	if (cs->drive[id].flags & SGP_DRIVE_ON) { cs->drive[id].flags &= ~SGP_DRIVE_ON; cs->n_driven--; cs->drive.dirty = true; }      // (a batch whose last driven character goes is an undriven batch again)
 	cs->slots.give_back(id);
 	return SGP_OK;
 }
@@ -159,32 +171,107 @@ SGP_API int sgp_characters_set_inputs(sgp_characters* cs, uint32_t first, uint32
 	return SGP_OK;
 }
 
-SGP_API int sgp_characters_update(sgp_characters* cs, float dt)
+SGP_API void sgp_default_character_drive(sgp_character_drive* d)
 {
-	{ int r = batch_update_admit(cs, "sgp_characters_update", "characters", std::isfinite(dt) && dt > 0.0f, "positive"); if (r != SGP_OK) return r; }
+	if (!d) return;
+	memset(d, 0, sizeof(*d));
+	// PlayerPhysics.cpp:29-41: jump_speed, max_air_speed, EYE_HEIGHT; gravity is on once the player has moved
+	d->flags = SGP_DRIVE_GRAVITY; d->jump_speed = 4.5f; d->max_air_speed = 8.0f; d->eye_height = 1.67f;
+}
+
+static const uint32_t k_drive_flags = SGP_DRIVE_ON | SGP_DRIVE_FLY | SGP_DRIVE_GRAVITY | SGP_DRIVE_FREE_CAMERA | SGP_DRIVE_SMOOTH_STAIRS;
+
+SGP_API int sgp_characters_set_drive(sgp_characters* cs, uint32_t first, uint32_t n, const sgp_character_drive* drives)
+{
+	if (!batch_usable(cs) || (n && !drives)) return fail(SGP_ERR_INVALID, "sgp_characters_set_drive: NULL, or the batch's world is gone");
+	if ((uint64_t)first + n > cs->slots.high) return fail(SGP_ERR_INVALID, "sgp_characters_set_drive: range beyond the last character");
+	for (uint32_t i = 0; i < n; ++i) {      // (all or nothing)
+		const sgp_character_drive& d = drives[i];
+		if (!finite3(d.move_desired_vel) || !std::isfinite(d.move_up) || !std::isfinite(d.jump_speed) || !std::isfinite(d.max_air_speed) || !std::isfinite(d.eye_height))
+			return fail(SGP_ERR_INVALID, "sgp_characters_set_drive: a non-finite value");
+		if (d.flags & ~k_drive_flags) return fail(SGP_ERR_INVALID, "sgp_characters_set_drive: unknown flag");
+		if (d.jump_speed < 0.0f || d.max_air_speed < 0.0f || !(d.eye_height > 0.0f)) return fail(SGP_ERR_INVALID, "sgp_characters_set_drive: a negative jump_speed or max_air_speed, or an eye_height that is not positive");
+	}
+	for (uint32_t i = 0; i < n; ++i) {
+		CharDrive& dr = cs->drive[first + i];
+		cs->n_driven += ((drives[i].flags & SGP_DRIVE_ON) ? 1u : 0u) - ((dr.flags & SGP_DRIVE_ON) ? 1u : 0u);
+		memcpy(dr.move, drives[i].move_desired_vel, 12); dr.move_up = drives[i].move_up; dr.flags = drives[i].flags;
+		dr.jump_speed = drives[i].jump_speed; dr.max_air_speed = drives[i].max_air_speed; dr.eye_height = drives[i].eye_height; dr.serial++;
+	}
+	if (n) cs->drive.dirty = true;
+	return SGP_OK;
+}
+
+SGP_API int sgp_characters_jump(sgp_characters* cs, const uint32_t* ids, uint32_t n, double cur_time)
+{
+	if (!batch_usable(cs) || (n && !ids)) return fail(SGP_ERR_INVALID, "sgp_characters_jump: NULL, or the batch's world is gone");
+	if (!std::isfinite(cur_time)) return fail(SGP_ERR_INVALID, "sgp_characters_jump: non-finite time");
+	for (uint32_t i = 0; i < n; ++i) if (!char_live(cs, ids[i])) return fail(SGP_ERR_INVALID, "sgp_characters_jump: no such character");      // (all or nothing)
+	for (uint32_t i = 0; i < n; ++i) { CharDrive& dr = cs->drive[ids[i]]; dr.jump_time = cur_time; dr.jump_serial++; }
+	if (n) cs->drive.dirty = true;
+	return SGP_OK;
+}
+
+static int characters_update(sgp_characters* cs, const char* fn, float dt, double cur_time)
+{
+	{ int r = batch_update_admit(cs, fn, "characters", std::isfinite(dt) && dt > 0.0f, "positive"); if (r != SGP_OK) return r; }
 	sgp_world* w = cs->w;
 	{ int r = cs->slots.empty() ? flush_cmds(w) : query_prelude(w); if (r != SGP_OK) return r; }      // (an empty batch applies the edits and leaves the grid alone)
 	if (cs->slots.empty()) return SGP_OK;
 	if (!cs->dv_valid || memcmp(&cs->dv[0], &w->dv, sizeof(DV)) != 0) { memcpy(&cs->dv[0], &w->dv, sizeof(DV)); cs->dv.dirty = cs->dv_valid = true; }
 	{ int r = cs->update_stage(); if (r != SGP_OK) return r; }
 	const CharBufs b = chars_bufs(cs);
-	launch_characters_update(cs->dv.d(), b, dt, w->stream);
+	const CharDriveArgs drive = { cs->drive.d(), cs->d_dst, cur_time, w->h_sp->water_enabled, w->h_sp->water_z };
+	launch_characters_update(cs->dv.d(), b, dt, cs->n_driven ? &drive : nullptr, w->stream);
 	launch_characters_push(w->dv, b, w->stream);
 	return cs->update_end();
 }
 
+// (no clock: one for which no jump window is open -- infinitely late)
+SGP_API int sgp_characters_update(sgp_characters* cs, float dt) { return characters_update(cs, "sgp_characters_update", dt, std::numeric_limits<double>::infinity()); }
+SGP_API int sgp_characters_update_at(sgp_characters* cs, float dt, double cur_time)
+{
+	if (!std::isfinite(cur_time)) return fail(SGP_ERR_INVALID, "sgp_characters_update_at: non-finite time");
+	return characters_update(cs, "sgp_characters_update_at", dt, cur_time);
+}
+
 SGP_API int sgp_characters_checkpoint(sgp_characters* cs, sgp_batch_checkpoint** io) { return batch_checkpoint(cs, SGP_BATCH_CHARACTERS, "sgp_characters_checkpoint", io); }
-SGP_API int sgp_characters_rollback(sgp_characters* cs, const sgp_batch_checkpoint* cp) { return batch_rollback(cs, SGP_BATCH_CHARACTERS, "sgp_characters_rollback", cp); }
+SGP_API int sgp_characters_rollback(sgp_characters* cs, const sgp_batch_checkpoint* cp)
+{
+	const int r = batch_rollback(cs, SGP_BATCH_CHARACTERS, "sgp_characters_rollback", cp);
+	if (r == SGP_OK) cs->count_driven();      // (the drive records are the capture's again)
+	return r;
+}
+
+// host edits pending and no update to carry them: they reach the device's states
+static int chars_sync(sgp_characters* cs)
+{
+	if (!cs->rec.dirty && !cs->in.dirty && !cs->drive.dirty) return (int)SGP_OK;
+	{ int r = cs->upload(); if (r != SGP_OK) return r; }
+	launch_characters_sync(chars_bufs(cs), cs->drive.d(), cs->d_dst, cs->w->stream);
+	return (int)SGP_OK;
+}
+
+SGP_API int sgp_characters_get_drive_states(sgp_characters* cs, uint32_t first, uint32_t n, sgp_character_drive_state* out)
+{
+	const CharDriveState* hs;
+	const int rc = batch_read_states(cs, "sgp_characters_get_drive_states", &sgp_characters::d_dst, first, n, out, &hs, [cs] { return chars_sync(cs); });
+	if (rc != SGP_OK || !hs) return rc;
+	for (uint32_t i = 0; i < n; ++i) {
+		sgp_character_drive_state& o = out[i];
+		memset(&o, 0, sizeof(o));
+		if (!char_live(cs, first + i)) continue;
+		const CharDriveState& s = hs[i];
+		memcpy(o.cam_pos, s.cam_pos, 12); o.campos_z_delta = s.campos_z_delta; memcpy(o.last_xy_plane_vel_rel_ground, s.last_xy, 12);
+		o.fraction_submerged = s.fraction_submerged; o.on_ground = s.on_ground; o.jumped = s.jumped; o.num_jumps = s.num_jumps;
+	}
+	return SGP_OK;
+}
 
 SGP_API int sgp_characters_get_states(sgp_characters* cs, uint32_t first, uint32_t n, sgp_character_state* out)
 {
 	const CharState* hs;
-	const int rc = batch_read_states(cs, "sgp_characters_get_states", &sgp_characters::d_st, first, n, out, &hs, [cs] {
-		if (!cs->rec.dirty && !cs->in.dirty) return (int)SGP_OK;
-		{ int r = cs->upload(); if (r != SGP_OK) return r; }      // (host edits pending and no update to carry them)
-		launch_characters_sync(chars_bufs(cs), cs->w->stream);
-		return (int)SGP_OK;
-	});
+	const int rc = batch_read_states(cs, "sgp_characters_get_states", &sgp_characters::d_st, first, n, out, &hs, [cs] { return chars_sync(cs); });
 	if (rc != SGP_OK || !hs) return rc;
 	const sgp_world* w = cs->w;
 	for (uint32_t i = 0; i < n; ++i) {

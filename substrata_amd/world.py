@@ -148,6 +148,30 @@ class Characters(_Batch):
         self._w._check(self._w._fn("characters_drain_contacts")(self._h, out.ctypes.data, cap, C.byref(n)), "characters_drain_contacts")
         return out[:min(n.value, cap)].copy()
 
+    # driven characters: PlayerPhysics::update's rule on the device
+    def default_drive(self):
+        d = abi.CharacterDrive()
+        self._w._fn("default_character_drive")(C.byref(d))
+        return d
+
+    def set_drive(self, first, drives):
+        """drives: array of abi.character_drive_dtype for characters first, first + 1, ...; in force until set again"""
+        drives = np.ascontiguousarray(drives, dtype=abi.character_drive_dtype).reshape(-1)
+        self._w._check(self._w._fn("characters_set_drive")(self._h, int(first), len(drives), drives.ctypes.data), "characters_set_drive")
+
+    def jump(self, ids, cur_time):
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        self._w._check(self._w._fn("characters_jump")(self._h, ids.ctypes.data, len(ids), float(cur_time)), "characters_jump")
+
+    def update_at(self, dt, cur_time):
+        self._w._check(self._w._fn("characters_update_at")(self._h, float(dt), float(cur_time)), "characters_update_at")
+
+    def drive_states(self, first=0, n=None):
+        n = self.capacity - first if n is None else int(n)
+        out = np.zeros(n, dtype=abi.character_drive_state_dtype)
+        self._w._check(self._w._fn("characters_get_drive_states")(self._h, int(first), n, out.ctypes.data), "characters_get_drive_states")
+        return out
+
 
 class Movers(_Batch):
     """A batch of path and move-to controllers of one world (sgp_movers): update() enqueues and returns; states() waits."""
